@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """CenterMask2 V2-39-eSE-FPN inference throughput on MI355X (BASELINE.json metric: images/sec at 3x800x1280).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the whole hot path (VoVNetV2-39-eSE + FPN -> FCOS head/decode/NMS/top-50 -> CenterROIHeads with
 SAG-Mask + MaskIoU) over one batch of 8 synthetic 3x800x1280 images per GPU, inputs already resident in HBM,
 results left as padded device buffers.  Images shard across ranks (weak scaling, no data-path collective inside the
 model); each step ends with one RCCL all-gather of the fixed-stride per-image results.
+--dump-outputs DIR: rank 0 writes what the last timed step returned (the padded result buffers and the gathered records) as DIR/<name>.npy,
+so that two builds can be compared output for output on the same seeded inputs (dump_outputs below).
 Rank 0 prints ONE JSON line, with
   roofline     — the dominant kernel (the fp32 Winograd F(4x4,3x3) conv on the matrix pipe) measured live with HIP events on the launch stream;
   cpu_baseline — the oracle (CPU restatement of the reference path, kind "port") timed on this host's cores on a bounded sample.
@@ -28,6 +30,7 @@ PEAK_F32_MATRIX_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 
 PEAK_HBM_GBS = 8000.0
 PEAK_16BIT_MATRIX_TFLOPS = 2010.0  # v_mfma_f32_32x32x16_{bf16,f16} measured on random operands (tools/probe/mfma_power_bf16.hip; nominal dense 2516 at 2.4 GHz): the pipe of the opt-in split kernels
 PROFILE_ROUND = "r03"            # prefix of the PMC summaries under profiles/ this bench quotes
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
 
 
 def build(conv_body, device):
@@ -93,6 +96,29 @@ def timed_steps(step, steps: int, warmup: int, world: int, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed, out
+
+
+def dump_outputs(dump_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """Write every tensor of `arrays` as <dump_dir>/<name>.npy: float64 tensors as float64, other floating tensors as float32, integer
+    and bool tensors as float64 (exact).  If together they exceed `limit` bytes, each array keeps the same fraction of its elements,
+    flattened: the elements at the sorted first m entries of torch.randperm(numel) drawn from a generator seeded with `seed`, so the
+    sample depends on the shapes alone and two builds run with the same arguments write the same elements.  Returns {name: shape written}."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.to(torch.float32) if t.is_floating_point() and t.dtype != torch.float64 else t.to(torch.float64)
+    total = sum(t.numel() * t.element_size() for t in host.values())
+    os.makedirs(dump_dir, exist_ok=True)
+    written = {}
+    for name, t in sorted(host.items()):
+        if total > limit:
+            n = t.numel()
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:n * limit // total].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(dump_dir, name + ".npy"), t.numpy())
+        written[name] = list(t.shape)
+    return written
 
 
 def collective_description(rec_floats: int, world: int) -> str:
@@ -399,7 +425,11 @@ def main():
     ap.add_argument("--path", choices=("fp32", "split"), default="fp32",
                     help="fp32 (default): every conv on the fp32 matrix instruction.  split: the OPT-IN kernels — fp32 results from two fp16 pieces per operand on the "
                          "16-bit matrix instructions, table tuned/*_split3.json (DESIGN section 3 'Split products'); `dtype` and `config.path` of the line say so")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -478,6 +508,11 @@ def main():
             return g_out, g_rec
 
         elapsed, (out, rec) = timed_steps(step, args.steps, args.warmup, world, dev)
+        dumped = None
+        if args.dump_outputs and rank == 0:      # before the extras below replay the step into the same buffers
+            arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+            arrays["records"] = exchange.gathered if world > 1 else rec
+            dumped = dump_outputs(args.dump_outputs, arrays)
 
         # ---- beyond the contract's K steps (extra keys, never `value`): a sustained run and a run fed from the host -------------
         sustained = fed = plugin_api = None
@@ -580,6 +615,8 @@ def main():
                            "weights": "seeded random-init, reference state-dict keys"},
                 "roofline": roof,
             }
+            if dumped is not None:
+                result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
             if sustained is not None:
                 result["sustained"] = sustained
                 result["fed"] = fed

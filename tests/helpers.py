@@ -10,6 +10,30 @@ def golden(name):
     return torch.load(os.path.join(GOLDEN, name + ".pt"), weights_only=True)
 
 
+def golden_f64():
+    """The reference's outputs computed in float64 (tests/golden/make_golden_f64.py), float64 tensors nested like the fp32 fixtures
+    they correct: {fixture name: {key: tensor | {index: tensor} | {key: ...}}}.  reference_f64.npz holds, per output, int8 steps from the
+    fp32 fixture's value and the step, STEP * max(1, max|output|): a decoded value is within half a step (5e-8 of that scale) of the
+    float64 output."""
+    import numpy as np
+    z = np.load(os.path.join(GOLDEN, "reference_f64.npz"))
+    fixtures, out = {}, {}
+    for key in z.files:
+        if key.startswith("step."):
+            continue
+        path = key.split(".")
+        if path[0] not in fixtures:
+            fixtures[path[0]] = golden(path[0])
+        base, node = fixtures[path[0]], out
+        for p in path[:-1]:
+            node = node.setdefault(int(p) if p.isdigit() else p, {})
+        for p in path[1:]:
+            base = base[int(p)] if isinstance(base, list) else base[p]
+        last = path[-1]
+        node[int(last) if last.isdigit() else last] = base.double() + torch.from_numpy(z[key]).double() * float(z["step." + key])
+    return out
+
+
 OBSERVED = {}      # what -> largest absolute error seen this session (printed by conftest at the end of a run: the margin on record)
 
 

@@ -4,11 +4,17 @@ import torch
 from centermask2_amd import synthetic as S
 from oracle import centermask_oracle as O
 
-from .helpers import close, golden
+from .helpers import close, golden, golden_f64
 
 
 def _sd():
     return S.make_synthetic_state_dict("V-39-eSE", 0)
+
+
+def _f64(sd):
+    """Convolutions run in float64 against reference_f64.npz (tests/golden/make_golden_f64.py): in float32 the order of their sums,
+    and with it the last bits, depends on the host CPU's vector width and thread count."""
+    return {k: v.double() for k, v in sd.items()}
 
 
 def test_state_dict_keys_equal_reference_listing():
@@ -19,32 +25,32 @@ def test_state_dict_keys_equal_reference_listing():
 
 
 def test_vovnet_odd_size_ceil_mode():
-    g = golden("vovnet_odd")
-    out = O.vovnet_forward(_sd(), g["x"])
+    g, ref = golden("vovnet_odd"), golden_f64()["vovnet_odd"]
+    out = O.vovnet_forward(_f64(_sd()), g["x"].double())
     for k in ("stage3", "stage4", "stage5"):
-        close(out[k], g[k], 1e-6, k)
+        close(out[k], ref[k], 1e-6, k)
 
 
 def test_backbone_fpn_small():
-    g = golden("backbone_small")
-    out = O.backbone_forward(_sd(), g["x"])
+    g, ref = golden("backbone_small"), golden_f64()["backbone_small"]
+    out = O.backbone_forward(_f64(_sd()), g["x"].double())
     for k in ("p3", "p4", "p5", "p6", "p7"):
-        close(out[k], g[k], 1e-6, k)
+        close(out[k], ref[k], 1e-6, k)
 
 
 def test_other_vovnet_bodies_incl_depthwise():
     """V-19-slim-dw / V-19-dw (dw_conv3x3 + conv_reduction, vovnet.py:110-130,284-288), V-19-slim, V-19 and V-57
     (vovnet.py:50-88)."""
-    g = golden("vovnet_bodies")
-    assert set(g.keys()) == {"V-19-slim-dw-eSE", "V-19-dw-eSE", "V-19-slim-eSE", "V-19-eSE", "V-57-eSE"}
+    g, ref64 = golden("vovnet_bodies"), golden_f64()["vovnet_bodies"]
+    assert set(g.keys()) == {"V-19-slim-dw-eSE", "V-19-dw-eSE", "V-19-slim-eSE", "V-19-eSE", "V-57-eSE"} == set(ref64.keys())
     for body, case in g.items():
-        sd = S.make_synthetic_state_dict(body, 0)
-        out = O.vovnet_forward(sd, case["x"], conv_body=body)
+        sd, ref = _f64(S.make_synthetic_state_dict(body, 0)), ref64[body]
+        out = O.vovnet_forward(sd, case["x"].double(), conv_body=body)
         for k in ("stage3", "stage4", "stage5"):
-            close(out[k], case[k], 1e-6, body + " " + k)
-        out = O.backbone_forward(sd, case["x32"], conv_body=body)
+            close(out[k], ref[k], 1e-6, body + " " + k)
+        out = O.backbone_forward(sd, case["x32"].double(), conv_body=body)
         for k in ("p3", "p4", "p5", "p6", "p7"):
-            close(out[k], case[k], 1e-6, body + " " + k)
+            close(out[k], ref[k], 1e-6, body + " " + k)
 
 
 def test_v99_end_to_end_800x1280():
@@ -63,15 +69,15 @@ def test_v99_end_to_end_800x1280():
 
 
 def test_fcos_head_decode_nms_small():
-    g, bb = golden("fcos_small"), golden("backbone_small")
-    sd = dict(_sd())
+    g, bb, ref = golden("fcos_small"), golden("backbone_small"), golden_f64()["fcos_small"]
+    sd = _f64(_sd())
     key = "proposal_generator.fcos_head.cls_logits.bias"
     sd[key] = sd[key] + float(g["cls_bias_shift"])
-    lg, reg, ctr = O.fcos_head_forward(sd, [bb[k] for k in ("p3", "p4", "p5", "p6", "p7")])
+    lg, reg, ctr = O.fcos_head_forward(sd, [bb[k].double() for k in ("p3", "p4", "p5", "p6", "p7")])
     for l in range(5):
-        close(lg[l], g["logits"][l], 1e-6)
-        close(reg[l], g["reg"][l], 1e-6)
-        close(ctr[l], g["ctr"][l], 1e-6)
+        close(lg[l], ref["logits"][l], 1e-6)
+        close(reg[l], ref["reg"][l], 1e-6)
+        close(ctr[l], ref["ctr"][l], 1e-6)
     props, cands = O.fcos_predict_proposals(g["logits"], g["reg"], g["ctr"], return_candidates=True)
     for i in range(2):
         r = g["img{}".format(i)]
@@ -81,18 +87,24 @@ def test_fcos_head_decode_nms_small():
         close(props[i]["scores"], r["scores"], 1e-7)
 
 
-def test_roi_heads_crafted_boxes():
-    g, bb = golden("roi_crafted"), golden("backbone_small")
+def test_roi_heads_crafted_boxes(monkeypatch):
+    g, bb, ref = golden("roi_crafted"), golden("backbone_small"), golden_f64()["roi_crafted"]
     props = [dict(boxes=g["img{}".format(i)]["boxes"], classes=g["img{}".format(i)]["classes"], scores=g["img{}".format(i)]["scores"],
                   locations=g["img{}".format(i)]["boxes"][:, :2]) for i in range(2)]
     res, inter = O.roi_heads_forward(_sd(), bb, props, [(64, 96)] * 2, return_intermediates=True)
     assert torch.equal(inter["levels"], g["levels"])
     close(inter["roi_feat"], g["roi_feat"], 1e-6)
-    close(inter["mask_logits"], g["mask_logits"], 1e-6)
-    close(inter["maskiou"], g["maskiou"], 1e-6)
+    # the heads in float64, through the same roi_heads_forward, on the reference's pooled features (exact in float64)
+    roi_feat, levels = g["roi_feat"].double(), inter["levels"]
+    monkeypatch.setattr(O, "roi_pooler", lambda feats, boxes, image_sizes: (roi_feat, levels))
+    props = [dict(p, scores=p["scores"].double()) for p in props]
+    res, inter = O.roi_heads_forward(_f64(_sd()), {k: bb[k].double() for k in ("p3", "p4", "p5")}, props, [(64, 96)] * 2,
+                                     return_intermediates=True)
+    close(inter["mask_logits"], ref["mask_logits"], 1e-6)
+    close(inter["maskiou"], ref["maskiou"], 1e-6)
     for i in range(2):
-        close(res[i]["pred_masks"], g["img{}".format(i)]["pred_masks"], 1e-6)
-        close(res[i]["mask_scores"], g["img{}".format(i)]["mask_scores"], 1e-6)
+        close(res[i]["pred_masks"], ref["img{}".format(i)]["pred_masks"], 1e-6)
+        close(res[i]["mask_scores"], ref["img{}".format(i)]["mask_scores"], 1e-6)
 
 
 def test_pooler_by_area_and_roialign_v1():

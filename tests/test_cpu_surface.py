@@ -283,6 +283,38 @@ def test_bench_exchange_and_timed_region_world_size_2_gloo(tmp_path):
     assert all(p.returncode == 0 for p in procs), outs
 
 
+def test_bench_dump_outputs_dtypes_and_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: float tensors as float32 (float64 kept), integers and bools as exact float64; above the byte limit every
+    array keeps the same seeded sample of its elements, identical from call to call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(7)
+    arrays = dict(score=torch.rand((8, 50), generator=g), cls=torch.randint(0, 80, (8, 50), generator=g),
+                  overflow=torch.tensor([False, True]), box=torch.rand((8, 50, 4), generator=g, dtype=torch.float64),
+                  pred_masks=torch.rand((8, 50, 1, 28, 28), generator=g).half())
+    shapes = bench.dump_outputs(str(tmp_path / "full"), arrays)
+    assert shapes == {k: list(v.shape) for k, v in arrays.items()}
+    back = {k: np.load(str(tmp_path / "full" / (k + ".npy"))) for k in arrays}
+    assert back["score"].dtype == np.float32 and np.array_equal(back["score"], arrays["score"].numpy())
+    assert back["cls"].dtype == np.float64 and np.array_equal(back["cls"], arrays["cls"].numpy().astype(np.float64))
+    assert back["overflow"].dtype == np.float64 and back["overflow"].tolist() == [0.0, 1.0]
+    assert back["box"].dtype == np.float64 and back["pred_masks"].dtype == np.float32
+
+    limit = 64 * 1024
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, limit=limit)
+    sizes = 0
+    for k, v in arrays.items():
+        a, b = (np.load(str(tmp_path / run / (k + ".npy"))) for run in ("a", "b"))
+        assert np.array_equal(a, b), k
+        sizes += a.nbytes
+        flat = back[k].reshape(-1)
+        assert a.ndim == 1 and a.size < flat.size, k
+        assert np.isin(a, flat).all(), k            # a sample of the array's own elements
+    assert 0 < sizes <= limit
+
+
 def test_average_precision_known_answers():
     from centermask2_amd.evaluation import average_precision, box_iou
     gt = [dict(boxes=torch.tensor([[0., 0., 10., 10.], [20., 20., 40., 40.]]), classes=torch.tensor([1, 2]))]
