@@ -766,13 +766,7 @@ static int launch(ConvArgs& a, int grid_y, hipStream_t st) {
     if (a.ksplit > 1 && (a.nprob != 1 || a.res_mode == 2 || !a.ws || vchunks % (2 * a.ksplit)))
         return fail(CMK_EINVAL, "conv: split-K needs one problem, a workspace, no upsampled residual and K chunks %% (2*splitk) == 0%s", "");
     hipLaunchKernelGGL(kern, dim3(((blocks + 7) / 8) * 8 * grid_y, a.ksplit), dim3(256), G::LDS_BYTES, st, a);
-    int rc = check_launch("conv_igemm");
-    if (rc || a.ksplit == 1) return rc;
-    const ConvProblem& p = a.p[0];
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((p.total_pix * (a.cout_pad >> 2) + 255) / 256, 256L * 32)), dim3(256), 0, st, a.ws, a.ksplit, p.total_pix,
-                       a.cout_pad, p.scale, p.shift, a.Cout, a.relu_upto, a.res_mode == 1 ? a.res : nullptr, a.res_cs, a.res_co, p.y, a.y_cs,
-                       a.y_co);
-    return check_launch("splitk_reduce");
+    return check_launch("conv_igemm");     // split-K: run() reduces the partial sums
 }
 
 // cost of running `blocks` equal workgroups with `resident` per CU on 256 CUs: full rounds keep every CU at `resident`
@@ -798,8 +792,10 @@ static bool variant_ok(int taps, int stride, int cout32, int wm, int sc, int wn)
     return true;
 }
 
+static int out_size(int h, int stride) { return stride == 1 ? h : (h - 1) / 2 + 1; }     // k3 p1 s2: floor((H+2-3)/2)+1
+
 // Default choice when the caller gives no tuned variant: minimise modelled time over the menu.
-static Variant choose_variant(const ConvArgs& a, int taps, int stride, int cout32) {
+static Variant choose_variant(const cmk_conv_desc* descs, int n, int taps, int stride, int cout32) {
     Variant best{1, taps == 1 ? 32 : 16, cout32 <= 7 ? cout32 : 4};
     double best_cost = 1e300;
     const int cout_pad32 = cout32 <= 7 ? cout32 : cdiv(cout32, 4) * 4;
@@ -810,8 +806,10 @@ static Variant choose_variant(const ConvArgs& a, int taps, int stride, int cout3
                 const int sr = 32 / sc, bm = 128 * wm;
                 const int th = taps == 9 ? sr * 4 * wm : 1, tw = taps == 9 ? sc : bm;
                 long blocks = 0;
-                for (int i = 0; i < a.nprob; ++i)
-                    blocks += taps == 9 ? (long)a.p[i].N * cdiv(a.p[i].Ho, th) * cdiv(a.p[i].Wo, tw) : (a.p[i].total_pix + bm - 1) / bm;
+                for (int i = 0; i < n; ++i) {
+                    const int ho = out_size(descs[i].H, stride), wo = out_size(descs[i].W, stride);
+                    blocks += taps == 9 ? (long)descs[i].N * cdiv(ho, th) * cdiv(wo, tw) : ((long)descs[i].N * ho * wo + bm - 1) / bm;
+                }
                 blocks *= cout_pad32 / wn;
                 const int apix = taps == 9 ? ((th - 1) * stride + 3) * ((tw - 1) * stride + 3) : bm;
                 const int abytes = apix * PST * 4, bbytes = 32 * wn * PST * 4;
@@ -876,13 +874,37 @@ static int validate(const cmk_conv_desc* d) {
     return CMK_OK;
 }
 
+// the checks of cmk_conv2d_nhwc_multi, on the caller's own tune fields
+static int validate_multi(const cmk_conv_desc* descs, int n) {
+    if (!descs || n < 1 || n > MAXP) return fail(CMK_EINVAL, "conv_multi: need 1..%s%ld problems", "", MAXP);
+    bool same_w = true;
+    for (int i = 0; i < n; ++i) {
+        int rc = validate(&descs[i]);
+        if (rc) return rc;
+        const cmk_conv_desc *a = &descs[0], *b = &descs[i];
+        same_w = same_w && b->w == a->w && b->w_wino == a->w_wino && b->w_wino6 == a->w_wino6 && b->w_split == a->w_split && b->w_splith == a->w_splith;
+        if (b->Cin != a->Cin || b->Cout != a->Cout || b->ksize != a->ksize || b->stride != a->stride ||
+            b->relu_upto != a->relu_upto || b->in_relu != a->in_relu || b->x_cs != a->x_cs || b->x_co != a->x_co || b->y_cs != a->y_cs ||
+            b->y_co != a->y_co || b->res_mode != 0 || b->tune_wm != a->tune_wm || b->tune_sc != a->tune_sc || b->tune_wn != a->tune_wn || (b->in_scale == nullptr) != (a->in_scale == nullptr) ||
+            b->gn_ws != a->gn_ws || b->gn_groups != a->gn_groups || b->splitk > 1 || b->pool_ws)
+            return fail(CMK_EINVAL, "conv_multi: problems must share channels/views/flags and carry no residual%s", "");
+    }
+    // problems with different weights (the cls and the bbox tower of the FCOS head, fcos.py:227-231, in one launch) and more than 5 problems:
+    // the F(4x4) kernels only, which take the packed weights per problem
+    if ((!same_w || n > 5) && (descs[0].tune_wm != 6 || descs[0].tune_wn != 1) && descs[0].tune_wm != 11)
+        return fail(CMK_EINVAL, "conv_multi: different weights per problem / more than 5 problems need tune_wm 6, tune_wn 1 (the F(4x4) map kernels)%s", "");
+    for (int i = 0; i < n; ++i)
+        if (descs[0].tune_wm == 6 && !descs[i].w_wino6) return fail(CMK_EINVAL, "conv_multi: w_wino6 missing%s", "");
+    return CMK_OK;
+}
+
 static void fill_problem(ConvProblem& p, const cmk_conv_desc* d) {
     p.x = d->x; p.y = d->y; p.scale = d->scale; p.shift = d->shift;
     p.in_scale = d->in_scale; p.in_shift = d->in_shift;
     p.w = d->w_wino6;
     p.N = d->N; p.H = d->H; p.W = d->W;
-    p.Ho = d->stride == 1 ? d->H : (d->H - 1) / 2 + 1;  // k3 p1 s2: floor((H+2-3)/2)+1
-    p.Wo = d->stride == 1 ? d->W : (d->W - 1) / 2 + 1;
+    p.Ho = out_size(d->H, d->stride);
+    p.Wo = out_size(d->W, d->stride);
     p.tiles_h = p.tiles_w = p.tile_begin = 0;
     p.total_pix = (long)p.N * p.Ho * p.Wo;
 }
@@ -933,62 +955,71 @@ static int gather_mt(const cmk_conv_desc* d, int n) {
     return wg4 >= 1024 ? 4 : 0;          // measured (tools/bench_ga.py): stem_3 1.28x conv_igemm; the 14 -> 7 maskiou conv and P6/P7 stay on its split-K gather form
 }
 
-// the pointwise kernel's launch, followed by the split-K reduction when it left partial sums
-static int run_pointwise(ConvArgs& a, int mt, hipStream_t st) {
-    int rc = launch_pw(a, mt, st);
-    if (rc || a.ksplit <= 1) return rc;
-    const ConvProblem& p = a.p[0];
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((p.total_pix * (a.cout_pad >> 2) + 255) / 256, 256L * 32)), dim3(256), 0, st, a.ws, a.ksplit, p.total_pix,
-                       a.cout_pad, p.scale, p.shift, a.Cout, a.relu_upto, a.res_mode == 1 ? a.res : nullptr, a.res_cs, a.res_co, p.y, a.y_cs,
-                       a.y_co);
-    return check_launch("splitk_reduce");
+// The variant a launch of these (validated) descriptors runs: the caller's tune fields as given, or the untuned default when they are all
+// zero.  gn: the launch produces fused GroupNorm statistics (gn_ws set, or cmk_conv_resolve's with_gn_stats) — the forms that do are
+// preferred; when none applies, the choice among the others.
+static Variant resolve(const cmk_conv_desc* descs, int n, bool gn) {
+    const cmk_conv_desc* d = &descs[0];
+    if (d->tune_wm || d->tune_sc || d->tune_wn) return Variant{d->tune_wm, d->tune_sc, d->tune_wn};     // the caller measured and picked one
+    // the 2-WG/CU Winograd form wins on every 3x3 stride-1 shape measured (tools/bench_wino.py), so take it whenever the caller packed the
+    // transformed weights; otherwise the direct-kernel cost model decides
+    const bool wino = d->ksize == 3 && d->stride == 1 && d->res_mode == 0 && !d->in_relu && d->Cin >= 32 && d->splitk <= 1;
+    // F(4x4,3x3) where its 12x40 tiles are reasonably full and there are enough of them (measured on the model's maps, tools/bench_wino6.py:
+    // 1.1-1.5x the 2x2 form down to 25x40 maps, 0.4x on 14x14 RoI maps whose tiles are 20 % full)
+    if (wino && d->w_wino6 && !(d->Cin & 7)) {
+        double px = 0.0, covered = 0.0;
+        long wgs = 0;
+        for (int i = 0; i < n; ++i) {
+            const long t = (long)descs[i].N * cdiv(descs[i].H, 12) * cdiv(descs[i].W, 40);
+            px += (double)descs[i].N * descs[i].H * descs[i].W;
+            covered += (double)t * 480.0;
+            wgs += t * cdiv(d->Cout, 32);
+        }
+        // maps of at most 16 x 14 (the 14x14 RoI features): two whole maps per workgroup instead of 12x40 tiles that would be 20 % full
+        if (n == 1 && d->H <= 16 && d->W <= 14 && !gn && (long)cdiv(d->N, 2) * cdiv(d->Cout, 32) >= 256) return Variant{6, 16, 2};
+        if (px >= 0.55 * covered && wgs >= 256) return Variant{6, 16, 1};
+    }
+    if (wino && d->w_wino) return Variant{5, 16, 2};
+    const int cout32 = (d->Cout + 31) / 32;
+    const int ho = out_size(d->H, d->stride), wo = out_size(d->W, d->stride);
+    // stride-2 3x3 on a map of at most 16x16 outputs (maskiou conv4 14->7, P6/P7): the spatial tiles would be mostly empty
+    if (d->ksize == 3 && d->stride == 2 && n == 1 && d->res_mode != 2 && !d->in_scale && ho <= 16 && wo <= 16) {
+        const int cout_pad32 = cout32 <= 7 ? cout32 : cdiv(cout32, 4) * 4;
+        const long total_pix = (long)d->N * ho * wo;
+        return Variant{7, 32, (cout_pad32 % 4 == 0 && total_pix >= 8192) ? 4 : (cout_pad32 % 2 == 0 && total_pix >= 2048) ? 2 : 1};
+    }
+    if (const int mt = pointwise_mt(d, n)) return Variant{8, 32, mt};
+    if (const int mt = gather_mt(d, n)) return Variant{9, 32, mt};
+    return choose_variant(descs, n, d->ksize * d->ksize, d->stride, cout32);
 }
 
-static int run(const cmk_conv_desc* descs, int n, void* stream) {
-    const cmk_conv_desc* d = &descs[0];
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nprob = n;
-    for (int i = 0; i < n; ++i) fill_problem(a.p[i], &descs[i]);
-    a.w = d->w; a.res = d->res;
-    a.Cin = d->Cin; a.Cout = d->Cout;
-    a.x_cs = d->x_cs; a.x_co = d->x_co; a.y_cs = d->y_cs; a.y_co = d->y_co;
-    a.res_cs = d->res_cs; a.res_co = d->res_co; a.res_mode = d->res_mode; a.Hr = d->Hr; a.Wr = d->Wr;
-    if (a.res_mode == 2 && (a.Hr * 2 < a.p[0].Ho || a.Wr * 2 < a.p[0].Wo)) return fail(CMK_EINVAL, "conv: upsampled residual too small%s", "");
-    a.relu_upto = d->relu_upto; a.in_relu = d->in_relu;
+// The launch of the explicit variant d->tune_wm/sc/wn (d: the first descriptor, resolved).  Returns with a.ksplit > 1 when the kernel left
+// split-K partial sums for run() to reduce.
+static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* descs, int n, hipStream_t st) {
     const int cout32 = (d->Cout + 31) / 32;
-    const int taps = d->ksize * d->ksize;
-    hipStream_t st = (hipStream_t)stream;
+    if (d->gn_ws) {                 // fused GroupNorm statistics: the Winograd forms and the direct fp16-split 3x3 produce them
+        if (d->tune_wm != 5 && d->tune_wm != 6 && d->tune_wm != 11)
+            return fail(CMK_EINVAL, "conv: fused GroupNorm statistics are only produced by the Winograd form%s", "");
+        int rc = setup_gn(a, d);
+        if (rc) return rc;
+    }
     if (d->tune_wm == 5) {          // Winograd F(2x2,3x3): 3x3 stride 1, no residual / input ReLU
         if (d->ksize != 3 || d->stride != 1 || d->res_mode != 0 || d->in_relu || !d->w_wino)
             return fail(CMK_EINVAL, "conv: Winograd variant not available for this conv%s", "");
         if (d->splitk > 1) return fail(CMK_EINVAL, "conv: split-K is a direct-kernel feature%s", "");
-        if (d->gn_ws) {
-            int rc = setup_gn(a, d);
-            if (rc) return rc;
-        }
         a.w = d->w_wino;
         return launch_wino(a, st);
     }
     if (d->tune_wm == 6) {          // Winograd F(4x4,3x3): same conditions, its own packed weights
         if (d->ksize != 3 || d->stride != 1 || d->res_mode != 0 || d->in_relu || !d->w_wino6 || (d->Cin & 7))
             return fail(CMK_EINVAL, "conv: Winograd F(4x4,3x3) variant not available for this conv%s", "");
-        if (d->gn_ws) {
-            int rc = setup_gn(a, d);
-            if (rc) return rc;
-        }
         a.w = d->w_wino6;
         a.ws = d->splitk_ws;          // split-K slabs (instrumented W6_TRACE builds: a stamp buffer)
         a.ksplit = d->splitk > 1 ? d->splitk : 1;
         a.cout_pad = cmk_conv_cout_pad(d->Cout);
         if (a.ksplit > 1) {           // F(4x4) with split-K (32-cout form, map tiles): partial sums + the reduce kernel of the direct path
             if (d->tune_sc == 64 || d->tune_wn != 1 || n != 1) return fail(CMK_EINVAL, "conv: Winograd split-K needs tune_sc 16, tune_wn 1, one problem%s", "");
-            int rc = launch_wino6(a, 0, st);
-            if (rc) return rc;
-            const ConvProblem& p = a.p[0];
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((p.total_pix * (a.cout_pad >> 2) + 255) / 256, 256L * 32)), dim3(256), 0, st, a.ws, a.ksplit,
-                               p.total_pix, a.cout_pad, p.scale, p.shift, a.Cout, a.relu_upto, (const float*)nullptr, 0, 0, p.y, a.y_cs, a.y_co);
-            return check_launch("splitk_reduce");
+            return launch_wino6(a, 0, st);
         }
         if (d->tune_wn != 1 && d->tune_wn != 2) return fail(CMK_EINVAL, "conv: tune_wm 6 takes tune_wn 1 (12x40 map tiles) or 2 (pairs of RoI maps up to 16x14)%s", "");
         if (d->tune_sc == 64) return launch_wino6s(a, d->tune_wn == 2 ? 1 : 0, st);      // 64 couts per workgroup, shared frequency image
@@ -1001,9 +1032,8 @@ static int run(const cmk_conv_desc* descs, int n, void* stream) {
     if (d->tune_wm == 8) {                             // pointwise GEMM kernel (conv_pw.hip); tune_wn = accumulator rows per wave
         if (d->ksize != 1 || cout32 <= 7) return fail(CMK_EINVAL, "conv: pointwise variant needs a 1x1 conv with Cout > 224%s", "");
         a.cout_pad = cdiv(cout32, 4) * 128;
-        a.gn_ws = d->gn_ws;
         if (a.ksplit > 1 && !pointwise_mt(d, n)) return fail(CMK_EINVAL, "conv: pointwise variant: split-K not available for this conv%s", "");
-        return run_pointwise(a, d->tune_wn, st);
+        return launch_pw(a, d->tune_wn, st);
     }
     if (d->tune_wm == 10) {                            // opt-in: the pointwise GEMM from bf16-split products (fp32-accurate, cmk.h w_split)
         if (!(d->ksize == 1 ? pointwise_mt(d, n) : gather_mt(d, n)))
@@ -1027,10 +1057,6 @@ static int run(const cmk_conv_desc* descs, int n, void* stream) {
     if (d->tune_wm == 11) {                            // opt-in: direct 3x3 conv on bf16-split products (conv_sp3.hip); tune_sc = pieces, tune_wn = geometry
         if (d->ksize != 3 || d->stride != 1 || !d->w_splith || d->splitk > 1 || d->res_mode != 0 || d->in_relu || d->pool_ws)
             return fail(CMK_EINVAL, "conv: the direct fp16-split variant needs w_splith and a plain 3x3 stride-1 conv%s", "");
-        if (d->gn_ws) {
-            int rc = setup_gn(a, d);
-            if (rc) return rc;
-        }
         for (int i = 0; i < n; ++i) {
             if (!descs[i].w_splith || !(descs[i].w_splith_scale > 0.f)) return fail(CMK_EINVAL, "conv: w_splith / w_splith_scale missing%s", "");
             a.p[i].w = reinterpret_cast<const float*>(descs[i].w_splith);
@@ -1045,7 +1071,7 @@ static int run(const cmk_conv_desc* descs, int n, void* stream) {
         if (!mt) return fail(CMK_EINVAL, "conv: pointwise gather variant not available for this conv%s", "");
         a.cout_pad = cdiv(cout32, 4) * 128;
         a.ga_stride = d->stride;
-        return run_pointwise(a, mt, st);
+        return launch_pw(a, mt, st);
     }
     if (d->tune_wm == 7) {                             // gather form: 3x3 (stride 1|2) as a flattened-pixel GEMM over 9x the K chunks
         if (d->ksize != 3 || n != 1 || d->res_mode == 2 || d->in_scale || (d->tune_wn != 1 && d->tune_wn != 2 && d->tune_wn != 4))
@@ -1058,72 +1084,36 @@ static int run(const cmk_conv_desc* descs, int n, void* stream) {
         return d->tune_wn == 4 ? launch<1, 1, 1, 4, 32, true>(a, gy, st) : d->tune_wn == 2 ? launch<1, 1, 1, 2, 32, true>(a, gy, st)
                                                                                            : launch<1, 1, 1, 1, 32, true>(a, gy, st);
     }
-    Variant v;
-    if (d->tune_wm || d->tune_sc || d->tune_wn) {      // the caller measured and picked a variant
-        if (d->gn_ws) return fail(CMK_EINVAL, "conv: fused GroupNorm statistics are only produced by the Winograd form (tune_wm 5)%s", "");
-        v = Variant{d->tune_wm, d->tune_sc, d->tune_wn};
-        if (!variant_ok(taps, d->stride, cout32, v.wm, v.sc, v.wn)) return fail(CMK_EINVAL, "conv: variant not available for this shape%s", "");
-    } else {
-        // untuned default: the 2-WG/CU Winograd form wins on every 3x3 stride-1 shape measured (tools/bench_wino.py), so take it
-        // whenever the caller packed the transformed weights; otherwise the direct-kernel cost model decides
-        // F(4x4,3x3) where its 12x40 tiles are reasonably full and there are enough of them (measured on the model's maps, tools/bench_wino6.py:
-        // 1.1-1.5x the 2x2 form down to 25x40 maps, 0.4x on 14x14 RoI maps whose tiles are 20 % full)
-        if (d->ksize == 3 && d->stride == 1 && d->res_mode == 0 && !d->in_relu && d->w_wino6 && d->Cin >= 32 && !(d->Cin & 7) && d->splitk <= 1) {
-            double px = 0.0, covered = 0.0;
-            long wgs = 0;
-            for (int i = 0; i < n; ++i) {
-                const long t = (long)descs[i].N * cdiv(descs[i].H, 12) * cdiv(descs[i].W, 40);
-                px += (double)descs[i].N * descs[i].H * descs[i].W;
-                covered += (double)t * 480.0;
-                wgs += t * cdiv(d->Cout, 32);
-            }
-            // maps of at most 16 x 14 (the 14x14 RoI features): two whole maps per workgroup instead of 12x40 tiles that would be 20 % full
-            if (n == 1 && d->H <= 16 && d->W <= 14 && !d->gn_ws && (long)cdiv(d->N, 2) * cdiv(d->Cout, 32) >= 256) {
-                a.w = d->w_wino6;
-                return launch_wino6(a, 1, st);
-            }
-            if (px >= 0.55 * covered && wgs >= 256) {
-                if (d->gn_ws) {
-                    int rc = setup_gn(a, d);
-                    if (rc) return rc;
-                }
-                a.w = d->w_wino6;
-                return launch_wino6(a, 0, st);
-            }
-        }
-        if (d->ksize == 3 && d->stride == 1 && d->res_mode == 0 && !d->in_relu && d->w_wino && d->Cin >= 32 && d->splitk <= 1) {
-            if (d->gn_ws) {
-                int rc = setup_gn(a, d);
-                if (rc) return rc;
-            }
-            a.w = d->w_wino;
-            return launch_wino(a, st);
-        }
-        if (d->gn_ws) return fail(CMK_EINVAL, "conv: fused GroupNorm statistics are only produced by the Winograd form%s", "");
-        // stride-2 3x3 on a map of at most 16x16 outputs (maskiou conv4 14->7, P6/P7): the spatial tiles would be mostly empty
-        if (d->ksize == 3 && d->stride == 2 && n == 1 && d->res_mode != 2 && !d->in_scale && a.p[0].Ho <= 16 && a.p[0].Wo <= 16) {
-            const int cout_pad32 = cout32 <= 7 ? cout32 : cdiv(cout32, 4) * 4;
-            const int wn = (cout_pad32 % 4 == 0 && a.p[0].total_pix >= 8192) ? 4 : (cout_pad32 % 2 == 0 && a.p[0].total_pix >= 2048) ? 2 : 1;
-            a.cout_pad = cout_pad32 * 32;
-            a.ga_stride = 2;
-            const int gy = cout_pad32 / wn;
-            return wn == 4 ? launch<1, 1, 1, 4, 32, true>(a, gy, st) : wn == 2 ? launch<1, 1, 1, 2, 32, true>(a, gy, st)
-                                                                               : launch<1, 1, 1, 1, 32, true>(a, gy, st);
-        }
-        if (const int mt = pointwise_mt(d, n)) {
-            a.cout_pad = cdiv(cout32, 4) * 128;
-            return launch_pw(a, mt, st);
-        }
-        if (const int mt = gather_mt(d, n)) {
-            a.cout_pad = cdiv(cout32, 4) * 128;
-            a.ga_stride = d->stride;
-            return launch_pw(a, mt, st);
-        }
-        v = choose_variant(a, taps, d->stride, cout32);
-    }
+    const Variant v{d->tune_wm, d->tune_sc, d->tune_wn};
+    if (!variant_ok(d->ksize * d->ksize, d->stride, cout32, v.wm, v.sc, v.wn)) return fail(CMK_EINVAL, "conv: variant not available for this shape%s", "");
     if (d->ksize == 1) return dispatch_wn<1, 1>(a, cout32, v, st);
     if (d->stride == 1) return dispatch_wn<9, 1>(a, cout32, v, st);
     return dispatch_wn<9, 2>(a, cout32, v, st);
+}
+
+static int run(const cmk_conv_desc* descs, int n, void* stream) {
+    const cmk_conv_desc* d = &descs[0];
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nprob = n;
+    for (int i = 0; i < n; ++i) fill_problem(a.p[i], &descs[i]);
+    a.w = d->w; a.res = d->res;
+    a.Cin = d->Cin; a.Cout = d->Cout;
+    a.x_cs = d->x_cs; a.x_co = d->x_co; a.y_cs = d->y_cs; a.y_co = d->y_co;
+    a.res_cs = d->res_cs; a.res_co = d->res_co; a.res_mode = d->res_mode; a.Hr = d->Hr; a.Wr = d->Wr;
+    if (a.res_mode == 2 && (a.Hr * 2 < a.p[0].Ho || a.Wr * 2 < a.p[0].Wo)) return fail(CMK_EINVAL, "conv: upsampled residual too small%s", "");
+    a.relu_upto = d->relu_upto; a.in_relu = d->in_relu;
+    const Variant v = resolve(descs, n, d->gn_ws != nullptr);
+    cmk_conv_desc dv = *d;          // zero tune fields launch exactly as the explicit variant they resolve to
+    dv.tune_wm = v.wm; dv.tune_sc = v.sc; dv.tune_wn = v.wn;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = dispatch(a, &dv, descs, n, st);
+    if (rc || a.ksplit <= 1) return rc;
+    const ConvProblem& p = a.p[0];      // split-K (one problem): sum the partial sums and apply the epilogue
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((p.total_pix * (a.cout_pad >> 2) + 255) / 256, 256L * 32)), dim3(256), 0, st, a.ws, a.ksplit, p.total_pix,
+                       a.cout_pad, p.scale, p.shift, a.Cout, a.relu_upto, a.res_mode == 1 ? a.res : nullptr, a.res_cs, a.res_co, p.y, a.y_cs,
+                       a.y_co);
+    return check_launch("splitk_reduce");
 }
 
 }  // namespace cmk
@@ -1177,25 +1167,16 @@ extern "C" int cmk_conv2d_nhwc(const cmk_conv_desc* d, void* stream) {
 }
 
 extern "C" int cmk_conv2d_nhwc_multi(const cmk_conv_desc* descs, int n, void* stream) {
-    using namespace cmk;
-    if (!descs || n < 1 || n > MAXP) return fail(CMK_EINVAL, "conv_multi: need 1..%s%ld problems", "", MAXP);
-    bool same_w = true;
-    for (int i = 0; i < n; ++i) {
-        int rc = validate(&descs[i]);
-        if (rc) return rc;
-        const cmk_conv_desc *a = &descs[0], *b = &descs[i];
-        same_w = same_w && b->w == a->w && b->w_wino == a->w_wino && b->w_wino6 == a->w_wino6 && b->w_split == a->w_split && b->w_splith == a->w_splith;
-        if (b->Cin != a->Cin || b->Cout != a->Cout || b->ksize != a->ksize || b->stride != a->stride ||
-            b->relu_upto != a->relu_upto || b->in_relu != a->in_relu || b->x_cs != a->x_cs || b->x_co != a->x_co || b->y_cs != a->y_cs ||
-            b->y_co != a->y_co || b->res_mode != 0 || b->tune_wm != a->tune_wm || b->tune_sc != a->tune_sc || b->tune_wn != a->tune_wn || (b->in_scale == nullptr) != (a->in_scale == nullptr) ||
-            b->gn_ws != a->gn_ws || b->gn_groups != a->gn_groups || b->splitk > 1 || b->pool_ws)
-            return fail(CMK_EINVAL, "conv_multi: problems must share channels/views/flags and carry no residual%s", "");
-    }
-    // problems with different weights (the cls and the bbox tower of the FCOS head, fcos.py:227-231, in one launch) and more than 5 problems:
-    // the F(4x4) kernels only, which take the packed weights per problem
-    if ((!same_w || n > 5) && (descs[0].tune_wm != 6 || descs[0].tune_wn != 1) && descs[0].tune_wm != 11)
-        return fail(CMK_EINVAL, "conv_multi: different weights per problem / more than 5 problems need tune_wm 6, tune_wn 1 (the F(4x4) map kernels)%s", "");
-    for (int i = 0; i < n; ++i)
-        if (descs[0].tune_wm == 6 && !descs[i].w_wino6) return fail(CMK_EINVAL, "conv_multi: w_wino6 missing%s", "");
-    return run(descs, n, stream);
+    int rc = cmk::validate_multi(descs, n);
+    if (rc) return rc;
+    return cmk::run(descs, n, stream);
+}
+
+extern "C" int cmk_conv_resolve(const cmk_conv_desc* descs, int n, int with_gn_stats, int variant[3]) {
+    int rc = n == 1 ? cmk::validate(descs) : cmk::validate_multi(descs, n);
+    if (rc) return rc;
+    if (!variant) return cmk::fail(CMK_EINVAL, "conv_resolve: null variant%s", "");
+    const cmk::Variant v = cmk::resolve(descs, n, with_gn_stats || descs[0].gn_ws);
+    variant[0] = v.wm; variant[1] = v.sc; variant[2] = v.wn;
+    return CMK_OK;
 }

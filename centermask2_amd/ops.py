@@ -306,10 +306,14 @@ def save_tuned(path: str) -> None:
         json.dump({_key_to_str(k): list(v) for k, v in sorted(_TUNED.items(), key=lambda kv: _key_to_str(kv[0]))}, f, indent=0)
 
 
+def _variant4(tv) -> tuple:
+    """(wm, sc, wn[, splitk]) -> (wm, sc, wn, splitk)."""
+    return tuple(tv[:3]) + (tv[3] if len(tv) > 3 else 1,)
+
+
 def _variant_on_menu(tv) -> bool:
     """(wm, sc, wn[, splitk]) names a kernel this library has (older tables may carry variants that were removed since)."""
-    wm, sc, wn = tv[:3]
-    sk = tv[3] if len(tv) > 3 else 1
+    wm, sc, wn, sk = _variant4(tv)
     if wm == 6 and sc == 64:          # F(4x4,3x3), shared-V form (conv_wino6s.hip)
         return wn in (1, 2) and sk == 1
     if wm == 10:                      # pointwise GEMM from bf16-split products: only where the caller opted in
@@ -318,7 +322,7 @@ def _variant_on_menu(tv) -> bool:
         return ALLOW_SPLIT_F16 and sc == 32 and wn == 4 and sk == 1
     if wm == 11:                      # direct 3x3 conv from bf16-split products (conv_sp3.hip): sc = pieces, wn = geometry
         return ALLOW_SPLIT_F16 and sc in (2, 21) and 0 <= wn <= 3 and sk == 1
-    return (wm in (1, 2, 5, 6, 7, 8, 9) and sc in (16, 32) and 1 <= wn <= 7 and sk in (1, 2, 4, 8)) or tuple(tv[:3]) == (0, 0, 0)
+    return (wm in (1, 2, 5, 6, 7, 8, 9) and sc in (16, 32) and 1 <= wn <= 7 and sk in (1, 2, 4, 8)) or (wm, sc, wn) == (0, 0, 0)
 
 
 def load_tuned(path: str) -> int:
@@ -343,8 +347,7 @@ def _out_pixels(d) -> int:
 
 def _set_variant(descs, n, tv):
     """Write a (wm, sc, wn[, splitk]) choice into the descriptors; returns the split-K workspace (keep it alive until the launch)."""
-    wm, sc, wn = tv[:3]
-    sk = tv[3] if len(tv) > 3 else 1
+    wm, sc, wn, sk = _variant4(tv)
     for i in range(n):
         descs[i].tune_wm, descs[i].tune_sc, descs[i].tune_wn = wm, sc, wn
         descs[i].splitk, descs[i].splitk_ws = 0, None
@@ -395,7 +398,7 @@ def _tune(descs, n, key) -> None:
         if small and d0.ksize == 3:
             cands += [(6, 16, 1, sk) for sk in (2, 4)]      # ... with the chunk loop split over 2 / 4 workgroups (launches of about one round)
     if TUNE_ONLY is not None:
-        cands = [tuple(tv) + (1,) * (4 - len(tv)) for tv in TUNE_ONLY(key)]
+        cands = [_variant4(tv) for tv in TUNE_ONLY(key)]
     times = {}
     for _ in range(TUNE_ROUNDS):
         for tv in cands:
@@ -420,17 +423,6 @@ def _tune(descs, n, key) -> None:
     TUNE_LOG.append((key, {tv: times[tv] for tv in cands if tv in times}))
 
 
-def _default_is_wino6(descs, n, pc) -> bool:
-    """The library's untuned choice between the two Winograd forms (conv_igemm.hip run()): F(4x4,3x3) when its 12x40 tiles are at
-    least 55 % full over the launch and there are at least 256 workgroups."""
-    if getattr(pc, "w_wino6", None) is None or pc.k != 3 or pc.stride != 1 or pc.cin_pad < 32:
-        return False
-    cd = lambda a, b: -(-a // b)
-    px = sum(descs[i].N * descs[i].H * descs[i].W for i in range(n))
-    tiles = sum(descs[i].N * cd(descs[i].H, 12) * cd(descs[i].W, 40) for i in range(n))
-    return px >= 0.55 * tiles * 480 and tiles * cd(pc.cout, 32) >= 256
-
-
 def _default_variant(d):
     """No table entry and no tuner: library defaults, plus split-K for skinny 1x1 GEMMs (maskiou_fc1: 400 x 12544 x 1024)."""
     if d.ksize == 1 and d.res_mode != 2 and _out_pixels(d) <= 1024 and d.Cin >= 4096:
@@ -441,16 +433,25 @@ def _default_variant(d):
     return (0, 0, 0)
 
 
-def _apply_tuning(descs, n, key):
-    if FORCE_VARIANT is not None:
-        return _set_variant(descs, n, FORCE_VARIANT)
-    tv = _TUNED.get(key)
-    if tv is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing():
+def _apply_tuning(descs, n, key, with_gn_stats=False, tune=True):
+    """Write an explicit variant into the descriptors: FORCE_VARIANT, else the loaded table, else (tune) the start-up tuner, else the split-K
+    default, with zero tune fields made explicit by the library (cmk_conv_resolve; with_gn_stats: as for a launch with fused GroupNorm
+    statistics).  Returns the (wm, sc, wn, splitk) written and the split-K workspace (keep it alive until the launch)."""
+    tv = FORCE_VARIANT if FORCE_VARIANT is not None else _TUNED.get(key)
+    if tv is None and tune and AUTOTUNE and not torch.cuda.is_current_stream_capturing():
         _tune(descs, n, key)
         tv = _TUNED[key]
     if tv is None:
         tv = _default_variant(descs[0]) if n == 1 else (0, 0, 0)
-    return _set_variant(descs, n, tv)
+    ws = _set_variant(descs, n, tv)
+    tv = _variant4(tv)
+    if tv[:3] == (0, 0, 0):
+        v = (ctypes.c_int * 3)()
+        check(_lib.load().cmk_conv_resolve(descs, n, int(with_gn_stats), v), "cmk_conv_resolve")
+        for i in range(n):
+            descs[i].tune_wm, descs[i].tune_sc, descs[i].tune_wn = v
+        tv = tuple(v) + tv[3:]
+    return tv, ws
 
 
 def _problem_key(descs, n):
@@ -460,38 +461,84 @@ def _problem_key(descs, n):
             tuple((descs[i].N, descs[i].H, descs[i].W) for i in range(n)))
 
 
+def _launch(descs, n, tv, ws, xs, ys, pcs, single=False, what="cmk_conv2d_nhwc_multi", **name_kw) -> None:
+    """Launch the filled descriptors (cmk_conv2d_nhwc if single, else the _multi entry) with the split-K workspace ws alive across the
+    call.  When PROFILE is a list, the launch is timed and recorded under the kernel that the variant written, tv, runs."""
+    lib = _lib.load()
+    if PROFILE is not None:
+        pc = pcs[0]
+        taps = pc.k * pc.k
+        pix = lambda v: v.t.shape[0] * v.t.shape[1] * v.t.shape[2]
+        flops = sum(2.0 * pix(y) * pc.cin * pc.cout * taps for y in ys)
+        weights = len({p.w.data_ptr() for p in pcs})          # read once per launch each
+        nbytes = sum(4.0 * (pix(x) * pc.cin + pix(y) * pc.cout) for x, y in zip(xs, ys)) + weights * 4.0 * pc.cin * pc.cout * taps
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(lib.cmk_conv2d_nhwc(ctypes.byref(descs[0]), _stream()) if single else lib.cmk_conv2d_nhwc_multi(descs, n, _stream()), what)
+    if PROFILE is not None:
+        e1.record()
+        shape = tuple(xs[0].nhw) + (pc.cin, pc.cout, pc.k, pc.stride) if single else None
+        PROFILE.append((_kernel_name(taps, pc.stride, tv, **name_kw), flops, nbytes, e0, e1, shape,
+                        executed_flops(taps, pc.stride, tv, [tuple(y.t.shape[:3]) for y in ys], pc.cin_pad, pc.cout)))
+    del ws                  # referenced until the launch has been issued
+
+
 def conv2d(x: View, pc: PackedConv, y: View, relu: bool = False, relu_upto: Optional[int] = None,
            res: Optional[View] = None, res_upsample: bool = False, in_relu: bool = False, pool: Optional[list] = None) -> None:
     """pool: a list that receives (partial sums, rows per record) when the kernel this conv runs on also leaves the average-pool partial
     sums of its output behind (cmk_conv_desc.pool_ws: the pointwise GEMM kernel, for the eSE gate); left empty otherwise."""
-    lib = _lib.load()
     descs = (ConvDesc * 1)()
     _fill_desc(descs[0], x, pc, y, relu, relu_upto, res, res_upsample, in_relu)
-    ws = _apply_tuning(descs, 1, _problem_key(descs, 1))      # split-K workspace (if any) stays referenced across the launch
-    if pool is not None and FUSE_POOL:
-        rows = lib.cmk_conv_pool_rows(ctypes.byref(descs[0]))
+    tv, ws = _apply_tuning(descs, 1, _problem_key(descs, 1))
+    pooled = pool is not None and FUSE_POOL
+    if pooled:
+        rows = _lib.load().cmk_conv_pool_rows(ctypes.byref(descs[0]))
         if rows > 0:
             d = descs[0]
             pws = torch.empty((2 * (-(-(d.N * d.H * d.W) // rows)), pc.cout), dtype=torch.float32, device=y.t.device)
             d.pool_ws = pws.data_ptr()
             pool.append((pws, rows))
-    check(lib.cmk_conv2d_nhwc(ctypes.byref(descs[0]), _stream()), "cmk_conv2d_nhwc")
-    del ws
+    _launch(descs, 1, tv, ws, [x], [y], [pc], single=True, what="cmk_conv2d_nhwc", pool=pooled, upres=bool(res_upsample), cout=pc.cout)
 
 
 def conv2d_multi(xs: Sequence[View], pcs: Sequence[PackedConv], ys: Sequence[View], relu: bool = False,
                  relu_upto: Optional[int] = None, in_affine=None) -> None:
     """One launch over several inputs that share the packed weights (pcs[i].w is the same tensor; scale/shift may differ).
     in_affine[i] = (scale, shift) of shape (N, Cin): the producer's GroupNorm+ReLU applied while staging input i."""
-    lib = _lib.load()
     n = len(xs)
     descs = (ConvDesc * n)()
     for i in range(n):
         assert pcs[i].w.data_ptr() == pcs[0].w.data_ptr()
         _fill_desc(descs[i], xs[i], pcs[i], ys[i], relu, relu_upto, None, False, False, in_affine[i] if in_affine is not None else None)
-    ws = _apply_tuning(descs, n, _problem_key(descs, n))
-    check(lib.cmk_conv2d_nhwc_multi(descs, n, _stream()), "cmk_conv2d_nhwc_multi")
-    del ws
+    tv, ws = _apply_tuning(descs, n, _problem_key(descs, n))
+    _launch(descs, n, tv, ws, xs, ys, pcs, aff=in_affine is not None)
+
+
+def _gn_records(descs, ys, tv, groups):
+    """Point the descriptors at a new workspace for the fused GroupNorm statistics that variant tv writes (records numbered over the problems
+    in order).  Returns affine(lo, hi, gamma, beta, eps) -> [(scale, shift)] of problems lo..hi-1, to be called after the launch."""
+    lib = _lib.load()
+    nimg, cout, dev = ys[0].t.shape[0], ys[0].c, ys[0].t.device
+    recs = [lib.cmk_conv_gn_records(y.t.shape[1], y.t.shape[2], 110 + tv[2] if tv[0] == 11 else tv[0]) for y in ys]
+    gws = torch.empty((nimg * sum(recs), groups, 2), dtype=torch.float64, device=dev)
+    for i in range(len(ys)):
+        descs[i].gn_ws, descs[i].gn_groups = gws.data_ptr(), groups
+
+    def affine(lo, hi, gamma, beta, eps):
+        m = hi - lo
+        out = [(torch.empty((nimg, cout), dtype=torch.float32, device=dev), torch.empty((nimg, cout), dtype=torch.float32, device=dev)) for _ in range(m)]
+        hs, wss, rc = (ctypes.c_int * m)(*[y.t.shape[1] for y in ys[lo:hi]]), (ctypes.c_int * m)(*[y.t.shape[2] for y in ys[lo:hi]]), (ctypes.c_int * m)(*recs[lo:hi])
+        ps, pb = (ctypes.c_void_p * m)(*[o[0].data_ptr() for o in out]), (ctypes.c_void_p * m)(*[o[1].data_ptr() for o in out])
+        check(lib.cmk_groupnorm_affine_tiles(gws.data_ptr() + nimg * sum(recs[:lo]) * groups * 2 * 8, hs, wss, rc, m, gamma.data_ptr(), beta.data_ptr(), nimg, cout,
+                                             groups, eps, ps, pb, _stream()), "cmk_groupnorm_affine_tiles")
+        return out
+    return affine
+
+
+def _gn_fusable(xs, cout, groups) -> bool:
+    """The statistics of a GroupNorm can come from the conv's epilogue: a power-of-two group width <= 32 and one image count."""
+    cpg = cout // groups if groups > 0 and cout % groups == 0 else 0
+    return 0 < cpg <= 32 and (cpg & (cpg - 1)) == 0 and all(x.t.shape[0] == xs[0].t.shape[0] for x in xs)
 
 
 def conv_gn_multi(xs: Sequence[View], pcs: Sequence[PackedConv], gamma: torch.Tensor, beta: torch.Tensor, groups: int = 32,
@@ -499,7 +546,6 @@ def conv_gn_multi(xs: Sequence[View], pcs: Sequence[PackedConv], gamma: torch.Te
     """Tower conv (no activation) over several levels + the statistics of the GroupNorm that follows (fcos.py:182-186).
     Returns (raw conv outputs, [(scale, shift)] per level) — the affine is applied by the NEXT conv while staging.
     When the Winograd kernel runs the conv, its epilogue produces the statistics (no pass over the output)."""
-    lib = _lib.load()
     n = len(xs)
     pc = pcs[0]
     ys = [View(torch.empty((x.t.shape[0], x.t.shape[1], x.t.shape[2], pc.cout), dtype=torch.float32, device=x.t.device)) for x in xs]
@@ -507,68 +553,32 @@ def conv_gn_multi(xs: Sequence[View], pcs: Sequence[PackedConv], gamma: torch.Te
     for i in range(n):
         assert pcs[i].w.data_ptr() == pc.w.data_ptr()
         _fill_desc(descs[i], xs[i], pcs[i], ys[i], False, None, None, False, False, in_affine[i] if in_affine is not None else None)
-    key = _problem_key(descs, n)
-    ws = _apply_tuning(descs, n, key)
-
-    def launch():
-        if PROFILE is None:
-            return check(lib.cmk_conv2d_nhwc_multi(descs, n, _stream()), "cmk_conv2d_nhwc_multi")
-        taps = pc.k * pc.k
-        flops = sum(2.0 * y.t.shape[0] * y.t.shape[1] * y.t.shape[2] * pc.cin * pc.cout * taps for y in ys)
-        nbytes = sum(4.0 * y.t.shape[0] * y.t.shape[1] * y.t.shape[2] * (pc.cin + pc.cout) for y in ys) + 4.0 * pc.cin * pc.cout * taps
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib.cmk_conv2d_nhwc_multi(descs, n, _stream()), "cmk_conv2d_nhwc_multi")
-        e1.record()
-        PROFILE.append((_kernel_name(taps, 1, _TUNED.get(key), in_affine is not None), flops, nbytes, e0, e1, None,
-                        executed_flops(taps, 1, _TUNED.get(key), [tuple(y.t.shape[:3]) for y in ys], pc.cin_pad, pc.cout)))
-
-    d0 = descs[0]
-    cpg = pc.cout // groups if groups > 0 and pc.cout % groups == 0 else 0
-    untuned = (d0.tune_wm, d0.tune_sc, d0.tune_wn) == (0, 0, 0)
-    wino = d0.tune_wm in (5, 6, 11) or (untuned and pc.w_wino is not None and pc.cin_pad >= 32 and pc.stride == 1)
-    gn_form = 110 + d0.tune_wn if d0.tune_wm == 11 else 6 if (d0.tune_wm == 6 or (untuned and _default_is_wino6(descs, n, pc))) else 5
-    fused = wino and 0 < cpg <= 32 and (cpg & (cpg - 1)) == 0 and all(x.t.shape[0] == xs[0].t.shape[0] for x in xs)
-    if not fused:
-        launch()
-        del ws
+    fusable = _gn_fusable(xs, pc.cout, groups)
+    tv, ws = _apply_tuning(descs, n, _problem_key(descs, n), with_gn_stats=fusable)
+    if not (fusable and tv[0] in (5, 6, 11)):
+        _launch(descs, n, tv, ws, xs, ys, pcs, aff=in_affine is not None)
         return ys, groupnorm_affine_multi([y.t for y in ys], gamma, beta, groups, eps)
-    nimg, dev = xs[0].t.shape[0], xs[0].t.device
-    recs_l = [lib.cmk_conv_gn_records(y.t.shape[1], y.t.shape[2], gn_form) for y in ys]
-    gws = torch.empty((nimg * sum(recs_l), groups, 2), dtype=torch.float64, device=dev)
-    for i in range(n):
-        descs[i].gn_ws, descs[i].gn_groups = gws.data_ptr(), groups
-    launch()
-    out = [(torch.empty((nimg, pc.cout), dtype=torch.float32, device=dev), torch.empty((nimg, pc.cout), dtype=torch.float32, device=dev)) for _ in ys]
-    hs, wss, recs = (ctypes.c_int * n)(), (ctypes.c_int * n)(), (ctypes.c_int * n)()
-    ps, pb = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
-    for i, y in enumerate(ys):
-        hs[i], wss[i], recs[i] = y.t.shape[1], y.t.shape[2], recs_l[i]
-        ps[i], pb[i] = out[i][0].data_ptr(), out[i][1].data_ptr()
-    check(lib.cmk_groupnorm_affine_tiles(gws.data_ptr(), hs, wss, recs, n, gamma.data_ptr(), beta.data_ptr(), nimg, pc.cout, groups, eps, ps, pb,
-                                         _stream()), "cmk_groupnorm_affine_tiles")
-    del ws
-    return ys, out
+    affine = _gn_records(descs, ys, tv, groups)
+    _launch(descs, n, tv, ws, xs, ys, pcs, aff=in_affine is not None)
+    return ys, affine(0, n, gamma, beta, eps)
 
 
 def conv_gn_multi_pair(xs_a: Sequence[View], pc_a: PackedConv, gn_a, xs_b: Sequence[View], pc_b: PackedConv, gn_b, groups: int = 32, eps: float = 1e-5,
                        in_affine_a=None, in_affine_b=None):
     """Two tower convs with DIFFERENT weights (the cls and the bbox tower of the FCOS head, fcos.py:227-231) over the same level shapes in
     ONE launch of up to 10 problems — half the launch ramps and tails of two launches — each followed by its own GroupNorm statistics
-    (gn_x = (gamma, beta)).  Only the F(4x4) map kernels take per-problem weights: returns None when the measured / default variant of this
-    problem is another kernel or the fused statistics do not apply (the caller then runs the two towers separately).
-    Returns ((ys_a, affine_a), (ys_b, affine_b)) like two conv_gn_multi calls."""
-    lib = _lib.load()
+    (gn_x = (gamma, beta)).  Only the F(4x4) map kernels (and the opt-in direct fp16-split form) take per-problem weights: returns None when
+    the measured / default variant of this problem is another kernel, splits K, or the fused statistics do not apply (the caller then runs
+    the two towers separately).  Returns ((ys_a, affine_a), (ys_b, affine_b)) like two conv_gn_multi calls."""
     na, nb = len(xs_a), len(xs_b)
     n = na + nb
     if not PAIR_TOWERS:
         return None
-    if na != nb or n > 10 or pc_a.cout != pc_b.cout or pc_a.cin_pad != pc_b.cin_pad or pc_a.w_wino6 is None or pc_b.w_wino6 is None:
+    if na != nb or n > 10 or pc_a.cout != pc_b.cout or pc_a.cin_pad != pc_b.cin_pad:
         return None
     if (in_affine_a is None) != (in_affine_b is None) or any(tuple(a.t.shape) != tuple(b.t.shape) for a, b in zip(xs_a, xs_b)):
         return None
-    cpg = pc_a.cout // groups if groups > 0 and pc_a.cout % groups == 0 else 0
-    if not (0 < cpg <= 32 and (cpg & (cpg - 1)) == 0) or any(x.t.shape[0] != xs_a[0].t.shape[0] for x in xs_a):
+    if not _gn_fusable(xs_a, pc_a.cout, groups):
         return None
     xs, pcs = list(xs_a) + list(xs_b), [pc_a] * na + [pc_b] * nb
     affs = (list(in_affine_a) + list(in_affine_b)) if in_affine_a is not None else None
@@ -576,51 +586,17 @@ def conv_gn_multi_pair(xs_a: Sequence[View], pc_a: PackedConv, gn_a, xs_b: Seque
     descs = (ConvDesc * n)()
     for i in range(n):
         _fill_desc(descs[i], xs[i], pcs[i], ys[i], False, None, None, False, False, affs[i] if affs is not None else None)
-    # the variant measured for ONE tower's launch (the table is keyed by the 5 level shapes) decides; the 10-problem launch has no entry of its own
-    half = (ConvDesc * na)()
-    for i in range(na):
-        _fill_desc(half[i], xs[i], pcs[i], ys[i], False, None, None, False, False, affs[i] if affs is not None else None)
-    key = _problem_key(half, na)
-    tv = FORCE_VARIANT if FORCE_VARIANT is not None else _TUNED.get(key)
-    if tv is None:
-        tv = (6, 16, 1) if _default_is_wino6(half, na, pc_a) else None
-    sp3 = tv is not None and tv[0] == 11 and pc_a.w_splith is not None and pc_b.w_splith is not None      # opt-in direct fp16-split form
-    if tv is None or not (sp3 or (tv[0] == 6 and tv[2] == 1)):
+    # the variant of ONE tower's launch (the table is keyed by the 5 level shapes, problems 0..na-1) decides; the 10-problem launch has no
+    # entry of its own and is not timed by the tuner
+    tv, _ = _apply_tuning(descs, na, _problem_key(descs, na), with_gn_stats=True, tune=False)
+    wino6 = tv[0] == 6 and tv[2] == 1 and pc_a.w_wino6 is not None and pc_b.w_wino6 is not None
+    sp3 = tv[0] == 11 and pc_a.w_splith is not None and pc_b.w_splith is not None      # opt-in direct fp16-split form
+    if tv[3] > 1 or not (wino6 or sp3):
         return None
     _set_variant(descs, n, tv)
-    nimg, dev = xs[0].t.shape[0], xs[0].t.device
-    recs_l = [lib.cmk_conv_gn_records(y.t.shape[1], y.t.shape[2], 110 + tv[2] if sp3 else 6) for y in ys]
-    gws = torch.empty((nimg * sum(recs_l), groups, 2), dtype=torch.float64, device=dev)
-    for i in range(n):
-        descs[i].gn_ws, descs[i].gn_groups = gws.data_ptr(), groups
-    taps = 9
-    if PROFILE is None:
-        check(lib.cmk_conv2d_nhwc_multi(descs, n, _stream()), "cmk_conv2d_nhwc_multi (tower pair)")
-    else:
-        flops = sum(2.0 * y.t.shape[0] * y.t.shape[1] * y.t.shape[2] * pc_a.cin * pc_a.cout * taps for y in ys)
-        nbytes = sum(4.0 * y.t.shape[0] * y.t.shape[1] * y.t.shape[2] * (pc_a.cin + pc_a.cout) for y in ys) + 2 * 4.0 * pc_a.cin * pc_a.cout * taps
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib.cmk_conv2d_nhwc_multi(descs, n, _stream()), "cmk_conv2d_nhwc_multi (tower pair)")
-        e1.record()
-        PROFILE.append((_kernel_name(taps, 1, tv, affs is not None), flops, nbytes, e0, e1, None,
-                        executed_flops(taps, 1, tv, [tuple(y.t.shape[:3]) for y in ys], pc_a.cin_pad, pc_a.cout)))
-    out = []
-    rec_off = 0
-    for t, (gamma, beta) in enumerate((gn_a, gn_b)):
-        sl = slice(t * na, (t + 1) * na)
-        res = [(torch.empty((nimg, pc_a.cout), dtype=torch.float32, device=dev), torch.empty((nimg, pc_a.cout), dtype=torch.float32, device=dev)) for _ in range(na)]
-        hs, wss, recs = (ctypes.c_int * na)(), (ctypes.c_int * na)(), (ctypes.c_int * na)()
-        ps, pb = (ctypes.c_void_p * na)(), (ctypes.c_void_p * na)()
-        for i, y in enumerate(ys[sl]):
-            hs[i], wss[i], recs[i] = y.t.shape[1], y.t.shape[2], recs_l[t * na + i]
-            ps[i], pb[i] = res[i][0].data_ptr(), res[i][1].data_ptr()
-        # the records of the second tower's problems follow those of the first (spatial tiles are numbered problem after problem)
-        check(lib.cmk_groupnorm_affine_tiles(gws.data_ptr() + rec_off * groups * 2 * 8, hs, wss, recs, na, gamma.data_ptr(), beta.data_ptr(), nimg, pc_a.cout,
-                                             groups, eps, ps, pb, _stream()), "cmk_groupnorm_affine_tiles")
-        rec_off += nimg * sum(recs_l[sl])
-        out.append((ys[sl], res))
-    return out[0], out[1]
+    affine = _gn_records(descs, ys, tv, groups)
+    _launch(descs, n, tv, None, xs, ys, pcs, what="cmk_conv2d_nhwc_multi (tower pair)", aff=affs is not None)
+    return (ys[:na], affine(0, na, gn_a[0], gn_a[1], eps)), (ys[na:], affine(na, n, gn_b[0], gn_b[1], eps))
 
 
 def conv_out_multi(xs: Sequence[View], pcs: Sequence[PackedConv], **kw) -> List[View]:  # kw: relu, relu_upto, in_affine
@@ -976,13 +952,9 @@ def executed_flops(taps: int, stride: int, tv, shapes, cin_pad: int, cout: int) 
         tiles = sum(cd(n * h * w, 128 * wm) for n, h, w in shapes)
     return float(tiles) * (128 * wm) * cout_pad * taps * cin_pad * 2.0
 
-_conv2d_plain = conv2d
-
 
 def _kernel_name(taps, stride, tv, aff=False, pool=False, upres=False, cout=None) -> str:
     """The template instantiation rocprofv3 will report (minus the `void cmk::` prefix and the argument list)."""
-    if not tv or tuple(tv[:3]) == (0, 0, 0):
-        return "conv_igemm_kernel<{}, {}, cost-model variant>".format(taps, stride)
     if tv[0] == 5:
         return "conv_wino4r_kernel<{}>".format("true" if aff else "false")
     if tv[0] == 6:
@@ -1000,51 +972,6 @@ def _kernel_name(taps, stride, tv, aff=False, pool=False, upres=False, cout=None
     if wm == 7:
         return "conv_igemm_kernel<1, 1, 1, {}, 32, true>".format(wn)
     return "conv_igemm_kernel<{}, {}, {}, {}, {}, false>".format(taps, stride, wm, wn, 32 if taps == 1 else sc)
-
-
-def conv2d(x, pc, y, **kw):  # noqa: F811
-    if PROFILE is None:
-        return _conv2d_plain(x, pc, y, **kw)
-    lib = _lib.load()
-    n, h, w = x.nhw
-    ho, wo = y.t.shape[1], y.t.shape[2]
-    taps = pc.k * pc.k
-    flops = 2.0 * n * ho * wo * pc.cin * pc.cout * taps
-    nbytes = 4.0 * (n * h * w * pc.cin + n * ho * wo * pc.cout + pc.cin * pc.cout * taps)
-    descs = (ConvDesc * 1)()
-    _fill_desc(descs[0], x, pc, y, kw.get("relu", False), kw.get("relu_upto"), kw.get("res"), kw.get("res_upsample", False), kw.get("in_relu", False))
-    tv = _TUNED.get(_problem_key(descs, 1))
-    key = _kernel_name(taps, pc.stride, tv, pool=kw.get("pool") is not None and FUSE_POOL, upres=bool(kw.get("res_upsample")), cout=pc.cout)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _conv2d_plain(x, pc, y, **kw)
-    e1.record()
-    PROFILE.append((key, flops, nbytes, e0, e1, (n, h, w, pc.cin, pc.cout, pc.k, pc.stride),
-                    executed_flops(taps, pc.stride, tv, [(n, ho, wo)], pc.cin_pad, pc.cout)))
-
-
-_conv2d_multi_plain = conv2d_multi
-
-
-def conv2d_multi(xs, pcs, ys, **kw):  # noqa: F811
-    if PROFILE is None:
-        return _conv2d_multi_plain(xs, pcs, ys, **kw)
-    pc = pcs[0]
-    taps = pc.k * pc.k
-    flops = sum(2.0 * y.t.shape[0] * y.t.shape[1] * y.t.shape[2] * pc.cin * pc.cout * taps for y in ys)
-    nbytes = sum(4.0 * (x.t.shape[0] * x.t.shape[1] * x.t.shape[2] * pc.cin + y.t.shape[0] * y.t.shape[1] * y.t.shape[2] * pc.cout) for x, y in zip(xs, ys))
-    nbytes += 4.0 * pc.cin * pc.cout * taps
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _conv2d_multi_plain(xs, pcs, ys, **kw)
-    e1.record()
-    descs = (ConvDesc * len(xs))()
-    for i in range(len(xs)):
-        _fill_desc(descs[i], xs[i], pcs[i], ys[i], kw.get("relu", False), kw.get("relu_upto"), None, False, False,
-                   kw["in_affine"][i] if kw.get("in_affine") is not None else None)
-    tv = _TUNED.get(_problem_key(descs, len(xs)))
-    PROFILE.append((_kernel_name(taps, 1, tv, kw.get("in_affine") is not None), flops, nbytes, e0, e1, None,
-                    executed_flops(taps, 1, tv, [tuple(y.t.shape[:3]) for y in ys], pc.cin_pad, pc.cout)))
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -48,7 +48,8 @@ typedef struct {
     int stride;                                 /* 1 or 2 */
     int relu_upto;                              /* ReLU applied to output channels < relu_upto */
     int in_relu;                                /* ReLU applied to the input while staging (fpn.py:34) */
-    /* optional tile variant picked by the caller's autotuner (all 0 = let the library's cost model choose):
+    /* optional tile variant picked by the caller's autotuner (all 0 = let the library's cost model choose; cmk_conv_resolve tells which
+     * explicit variant that is):
      * tune_wm in {1,2} (128 or 256 pixels per workgroup), tune_sc in {16,32} (sub-tile 2x16 or 1x32 pixels; 32 for 1x1),
      * tune_wn in 1..7 (32*tune_wn output channels per workgroup; must divide the padded Cout).  Results are bitwise
      * identical across variants (the K order per output does not depend on the tile).
@@ -143,6 +144,12 @@ int cmk_conv_pool_rows(const cmk_conv_desc* d);
  * different weights, fcos.py:227-231 — run as one launch of 2 x 5 problems.  Fused GroupNorm records (gn_ws) are numbered over the spatial
  * tiles of all problems in order, so the records of problems 5..9 follow those of problems 0..4. */
 int cmk_conv2d_nhwc_multi(const cmk_conv_desc* descs, int n, void* stream);
+/* The explicit variant cmk_conv2d_nhwc (n == 1) / cmk_conv2d_nhwc_multi would run for these descriptors, as variant = {tune_wm, tune_sc,
+ * tune_wn}: the caller's tune fields unchanged when set, else the untuned default (splitk, which the caller sets with its workspace, counts).
+ * Validates the descriptors as the launch does; never touches a device.  with_gn_stats != 0: prefer the forms that produce fused GroupNorm
+ * statistics exactly as a launch with gn_ws set does (gn_ws may still be NULL: its size depends on the answer); when none applies, return
+ * the choice among the others rather than fail. */
+int cmk_conv_resolve(const cmk_conv_desc* descs, int n, int with_gn_stats, int variant[3]);
 /* number of floats of the packed layout for (Cout, Cin, k): taps * ceil(Cin/16) * cout_pad * 16 */
 int64_t cmk_conv_packed_floats(int Cout, int Cin, int ksize);
 int cmk_conv_cout_pad(int Cout);

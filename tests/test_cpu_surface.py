@@ -39,6 +39,44 @@ def test_c_abi_argument_validation_without_gpu():
     assert lib.cmk_nms_topk(None, None, None, None, None, 1, 1, 0.6, 50, None, None, None, None, None, None, None, None) == -1
 
 
+def test_conv_resolve_names_the_untuned_choice_without_gpu():
+    """cmk_conv_resolve: the explicit (tune_wm, tune_sc, tune_wn) a launch with zero tune fields runs, decided on the host (dummy, aligned
+    pointers; nothing is launched).  Explicit variants come back unchanged; bad descriptors fail as the launch does."""
+    from centermask2_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_float * 64)()
+    ptr = (ctypes.addressof(buf) + 15) // 16 * 16
+
+    def desc(n, h, w, cin, cout, k=3, stride=1, w_wino6=False, w_wino=False, x_cs=None, tune=(0, 0, 0)):
+        d = _lib.ConvDesc()
+        d.x = d.w = d.scale = d.shift = d.y = ptr
+        d.w_wino6, d.w_wino = (ptr if w_wino6 else None), (ptr if w_wino else None)
+        d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = n, h, w, cin, cout, k, stride
+        d.x_cs, d.y_cs = x_cs or cin, cout
+        d.tune_wm, d.tune_sc, d.tune_wn = tune
+        return d
+
+    def resolve(descs, with_gn_stats=0):
+        arr, v = (_lib.ConvDesc * len(descs))(*descs), (ctypes.c_int * 3)()
+        rc = lib.cmk_conv_resolve(arr, len(descs), with_gn_stats, v)
+        return tuple(v) if rc == 0 else lib.cmk_last_error()
+
+    assert resolve([desc(8, 100, 160, 256, 256, w_wino6=True)]) == (6, 16, 1)                       # F(4x4) map tiles
+    assert resolve([desc(400, 14, 14, 256, 256, w_wino6=True)]) == (6, 16, 2)                       # F(4x4) RoI map pairs
+    assert resolve([desc(400, 14, 14, 256, 256, w_wino6=True, w_wino=True)], 1) == (5, 16, 2)       # ... which write no GroupNorm records
+    levels = [(100, 160), (50, 80), (25, 40), (13, 20), (7, 10)]
+    for cout in (256, 80, 5):                                                                       # the FCOS towers / predictors
+        assert resolve([desc(8, h, w, 256, cout, w_wino6=True, w_wino=True) for h, w in levels], 1) == (6, 16, 1), cout
+    assert resolve([desc(8, 400, 640, 64, 128, stride=2, x_cs=64)]) == (9, 32, 4)                   # stem_3: the gather GEMM
+    assert resolve([desc(8, 200, 320, 768, 256, k=1)]) == (8, 32, 4)                                # pointwise GEMM
+    assert resolve([desc(8, 13, 20, 256, 256, stride=2)]) == (7, 32, 1)                              # small stride-2 gather form
+    assert resolve([desc(8, 50, 80, 64, 64, w_wino=True)])[0] == 5                                   # F(2x2) without the F(4x4) packing
+    for tv in ((6, 64, 1), (8, 32, 2)):
+        assert resolve([desc(8, 50, 80, 64, 64, w_wino6=True, w_wino=True, tune=tv)]) == tv
+    assert b"multiple of 16" in resolve([desc(8, 50, 80, 24, 64)])
+    assert b"ksize" in resolve([desc(8, 50, 80, 64, 64, k=5)])
+
+
 def test_config_matches_reference_recipe():
     from centermask2_amd.config import config_path, get_cfg
     cfg = get_cfg()

@@ -639,9 +639,10 @@ def test_tower_pair_launch_equals_two_launches(dev, sc, with_affine, monkeypatch
     for (ys, affs), (ys_ref, affs_ref) in zip(pair, ((ya, affa), (yb, affb))):
         for y, yr, (sc_, sh_), (scr, shr) in zip(ys, ys_ref, affs, affs_ref):
             assert torch.equal(y.t, yr.t) and torch.equal(sc_, scr) and torch.equal(sh_, shr)
-    # the library refuses different weights per problem on the kernels that take one weight pointer per launch
-    monkeypatch.setattr(ops, "FORCE_VARIANT", (5, 16, 2))
-    assert ops.conv_gn_multi_pair(xs, pca, gn[0], xs, pcb, gn[1], groups, 1e-5) is None
+    # the library refuses different weights per problem on the kernels that take one weight pointer per launch, and split-K in a multi launch
+    for tv in ((5, 16, 2), (6, 16, 1, 4)):
+        monkeypatch.setattr(ops, "FORCE_VARIANT", tv)
+        assert ops.conv_gn_multi_pair(xs, pca, gn[0], xs, pcb, gn[1], groups, 1e-5) is None
 
 
 @pytest.mark.parametrize("case", [(2, 13, 19, 96, 256, False), (1, 25, 40, 2144, 1024, True), (1, 16, 16, 64, 320, False), (1, 64, 64, 768, 256, True),
