@@ -1014,7 +1014,7 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         if (d->ksize != 3 || d->stride != 1 || d->res_mode != 0 || d->in_relu || !d->w_wino6 || (d->Cin & 7))
             return fail(CMK_EINVAL, "conv: Winograd F(4x4,3x3) variant not available for this conv%s", "");
         a.w = d->w_wino6;
-        a.ws = d->splitk_ws;          // split-K slabs (instrumented W6_TRACE builds: a stamp buffer)
+        a.ws = d->splitk_ws;          // split-K slabs
         a.ksplit = d->splitk > 1 ? d->splitk : 1;
         a.cout_pad = cmk_conv_cout_pad(d->Cout);
         if (a.ksplit > 1) {           // F(4x4) with split-K (32-cout form, map tiles): partial sums + the reduce kernel of the direct path

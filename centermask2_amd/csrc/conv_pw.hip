@@ -138,48 +138,6 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
         for (int it = 0; it < MT; ++it) *reinterpret_cast<f32x4*>(dst + it * 64 * PST) = a_st[it];
     };
 
-#ifdef PW_TRACE
-    // instrumented build (tools/ab/trace_pw.py): lane 0 of every wave of every 16th workgroup stamps the shader clock into LDS (a global
-    // store inside the loop would make every barrier drain the loads in flight) and copies the stamps to a.ws at the end:
-    // [0] start, [1] prologue done, [2+2c] barrier of chunk c reached, [3+2c] passed (c < 28), [58] loop done, [59] stores issued,
-    // [60] XCC id, [61] HW id, [62]/[63] real time at the end/start
-    const bool tracing = a.ws && (blockIdx.x % 16) == 0 && lane == 0;
-    unsigned long long* trl = reinterpret_cast<unsigned long long*>(smem + 2 * ABUF) + wave * 64;
-    unsigned long long* trc = reinterpret_cast<unsigned long long*>(a.ws) + ((blockIdx.x / 16) * 4 + wave) * 64;
-#define PW_STAMP(slot) do { if (tracing) trl[slot] = __builtin_readcyclecounter(); } while (0)
-    if (tracing) {
-        trl[63] = __builtin_amdgcn_s_memrealtime();
-        trl[61] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | ((32 - 1) << 11));
-        trl[60] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((32 - 1) << 11));
-    }
-    PW_STAMP(0);
-#else
-#define PW_STAMP(slot) do { } while (0)
-#endif
-    // PW_ABL (timing ablations, results wrong): 1 no barrier, 2 no activation loads, 4 no weight loads, 8 no LDS writes
-#ifndef PW_ABL
-#define PW_ABL 0
-#endif
-#if PW_ABL & 1
-#define PW_SYNC
-#else
-#define PW_SYNC __syncthreads()
-#endif
-#if PW_ABL & 2
-#define PW_LOAD_A(c)
-#else
-#define PW_LOAD_A(c) load_A(c)
-#endif
-#if PW_ABL & 4
-#define PW_LOAD_B(c, s)
-#else
-#define PW_LOAD_B(c, s) load_B(c, s)
-#endif
-#if PW_ABL & 8
-#define PW_STORE_A(b)
-#else
-#define PW_STORE_A(b) store_A(b)
-#endif
     f32x16 acc[MT][2];
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -376,10 +334,8 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
                 const f32x4 r2 = {r1.x - f_lo(m_.x), r1.y - f_hi(m_.x), r1.z - f_lo(m_.y), r1.w - f_hi(m_.y)};
                 *reinterpret_cast<u32x2*>(dst + st_off[it]) = h;
                 *reinterpret_cast<u32x2*>(dst + st_off[it] + 64 * 16) = m_;
-#if !(PW_ABL & 16)
                 l.x = pk(r2.x, r2.y); l.y = pk(r2.z, r2.w);
                 *reinterpret_cast<u32x2*>(dst + st_off[it] + 2 * 64 * 16) = l;
-#endif
             }
         };
         const u32x4* wsp = reinterpret_cast<const u32x4*>(a.w) + ((long)(co0 >> 5) * 3) * 64 + lane;      // wave-uniform base + lane
@@ -389,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
 #pragma unroll
             for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
-                for (int p_ = 0; p_ < ((PW_ABL & 16) ? 2 : 3); ++p_) wb[nn][p_] = wsp[chunk * wstep + (nn * 3 + p_) * 64];
+                for (int p_ = 0; p_ < 3; ++p_) wb[nn][p_] = wsp[chunk * wstep + (nn * 3 + p_) * 64];
         };
         // (GA: load_A walks the 9 taps x Cin / 16 chunks in order, re-pointing the rows per tap; the split weights are packed tap-major to match)
         load_A(0);
@@ -407,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
             load_Bs(min(c + 1, nchunks - 1));
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                const u32x4 ah = ap[(m * 3 + 0) * 64], am = ap[(m * 3 + 1) * 64], al = (PW_ABL & 16) ? am : ap[(m * 3 + 2) * 64];
+                const u32x4 ah = ap[(m * 3 + 0) * 64], am = ap[(m * 3 + 1) * 64], al = ap[(m * 3 + 2) * 64];
                 if (m == 1) {           // the next chunk's activations (in registers since the last chunk) are split between the MFMA groups
                     stage((c + 1) & 1);
                     load_A(min(c + 2, nchunks - 1));
@@ -417,11 +373,9 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
                 for (int nn = 0; nn < 2; ++nn) {
                     const bf16x8 Bh = __builtin_bit_cast(bf16x8, wc[nn][0]), Bm = __builtin_bit_cast(bf16x8, wc[nn][1]), Bl = __builtin_bit_cast(bf16x8, wc[nn][2]);
                     f32x16 cacc = acc[m][nn];
-#if !(PW_ABL & 16)
                     cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, cacc, 0, 0, 0);
                     cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, cacc, 0, 0, 0);
                     cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, cacc, 0, 0, 0);
-#endif
                     cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, cacc, 0, 0, 0);
                     cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, cacc, 0, 0, 0);
                     cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, cacc, 0, 0, 0);
@@ -488,33 +442,25 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     load_B(c_lo + 1, 1);
     __builtin_amdgcn_sched_barrier(0);
-    PW_STAMP(1);
-    PW_SYNC;
+    __syncthreads();
     rd(avA, 0, 0);
     for (int c = c_lo; c < nchunks; c += 2) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             rd(avB, u, 1);
             mh(avA, u, 0);
-            PW_STORE_A(u ^ 1);
-            PW_LOAD_A(min(c + u + 2, nchunks - 1));
+            store_A(u ^ 1);
+            load_A(min(c + u + 2, nchunks - 1));
             __builtin_amdgcn_sched_barrier(0);      // (the compiler otherwise moves the second half's MFMAs in front of the barrier)
-#ifdef PW_TRACE
-            if (c + u < 28) PW_STAMP(2 + 2 * (c + u));
-#endif
-            PW_SYNC;
-#ifdef PW_TRACE
-            if (c + u < 28) PW_STAMP(3 + 2 * (c + u));
-#endif
+            __syncthreads();
             rd(avA, u ^ 1, 0);
             __builtin_amdgcn_sched_barrier(0);
             mh(avB, u, 1);
-            PW_LOAD_B(min(c + u + 2, nchunks - 1), u);
+            load_B(min(c + u + 2, nchunks - 1), u);
         }
     }
 
     }       // fp32-MFMA operand path
-    PW_STAMP(58);
     // ---- epilogue: scale/shift (+same-size residual) (+ReLU), NHWC stores ------------------------------------------------------------------------
     // accumulator register r of lane half hh is pixel row (r & 3) + 8 * (r >> 2) + 4 * hh of the 32-pixel sub-tile; the lane is the cout
     const long wpix0 = pix0 + wm * (MT * 32);
@@ -664,32 +610,12 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
     };
     if (interior) epilogue(std::true_type{});
     else epilogue(std::false_type{});
-#ifdef PW_TRACE
-    PW_STAMP(59);
-    if (tracing) {
-        trl[62] = __builtin_amdgcn_s_memrealtime();
-        for (int i = 0; i < 64; ++i) trc[i] = trl[i];
-    }
-#endif
 }
 
 template <int MT, bool POOL, bool GA, bool UPRES = false, bool SPLITK = false, int SPLIT = 0>
 static int launch_pw_mt(ConvArgs& a, hipStream_t st) {
     constexpr int BM = 64 * MT;
-#ifdef PW_TRACE
-#ifndef PW_LDS_EXTRA
-#define PW_LDS_EXTRA 0
-#endif
-    constexpr int LDS_BYTES = 2 * BM * PST * 4 + 4 * 64 * 8 + PW_LDS_EXTRA;      // PW_LDS_EXTRA: experiments with one workgroup per CU
-    static DeviceOnce once;
-    int rc0 = once.run([]() {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pw_kernel<MT, POOL, GA, UPRES, SPLITK, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        return e == hipSuccess ? CMK_OK : fail(CMK_ELAUNCH, "conv_pw: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    });
-    if (rc0) return rc0;
-#else
     constexpr int LDS_BYTES = SPLIT == 2 && !GA ? 2 * (BM / 32) * 4 * 64 * 16 : SPLIT ? 2 * (BM / 32) * (SPLIT == 2 ? 2 : 3) * 64 * 16 : 2 * BM * PST * 4;       // 40 KB (MT 4) / 20 KB (MT 2) / 48 | 32 KB (split): under the 64 KB a kernel gets without an attribute
-#endif
     ConvProblem& p = a.p[0];
     p.tile_begin = 0;
     p.tiles_h = p.tiles_w = 0;

@@ -62,16 +62,7 @@ struct SP3L {
     static constexpr int ITEMS = HR * HC * 4;                       // float4 loads per chunk
     static constexpr int IT = (ITEMS + 255) / 256;
     static constexpr int LDS_BYTES = 2 * STAGE;
-#ifdef SP3_TRACE
-    static constexpr int LDS_ALLOC = LDS_BYTES + 4 * 128 * 8;
-#else
-    static constexpr int LDS_ALLOC = LDS_BYTES;
-#endif
 };
-
-#ifndef SP3_ABL
-#define SP3_ABL 0      // timing ablations (results wrong): 1 no activation loads, 2 no split / LDS writes, 4 no weight loads, 8 no A reads, 16 no MFMAs, 32 no stores, 64 all weight requests to the same lines, 128 no 2^-11 multiply of the weight piece
-#endif
 
 template <int GEO, int NB, int P, bool AFF>
 __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
@@ -133,9 +124,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     }
     f32x4 st[IT];
     auto load_X1 = [&](int chunk, int it) {
-#if !(SP3_ABL & 1)
         st[it] = sp3_buffer_load(rsrc, st_voff[it], chunk * 64, 0);
-#endif
     };
     auto load_X = [&](int chunk) {
 #pragma unroll
@@ -148,7 +137,6 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     auto pk = [](float x, float y) { return __builtin_bit_cast(unsigned, f16x2{(_Float16)x, (_Float16)y}); };       // round to nearest even
     auto unpk = [](unsigned p_) { const f16x2 h_ = __builtin_bit_cast(f16x2, p_); return f32x2{(float)h_.x, (float)h_.y}; };
     auto stage = [&](int buf, int chunk) {
-#if !(SP3_ABL & 2)
         unsigned char* dst = sb + buf * L::STAGE;
         f32x4 isc = {SX, SX, SX, SX}, ish = {0.f, 0.f, 0.f, 0.f};
         if constexpr (AFF) {
@@ -177,7 +165,6 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
                 *reinterpret_cast<u32x2*>(dst + st_dst[it] + 2 * L::PLANE) = m_;
             }
         }
-#endif
     };
 
     // ---- weights: wave-uniform base + lane ----------------------------------------------------------------------------------------------------
@@ -194,23 +181,17 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     const int wlane = lane * 16;
     int wblk[NB];
 #pragma unroll
-    for (int nn = 0; nn < NB; ++nn) wblk[nn] = ((SP3_ABL & 64) ? nn : min(cb0 + nn, nblocks - 1)) * P * 64;       // (tiles past cout_pad: any valid block, never stored)
+    for (int nn = 0; nn < NB; ++nn) wblk[nn] = min(cb0 + nn, nblocks - 1) * P * 64;       // (tiles past cout_pad: any valid block, never stored)
     static_assert(P == 2, "two fp16 pieces per operand");
     constexpr int BD = 2;                   // taps a weight request runs ahead (BD + 1 register sets; 9 taps % (BD + 1) == 0: no set is indexed at run time)
     constexpr int ST = 3, XT = 4;           // the tap after whose MFMAs the next chunk's halo is split and written / at which the one after is requested
     u32x4 wq[BD + 1][NB][P];
     auto load_B = [&](int set, int chunk, int tap, int part = -1) {      // part: one of the NB * P registers, -1: all
-#if !(SP3_ABL & 4)
-#if SP3_ABL & 64
-        const long k = 0 * (tap + chunk);        // every request of the launch hits the same lines
-#else
         const long k = ((long)tap * nchunks + chunk) * nblocks * P * 64;
-#endif
 #pragma unroll
         for (int j = 0; j < NB * P; ++j)
             if (part < 0 || part == j)
                 wq[set][j / P][j % P] = __builtin_bit_cast(u32x4, sp3_buffer_load(wrsrc, wlane, (int)(k + wblk[j / P] + (j % P) * 64) * 16, 0));
-#endif
     };
 
     // ---- A operand addresses: patch b = wr * 4 + m -> (b / BC, b % BC); lane -> pixel (li >> 3, li & 7) of the patch, k half hh ----------------
@@ -222,23 +203,6 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
         a_addr[m] = hh * L::PLANE + ((br * 4 + (li >> 3)) * L::PITCH + bc * 8 + (li & 7)) * 16;
     }
 
-#ifdef SP3_TRACE
-    // instrumented build (tools/ab/trace_sp3.py): lane 0 of every wave of every 8th workgroup stamps the shader clock into LDS (a global store in
-    // the loop would make every wait drain it) and copies the stamps to a.ws at the end: [0] start, [1] prologue done, chunk c < 6 at 2 + 11 c:
-    // barrier reached, passed, taps 0..8 done; [120] loop done, [121] stores issued, [122] / [123] real time at the end / start, [124] HW id
-    const bool tracing = a.ws && (blockIdx.x % 8) == 0 && lane == 0;
-    unsigned long long* trl = reinterpret_cast<unsigned long long*>(sb + L::LDS_BYTES) + wave * 128;
-    unsigned long long* trc = reinterpret_cast<unsigned long long*>(a.ws) + ((blockIdx.x / 8) * 4 + wave) * 128;
-#define SP3_STAMP(slot) do { if (tracing) trl[slot] = __builtin_readcyclecounter(); } while (0)
-    if (tracing) {
-        for (int i = 0; i < 128; ++i) trl[i] = 0;
-        trl[123] = __builtin_amdgcn_s_memrealtime();
-        trl[124] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | ((32 - 1) << 11));
-    }
-    SP3_STAMP(0);
-#else
-#define SP3_STAMP(slot) do { } while (0)
-#endif
     f32x16 acc[4][NB];
 #pragma unroll
     for (int m = 0; m < 4; ++m)
@@ -256,24 +220,14 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     // trip is about one tap of a wave's MFMAs, and the wait counter is in order: a halo request (HBM latency) issued between two weight requests
     // is waited for with the second one, BD taps later
     auto chunk_body = [&](int c) {
-#ifdef SP3_TRACE
-        if (c < 6) SP3_STAMP(2 + 11 * c);
-#endif
         __syncthreads();                // stage c & 1 is complete; everybody has read all of the other stage
-#ifdef SP3_TRACE
-        if (c < 6) SP3_STAMP(3 + 11 * c);
-#endif
         const unsigned char* As = sb + (c & 1) * L::STAGE;
         u32x4 av[2][P];                 // the A operands of patch m are read while patch m - 1 is multiplied
         auto read_A = [&](int slot, int tap, int m) {
             const int kh = tap / 3, kw = tap - kh * 3;
 #pragma unroll
             for (int p_ = 0; p_ < P; ++p_) {
-#if SP3_ABL & 8
-                av[slot][p_] = u32x4{(unsigned)tap, (unsigned)m, (unsigned)p_, 0u};
-#else
                 av[slot][p_] = *reinterpret_cast<const u32x4*>(As + a_addr[m] + (kh * L::PITCH + kw) * 16 + p_ * 2 * L::PLANE);
-#endif
             }
         };
         read_A(0, 0, 0);
@@ -299,11 +253,10 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
                 else if (tap < 8) read_A((m + 1) & 1, tap + 1, 0);
                 __builtin_amdgcn_sched_barrier(0);        // (the compiler otherwise sinks the requests to just before their use: no run-ahead left)
                 const f16x8 Ah = __builtin_bit_cast(f16x8, av[m & 1][0]), Am = __builtin_bit_cast(f16x8, av[m & 1][1]);
-#if !(SP3_ABL & 16)
                 if (m == 0) {
 #pragma unroll
                     for (int nn = 0; nn < NB; ++nn)
-                        Bhs[nn] = (SP3_ABL & 128) ? __builtin_bit_cast(f16x8, wq[set][nn][0]) : __builtin_bit_cast(f16x8, wq[set][nn][0]) * (_Float16)(1.f / RS);
+                        Bhs[nn] = __builtin_bit_cast(f16x8, wq[set][nn][0]) * (_Float16)(1.f / RS);
                 }
 #pragma unroll
                 for (int nn = 0; nn < NB; ++nn) {
@@ -314,37 +267,21 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
                     cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, cacc, 0, 0, 0);
                     acc[m][nn] = cacc;
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (tap == ST && c + 1 < nchunks) {       // the next chunk's halo: in registers since taps XT, XT + 1 of the last chunk
                 stage((c + 1) & 1, c + 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#ifdef SP3_TRACE
-            if (c < 6) SP3_STAMP(4 + 11 * c + tap);
-#endif
         }
     };
-    SP3_STAMP(1);
     for (int c = 0; c < nchunks; ++c) chunk_body(c);
-    SP3_STAMP(120);
 
     // ---- epilogue: scale / shift (+ReLU), NHWC stores: accumulator register r of lane half hh is pixel (r >> 2, (r & 3) + 4 hh) of the patch ---
-#if !(SP3_ABL & 32)
     float* yimg = Pb.y + (long)n * H * W * a.y_cs + a.y_co;
     const bool interior = oy0 + L::TH <= H && ox0 + L::TW <= W && (cb0 + NB) * 32 <= a.Cout;
     // fused GroupNorm statistics of the NEXT layer's normalisation (fcos.py:182-186): one {sum, sumsq} record per (spatial tile, pixel row of
     // waves), every group of it written by the wave that owns those couts (cmk_conv_gn_records: WROWS records per tile)
-    auto trace_out = [&]() {
-#ifdef SP3_TRACE
-        SP3_STAMP(121);
-        if (tracing) {
-            trl[122] = __builtin_amdgcn_s_memrealtime();
-            for (int i = 0; i < 128; ++i) trc[i] = trl[i];
-        }
-#endif
-    };
     const bool want_stats = a.gn_ws != nullptr;
     const float acc_scale = Pb.acc_scale * (1.f / SX);          // 1 / (S_x * S_w)
     auto put_stats = [&](int co, bool cvalid, float gs, float gss) {
@@ -394,7 +331,6 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
             }
             if (want_stats) put_stats(co, true, gs2.x + gs2.y, gss2.x + gss2.y);
         }
-        trace_out();
         return;
     }
     // border tiles: the same walk; a store is predicated on its row (wave-uniform) and its column / cout (per lane, four compares per patch)
@@ -451,8 +387,6 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
             if (want_stats) put_stats(co, cvalid, gs_b, gss_b);
         }
     }
-    trace_out();
-#endif
 }
 
 template <int GEO, int NB, int P>
@@ -460,9 +394,9 @@ static int launch_sp3_geo(ConvArgs& a, hipStream_t st) {
     typedef SP3L<GEO, P> L;
     static DeviceOnce once;
     int rc = once.run([]() {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sp3_kernel<GEO, NB, P, false>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_ALLOC);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sp3_kernel<GEO, NB, P, false>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_BYTES);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sp3_kernel<GEO, NB, P, true>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_ALLOC);
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sp3_kernel<GEO, NB, P, true>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_BYTES);
         return e == hipSuccess ? CMK_OK : fail(CMK_ELAUNCH, "conv_sp3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     });
     if (rc) return rc;
@@ -478,9 +412,9 @@ static int launch_sp3_geo(ConvArgs& a, hipStream_t st) {
     a.grid_y = cdiv(a.Cout, 32 * NB * SP3G<GEO>::WCOLS);
     const dim3 grid(((blocks + 7) / 8) * 8 * a.grid_y);
     if (a.p[0].in_scale)
-        hipLaunchKernelGGL((conv_sp3_kernel<GEO, NB, P, true>), grid, dim3(256), L::LDS_ALLOC, st, a);
+        hipLaunchKernelGGL((conv_sp3_kernel<GEO, NB, P, true>), grid, dim3(256), L::LDS_BYTES, st, a);
     else
-        hipLaunchKernelGGL((conv_sp3_kernel<GEO, NB, P, false>), grid, dim3(256), L::LDS_ALLOC, st, a);
+        hipLaunchKernelGGL((conv_sp3_kernel<GEO, NB, P, false>), grid, dim3(256), L::LDS_BYTES, st, a);
     return check_launch("conv_sp3");
 }
 

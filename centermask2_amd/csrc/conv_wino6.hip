@@ -37,28 +37,11 @@
 
 #include "wino6_common.hpp"
 
-#ifndef W6_TRACE_EVERY
-#define W6_TRACE_EVERY 16
-#endif
-#ifndef W6_ABL
-#define W6_ABL 0     // timing ablations (tools/ab): 1 no pass 1, 2 no halo loads, 4 no weight loads, 8 no barrier, 16 no W sample reads — results are wrong with any set
-#endif
-#ifndef W6_NOFENCE
-#define W6_FENCE __builtin_amdgcn_sched_barrier(0)
-#else
-#define W6_FENCE
-#endif
-
 namespace cmk {
 
 constexpr int W6_EX_FLOATS = 4 * 4 * 2 * 8 * 64;       // epilogue exchange: [src wave][dst wave][value][lane][register pair of the round] = 64 KiB
 template <int GEO> constexpr int w6_lds_bytes() { return (2 * W6G<GEO>::WB * 16 > W6_EX_FLOATS * 4) ? 2 * W6G<GEO>::WB * 16 : W6_EX_FLOATS * 4; }
-#ifdef W6_ONE_WG     // experiment: one workgroup per CU (how fast is a workgroup without a partner?)
-template <int GEO> constexpr int w6_lds_alloc() { return 96 * 1024; }
-#else
-template <int GEO> constexpr int w6_lds_alloc() { return w6_lds_bytes<GEO>(); }
 static_assert(2 * w6_lds_bytes<0>() <= LDS_CU && 2 * w6_lds_bytes<1>() <= LDS_CU, "two workgroups per CU");
-#endif
 
 // AFF: the producer's GroupNorm+ReLU is applied to the input in pass 1 (FCOS tower convs 2-4 and the predictors)
 template <bool AFF, int GEO>
@@ -137,10 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     f32x4 in_sc = {1.f, 1.f, 1.f, 1.f}, in_sh = {0.f, 0.f, 0.f, 0.f};
     auto load_D = [&](int chunk) {
 #pragma unroll
-#ifndef W6_HALO_AUX
-#define W6_HALO_AUX 0          // cache policy of the halo loads (experiments: 1 sc0, 2 nt, 16 sc1)
-#endif
-        for (int i = 0; i < 6; ++i) d[i] = w6_buffer_load(rsrc, voff0 + i * row_bytes, chunk * 32, W6_HALO_AUX);
+        for (int i = 0; i < 6; ++i) d[i] = w6_buffer_load(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
         if (AFF) {
             in_sc = *reinterpret_cast<const f32x4*>(P.in_scale + chunk * 8 + aff_off);
             in_sh = *reinterpret_cast<const f32x4*>(P.in_shift + chunk * 8 + aff_off);
@@ -192,9 +172,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     const int u_lane_off = lane * 4;
     f32x4 ub[3][3];
     auto load_U = [&](int step, int buf) {          // step = chunk*3 + s
-#if W6_ABL & 4
-        if (step > 2) return;
-#endif
         const int c = step / 3, s = step - c * 3;
         const float* src = u_wave + c * u_chunk + s * (3 * 256);
 #pragma unroll
@@ -202,19 +179,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     };
     const int total_steps = nchunks * 3;                        // END of the step range
 
-#ifdef W6_TRACE
-    // instrumented build (tools/ab/trace_wino6.py): lane 0 of every wave of every 16th workgroup stamps the shader clock into a.ws
-    unsigned long long* trc = (a.ws && (blockIdx.x % W6_TRACE_EVERY) == 0 && lane == 0) ? reinterpret_cast<unsigned long long*>(a.ws) + ((blockIdx.x / W6_TRACE_EVERY) * 4 + wave) * 64 : nullptr;
-    int trn = 0;
-#define W6_STAMP() do { if (trc) { trc[trn] = __builtin_readcyclecounter(); } ++trn; } while (0)
-    if (trc) {
-        trc[63] = __builtin_amdgcn_s_memrealtime();
-        trc[61] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | ((32 - 1) << 11));       // HW_REG_HW_ID (wave slot, SIMD, CU, SH, SE)
-        trc[60] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((32 - 1) << 11));      // HW_REG_XCC_ID
-    }
-#else
-#define W6_STAMP() do { } while (0)
-#endif
     if (GEO == 1) {
         // halo columns 15..17 (image columns >= 14) are zero for every image this geometry accepts: their W slots are cleared here, once,
         // in both buffers, and pass 1 never touches them
@@ -225,7 +189,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
             sW[(qb >> 1) * G::WB + w6_slot<GEO>(qb & 1, r, a6, 15 + c3)] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
-    W6_STAMP();                                       // 0: start
     // ---- prologue ----------------------------------------------------------------------------------------------------------------
     // the halos of chunks 0 and 1 and the first weights are requested together: one memory round trip before the first MFMA
     load_D(c_lo);
@@ -265,11 +228,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
         const f32x2* w2 = reinterpret_cast<const f32x2*>(wrow) + h;
         X5 x;
         constexpr int K = G::CK;
-#if W6_ABL & 16
-        x.x0 = x.x1 = x.x2 = x.x3 = x.x4 = f32x2{1.f, 2.f};
-        asm volatile("" : "+v"(x.x0), "+v"(x.x1), "+v"(x.x2), "+v"(x.x3), "+v"(x.x4) : "v"(w2));
-        return x;
-#endif
         if (!second) { x.x0 = w2[0 * 2]; x.x1 = w2[K * 2]; x.x2 = w2[2 * K * 2]; x.x3 = w2[3 * K * 2]; x.x4 = w2[1 * 2]; }
         else         { x.x0 = w2[K * 2]; x.x1 = w2[2 * K * 2]; x.x2 = w2[3 * K * 2]; x.x3 = w2[1 * 2]; x.x4 = w2[(K + 1) * 2]; }
         return x;
@@ -281,11 +239,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
         const f32x2* a2 = reinterpret_cast<const f32x2*>(wa) + h;
         X5 x;
         constexpr int K = G::CK;
-#if W6_ABL & 16
-        x.x0 = x.x1 = x.x2 = x.x3 = x.x4 = f32x2{1.f, 2.f};
-        asm volatile("" : "+v"(x.x0), "+v"(x.x1), "+v"(x.x2), "+v"(x.x3), "+v"(x.x4) : "v"(a2), "v"(w3));
-        return x;
-#endif
         x.x0 = a2[0]; x.x1 = a2[K * 2]; x.x2 = a2[2 * K * 2]; x.x3 = reinterpret_cast<const f32x2*>(w3)[h]; x.x4 = a2[1 * 2];
         return x;
     };
@@ -310,26 +263,13 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
         else            { asm volatile("" ::: "memory"); w6_half_second(x.x0, x.x1, x.x2, x.x3, x.x4, five, v0, v1, v2); }
         mm(v0, v1, v2, h, 2, 6);
     };
-    W6_STAMP();                                       // 1: prologue done
     // two periods per trip: the W buffer of a period is then a compile-time offset of every LDS instruction (the parity as a register cost
     // vector adds per period)
     auto period = [&](const int c, auto parity) {
         constexpr int wcur = decltype(parity)::value * W6_WB;
         f32x4* wnext = sW + (1 - decltype(parity)::value) * W6_WB;
         const int step = c * 3;
-#if !(W6_ABL & 8)
         __syncthreads();
-#endif
-#ifdef W6_TRACE
-        if (c < 40) W6_STAMP();                       // 2 + c: period c entered
-#endif
-        // the LDS reads of half-step k+1 are issued in front of the MFMAs of half-step k: their latency hides under the 6 MFMAs
-#ifdef W6_TRACE
-#define W6_STAMP_AT(slot) do { if (trc && c == 8) trc[slot] = __builtin_readcyclecounter(); } while (0)
-#else
-#define W6_STAMP_AT(slot) do { } while (0)
-#endif
-        W6_STAMP_AT(50);
         // AHEAD (variants without the fused input affine): the LDS reads of half-step k+1 are issued in front of the MFMAs of half-step k.
         // With the affine its scale/shift registers leave no room for the second sample set (6 spilled registers, reloaded every period):
         // there each half-step reads its own samples.
@@ -338,33 +278,23 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
         X5 xa = rd(wA + wcur, false, 0), xb;
         if (AHEAD) xb = rd(wA + wcur, false, 1);
         half_step(xa, false, 0, 0, 0);
-        W6_STAMP_AT(51);                              // after reads + transform + 6 MFMAs issued
         if (AHEAD) xa = rd(wA + wcur, true, 0); else xb = rd(wA + wcur, false, 1);
         half_step(xb, false, 1, 0, 0);
-        W6_STAMP_AT(52);                              // step 0 issued
-        W6_FENCE;
-#if !(W6_ABL & 1)
+        __builtin_amdgcn_sched_barrier(0);
         pass1(wnext);
-#endif
-        W6_STAMP_AT(53);                              // pass 1 done (LDS writes issued)
-#if !(W6_ABL & 2)
         load_D(min(c + 2, nchunks - 1));
-#endif
-        W6_STAMP_AT(54);                              // halo loads issued
-        W6_FENCE;
+        __builtin_amdgcn_sched_barrier(0);
         load_U(min(step + 3, total_steps - 1), 0);
         if (AHEAD) xb = rd(wA + wcur, true, 1); else xa = rd(wA + wcur, true, 0);
         half_step(xa, true, 0, 1, 3);
         if (AHEAD) xa = rdB(wBa + wcur, wB3 + wcur, 0); else xb = rd(wA + wcur, true, 1);
         half_step(xb, true, 1, 1, 3);
-        W6_STAMP_AT(55);                              // step 1 issued
-        W6_FENCE;
+        __builtin_amdgcn_sched_barrier(0);
         load_U(min(step + 4, total_steps - 1), 1);
         if (AHEAD) xb = rdB(wBa + wcur, wB3 + wcur, 1); else xa = rdB(wBa + wcur, wB3 + wcur, 0);
         half_stepB(xa, 0);
         if (!AHEAD) xb = rdB(wBa + wcur, wB3 + wcur, 1);
         half_stepB(xb, 1);
-        W6_STAMP_AT(56);                              // step 2 issued
     };
     for (int c = c_lo; c < nchunks; c += 2) {     // an even number of chunks: Cin is a multiple of 16 (validate), split-K bounds are even (host)
         period(c, std::integral_constant<int, 0>{});
@@ -380,12 +310,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     const bool cvalid = co < a.Cout;
     float sc = P.scale[min(co, a.Cout - 1)];
     float sh = P.shift[min(co, a.Cout - 1)];
-#ifdef W6_TRACE
-    trn = 42;
-#endif
-    W6_STAMP();                                       // 42: loop done (own MFMAs issued)
     __syncthreads();
-    W6_STAMP();                                       // 43: everybody done
     // The stores below sit in per-tile predicated blocks; the compiler's wait-count pass cannot prove across their joins that the two loads
     // above have landed and would put `s_waitcnt vmcnt(0)` in front of every store — which also waits for the previous STORE to retire
     // (measured: 340 ns per store, 26 us of a 76 us workgroup).  Wait once here and hand the values over through an asm the pass
@@ -448,9 +373,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
                 for (int k = 0; k < 8; ++k) ex2[(((wave * 4 + dd) * 8 + k) << 6) + lane] = v[k];
             }
         }
-        W6_STAMP();                                   // 44 / 47: round written
         __syncthreads();
-        W6_STAMP();                                   // 45 / 48: round visible
         // P[a][j]: rows 0..3 from waves 0..3 (values 0..3), row 4 = halves of waves 0, 1, row 5 = halves of waves 2, 3 (values 4..7)
         f32x2 Pm[6][4];
         {
@@ -537,16 +460,12 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
                     gss2 = __builtin_elementwise_fma(t, yv[i][j], gss2);
                 }
         }
-        W6_STAMP();                                   // 46 / 49: round stored
         if (q == 0) __syncthreads();                        // the exchange buffer is reused by round 1
     }
     gs += gs2.x + gs2.y;
     gss += gss2.x + gss2.y;
     // fused GroupNorm statistics of the NEXT layer's normalisation (fcos.py:182-186): one {sum, sumsq} record per
     // (spatial tile, wave, group)
-#ifdef W6_TRACE
-    if (trc) trc[62] = __builtin_amdgcn_s_memrealtime();
-#endif
     if (a.gn_ws) {
         for (int o = 1; o < a.gn_cpg; o <<= 1) { gs += __shfl_xor(gs, o); gss += __shfl_xor(gss, o); }
         gs += __shfl_xor(gs, 32);
@@ -563,9 +482,9 @@ template <int GEO>
 static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
     static DeviceOnce once;
     int rc = once.run([]() {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6_kernel<false, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, w6_lds_alloc<GEO>());
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6_kernel<false, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, w6_lds_bytes<GEO>());
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6_kernel<true, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, w6_lds_alloc<GEO>());
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6_kernel<true, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, w6_lds_bytes<GEO>());
         return e == hipSuccess ? CMK_OK : fail(CMK_ELAUNCH, "conv_wino6: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     });
     if (rc) return rc;
@@ -587,9 +506,9 @@ static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
     if (a.ksplit < 1) a.ksplit = 1;
     const dim3 grid(((blocks + 7) / 8) * 8 * a.grid_y, a.ksplit);
     if (a.p[0].in_scale)
-        hipLaunchKernelGGL((conv_wino6_kernel<true, GEO>), grid, dim3(256), w6_lds_alloc<GEO>(), st, a);
+        hipLaunchKernelGGL((conv_wino6_kernel<true, GEO>), grid, dim3(256), w6_lds_bytes<GEO>(), st, a);
     else
-        hipLaunchKernelGGL((conv_wino6_kernel<false, GEO>), grid, dim3(256), w6_lds_alloc<GEO>(), st, a);
+        hipLaunchKernelGGL((conv_wino6_kernel<false, GEO>), grid, dim3(256), w6_lds_bytes<GEO>(), st, a);
     return check_launch("conv_wino6");
 }
 

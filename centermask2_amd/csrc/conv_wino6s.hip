@@ -28,17 +28,6 @@
 
 #include "wino6_common.hpp"
 
-#ifndef W6S_FENCE
-#define W6S_FENCE __builtin_amdgcn_sched_barrier(0)
-#endif
-#ifndef W6S_PRIO
-#define W6S_PRIO 1    // wave priority during the transform phase (0..3); measured 1.8 % faster than 0 on the model's map shapes, 2 and 3 the same
-#endif
-#ifndef W6S_ABL
-#define W6S_ABL 0     // timing ablations (tools/ab; results are wrong with any set): 1 no pass 1, 2 no halo loads, 4 no weight loads, 8 no pass 2,
-#endif                //   16 no MFMAs, 32 no barrier, 64 no V reads; finer: 128 no V stores (pass 2), 256 no W stores (pass 1), 512 no pass-2 VALU,
-                      //   1024 no W sample reads, 2048 no pass-1 VALU
-
 namespace cmk {
 
 __device__ f32x2 w6s_buffer_load2(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
@@ -158,18 +147,10 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
         }
         if (GEO == 1 && !p_active) return;
         f32x2 w0, w1, w2, w3, w4, w5;
-#if W6S_ABL & 2048
-        w0 = d[0]; w1 = d[1]; w2 = d[2]; w3 = d[3]; w4 = d[4]; w5 = d[5];
-#else
         w6_half_first(d[0], d[1], d[2], d[3], d[4], five, w0, w1, w2);
         w6_half_second(d[1], d[2], d[3], d[4], d[5], five, w3, w4, w5);
-#endif
-#if W6S_ABL & 256
-        asm volatile("" :: "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "v"(w5));
-#else
         dst[0 * 2 * AP] = w0; dst[1 * 2 * AP] = w1; dst[2 * 2 * AP] = w2;
         dst[3 * 2 * AP] = w3; dst[4 * 2 * AP] = w4; dst[5 * 2 * AP] = w5;
-#endif
     };
 
     // ---- pass 2 tasks of this wave ------------------------------------------------------------------------------------------------
@@ -192,27 +173,14 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     struct X5 { f32x2 x0, x1, x2, x3, x4; };
     auto rd5 = [&](const f32x2* pa, const f32x2* p3) {
         X5 x;
-#if W6S_ABL & 1024
-        x.x0 = x.x1 = x.x2 = x.x3 = x.x4 = f32x2{1.f, 2.f};
-        asm volatile("" : "+v"(x.x0), "+v"(x.x1), "+v"(x.x2), "+v"(x.x3), "+v"(x.x4));
-#else
         x.x0 = pa[0]; x.x1 = pa[K * 2]; x.x2 = pa[2 * K * 2]; x.x3 = p3[0]; x.x4 = pa[1 * 2];
-#endif
         return x;
     };
     auto taskX = [&](const X5& x, f32x2* dst) {        // which half is wave-uniform; only the transform sits in the branch
         f32x2 v0, v1, v2;
-#if W6S_ABL & 512
-        v0 = x.x0 ; v1 = x.x1; v2 = x.x2; asm volatile("" :: "v"(x.x3), "v"(x.x4));
-#else
         if (halfX == 0) { asm volatile("" ::: "memory"); w6_half_first(x.x0, x.x1, x.x2, x.x3, x.x4, five, v0, v1, v2); }
         else            { asm volatile("" ::: "memory"); w6_half_second(x.x0, x.x1, x.x2, x.x3, x.x4, five, v0, v1, v2); }
-#endif
-#if W6S_ABL & 128
-        asm volatile("" :: "v"(v0), "v"(v1), "v"(v2));
-#else
         dst[0] = v0; dst[64 * 2] = v1; dst[2 * 64 * 2] = v2;
-#endif
     };
     // X with both channel pairs at once: 5 ds_read_b128 (conflict-free by the TP rule, as conv_wino6.hip's b128 reads) and 3 ds_write_b128
     // (a contiguous KiB each) instead of 10 + 6 eight-byte accesses with their 2-way bank conflicts
@@ -239,16 +207,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     };
     auto taskY = [&](const X5& x, f32x2* dst) {
         f32x2 v0, v1, v2;
-#if W6S_ABL & 512
-        v0 = x.x0 ; v1 = x.x1; v2 = x.x2; asm volatile("" :: "v"(x.x3), "v"(x.x4));
-#else
         w6_half_second(x.x0, x.x1, x.x2, x.x3, x.x4, five, v0, v1, v2);
-#endif
-#if W6S_ABL & 128
-        asm volatile("" :: "v"(v0), "v"(v1), "v"(v2));
-#else
         dst[0] = v0; dst[64 * 2] = v1; dst[2 * 64 * 2] = v2;
-#endif
     };
 
     // ---- MFMA side -------------------------------------------------------------------------------------------------------------
@@ -262,23 +222,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     const int u_lane_off = lane * 4;
     f32x4 ub[9];
     auto load_U1 = [&](int chunk, int k) {
-#if W6S_ABL & 4
-        if (chunk > 0) return;
-#endif
         ub[k] = *reinterpret_cast<const f32x4*>(u_wave + chunk * u_chunk + (u_lane_off + k * 256));
     };
 
-#ifdef W6S_TRACE
-    // instrumented build (tools/ab/trace_wino6s.py): lane 0 of every wave of every 8th workgroup stamps the shader clock into a.ws
-    unsigned long long* trc = (a.ws && (blockIdx.x % 8) == 0 && lane == 0) ? reinterpret_cast<unsigned long long*>(a.ws) + ((blockIdx.x / 8) * 8 + wave) * 64 : nullptr;
-#define W6S_STAMP(slot) do { if (trc) trc[slot] = __builtin_readcyclecounter(); } while (0)
-#define W6S_STAMP_P(cc, k) do { if ((cc) < 9) W6S_STAMP(3 + 4 * (cc) + (k)); } while (0)
-    if (trc) trc[63] = __builtin_amdgcn_s_memrealtime();
-#else
-#define W6S_STAMP(slot) do { } while (0)
-#define W6S_STAMP_P(cc, k) do { } while (0)
-#endif
-    W6S_STAMP(0);
     if (GEO == 1) {
         // halo columns 15..17 (image columns >= 14) are zero for every image this geometry accepts: their W slots are cleared once, in both
         // buffers, and pass 1 never touches them
@@ -342,81 +288,14 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     //   in period c:  the MFMAs read V(c) [buffer c & 1];  pass 2 turns W(c+1) [buffer (c+1) & 1] into V(c+1);  pass 1 turns the halo of
     //   chunk c+2 (in registers since period c-1) into W(c+2) [buffer c & 1];  the halo of chunk c+3 and the weights of chunk c+1 are requested.
     //   Past the last chunk the transforms run on repeated data and nobody reads their output.
-    auto mm4 = [&](const f32x4 va, const int k) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[j], ub[k][j], acc[k], 0, 0, 0);
-    };
-    auto period = [&](const int c, auto parity, auto ACT) {
-        constexpr int par = decltype(parity)::value;
-#if W6S_ABL & 16
-        constexpr bool A = false;
-#else
-        constexpr bool A = decltype(ACT)::value;
-#endif
-        constexpr int vcur = par * VS;                       // slots
-        constexpr int vnxt2 = (1 - par) * VS * 2;            // f32x2 units
-        constexpr int wrd2 = (1 - par) * WB * 2;
-        constexpr int wwr = par * WB * 2;
-        const int cn = min(c + 1, nchunks - 1);
-#if !(W6S_ABL & 32)
-        __syncthreads();
-#endif
-        f32x4 va0, va1, va2;
-#if W6S_ABL & 64
-#define W6S_VRD(dst, src) dst = f32x4{1.f, 2.f, 3.f, 4.f}
-#else
-#define W6S_VRD(dst, src) dst = src
-#endif
-        if (A) { W6S_VRD(va0, vA[vcur + 0 * 64]); W6S_VRD(va1, vA[vcur + 1 * 64]); W6S_VRD(va2, vA[vcur + 2 * 64]); }
-#if W6S_ABL & 8
-#define W6S_P2(stmt)
-        X5 x;
-#else
-#define W6S_P2(stmt) stmt
-        X5 x = rd5(xa + wrd2, x3 + wrd2);
-#endif
-        W6S_FENCE;
-#if !(W6S_ABL & 1)
-        pass1(wwr2 + wwr);
-#endif
-#if !(W6S_ABL & 2)
-        load_D(min(c + 3, nchunks - 1));
-#endif
-        W6S_FENCE;
-        if (A) { mm4(va0, 0); load_U1(cn, 0); W6S_VRD(va0, vA[vcur + 3 * 64]); }
-        W6S_FENCE;
-        W6S_P2(taskX(x, vX + vnxt2));
-        W6S_P2(x = rd5(xa + wrd2 + 1, x3 + wrd2 + 1));
-        W6S_FENCE;
-        if (A) { mm4(va1, 1); load_U1(cn, 1); W6S_VRD(va1, vA[vcur + 4 * 64]); }
-        W6S_FENCE;
-        if (A) { mm4(va2, 2); load_U1(cn, 2); W6S_VRD(va2, vA[vcur + 5 * 64]); }
-        W6S_FENCE;
-        W6S_P2(taskX(x, vX + vnxt2 + 1));
-        W6S_P2(x = rd5(ya + wrd2, y3 + wrd2));
-        W6S_FENCE;
-        if (A) { mm4(va0, 3); load_U1(cn, 3); W6S_VRD(va0, vB[vcur + 0 * 64]); }
-        W6S_FENCE;
-        if (A) { mm4(va1, 4); load_U1(cn, 4); W6S_VRD(va1, vB[vcur + 1 * 64]); }
-        W6S_FENCE;
-        W6S_P2(taskY(x, vY + vnxt2));
-        W6S_FENCE;
-        if (A) { mm4(va2, 5); load_U1(cn, 5); W6S_VRD(va2, vB[vcur + 2 * 64]); }
-        W6S_FENCE;
-        if (A) { mm4(va0, 6); load_U1(cn, 6); }
-        W6S_FENCE;
-        if (A) { mm4(va1, 7); load_U1(cn, 7); }
-        W6S_FENCE;
-        if (A) { mm4(va2, 8); load_U1(cn, 8); }
-    };
-    // Staggered schedule (W6S_SCHED 1, the default): the two waves of a SIMD (wave w and w + 4, i.e. the two cout tiles) would otherwise run
-    // the same phases at the same time — both transforming, the matrix pipe idle; both issuing MFMAs, queueing.  Between two barriers waves
-    // 0-3 do their transforms FIRST and then their MFMAs, waves 4-7 issue their MFMAs first and transform LAST: one wave of a SIMD always
-    // has MFMAs to issue.  There is ONE copy of the code: the instruction stream is the cycle  T(c) M(c) T(c+1) M(c+1) ...  and only the
-    // place of the barrier in it differs — waves 0-3:  B T(c) M(c) B ...,  waves 4-7:  B M(c) T(c) B ...  = the same loop body
-    // [T(c); M(c + ct)] with the barrier after M (ct = 0) or between T and M (ct = 1), one extra M(0) in front for ct = 1.  (Two copies of
-    // the transforms under complementary wave-uniform branches made the register allocator spill 246 registers.)  Three accumulators are
-    // walked round-robin so that consecutive MFMAs never depend on each other.
+    // Staggered schedule: the two waves of a SIMD (wave w and w + 4, i.e. the two cout tiles) would otherwise run the same phases at the
+    // same time — both transforming, the matrix pipe idle; both issuing MFMAs, queueing.  Between two barriers waves 0-3 do their
+    // transforms FIRST and then their MFMAs, waves 4-7 issue their MFMAs first and transform LAST: one wave of a SIMD always has MFMAs to
+    // issue.  There is ONE copy of the code: the instruction stream is the cycle  T(c) M(c) T(c+1) M(c+1) ...  and only the place of the
+    // barrier in it differs — waves 0-3:  B T(c) M(c) B ...,  waves 4-7:  B M(c) T(c) B ...  = the same loop body [T(c); M(c + ct)] with
+    // the barrier after M (ct = 0) or between T and M (ct = 1), one extra M(0) in front for ct = 1.  (Two copies of the transforms under
+    // complementary wave-uniform branches made the register allocator spill 246 registers.)  Three accumulators are walked round-robin so
+    // that consecutive MFMAs never depend on each other.
     auto mm12 = [&](const f32x4 a0, const f32x4 a1, const f32x4 a2, const int k0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -431,64 +310,34 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
         constexpr int vnxt2 = (1 - par) * VS * 2;            // f32x2 units
         constexpr int wrd2 = (1 - par) * WB * 2;
         constexpr int wwr = par * WB * 2;
-#if W6S_PRIO
-        __builtin_amdgcn_s_setprio(W6S_PRIO);             // the transform phase competes with the SIMD partner's MFMA stream for issue slots
-#endif
-#if !(W6S_ABL & 8)
-#ifdef W6S_X64
-        X5 x0 = rd5(xa + wrd2, x3 + wrd2);
-        X5 x1 = rd5(xa + wrd2 + 1, x3 + wrd2 + 1);
-#else
+        // the transform phase competes with the SIMD partner's MFMA stream for issue slots: priority 1 during it was measured 1.8 % faster
+        // than 0 on the model's map shapes, 2 and 3 the same
+        __builtin_amdgcn_s_setprio(1);
         X5q xq = rd5q(reinterpret_cast<const f32x4*>(xa + wrd2), reinterpret_cast<const f32x4*>(x3 + wrd2));
-#endif
         X5 xy = rd5(ya + wrd2, y3 + wrd2);
-#endif
-#if !(W6S_ABL & 1)
         pass1(wwr2 + wwr);
-#endif
-#if !(W6S_ABL & 2)
         load_D(min(c + 3, nchunks - 1));
-#endif
-#if !(W6S_ABL & 8)
-#ifdef W6S_X64
-        taskX(x0, vX + vnxt2);
-        taskX(x1, vX + vnxt2 + 1);
-#else
         taskXq(xq, reinterpret_cast<f32x4*>(vX + vnxt2));
-#endif
         taskY(xy, vY + vnxt2);
-#endif
-#if W6S_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
     };
     // M(cw): the 36 MFMAs of chunk cw on V(cw) (pa, pb: the wave's row-A / row-B operand pointers into that V buffer), weights of chunk cw + 1 requested
     auto M = [&](const int cw, const f32x4* pa, const f32x4* pb) {
         const int cn = min(cw + 1, nchunks - 1);
-        f32x4 va0, va1, va2, vb0, vb1, vb2;
-        W6S_VRD(va0, pa[0 * 64]); W6S_VRD(va1, pa[1 * 64]); W6S_VRD(va2, pa[2 * 64]);
-        W6S_VRD(vb0, pa[3 * 64]); W6S_VRD(vb1, pa[4 * 64]); W6S_VRD(vb2, pa[5 * 64]);
-        W6S_FENCE;
+        f32x4 va0 = pa[0 * 64], va1 = pa[1 * 64], va2 = pa[2 * 64];
+        const f32x4 vb0 = pa[3 * 64], vb1 = pa[4 * 64], vb2 = pa[5 * 64];
+        __builtin_amdgcn_sched_barrier(0);
         mm12(va0, va1, va2, 0);
         load_U1(cn, 0); load_U1(cn, 1); load_U1(cn, 2);
-        W6S_VRD(va0, pb[0 * 64]); W6S_VRD(va1, pb[1 * 64]); W6S_VRD(va2, pb[2 * 64]);
-        W6S_FENCE;
+        va0 = pb[0 * 64]; va1 = pb[1 * 64]; va2 = pb[2 * 64];
+        __builtin_amdgcn_sched_barrier(0);
         mm12(vb0, vb1, vb2, 3);
         load_U1(cn, 3); load_U1(cn, 4); load_U1(cn, 5);
-        W6S_FENCE;
+        __builtin_amdgcn_sched_barrier(0);
         mm12(va0, va1, va2, 6);
         load_U1(cn, 6); load_U1(cn, 7); load_U1(cn, 8);
-        W6S_FENCE;
+        __builtin_amdgcn_sched_barrier(0);
     };
-#if W6S_ABL & 16
-    const bool do_m = false;
-#else
-    const bool do_m = act;
-#endif
-#ifndef W6S_SCHED
-#define W6S_SCHED 1
-#endif
-#if W6S_SCHED == 1
     // Every path through the loop body issues the same memory operations in the same order — the M phase is unconditional inside the loop
     // (waves without a cout tile run their own copy of the loop, and the one M a ct = 1 wave must not run is peeled off with the last
     // trip): the compiler's s_waitcnt vmcnt(N) in front of pass 1 is the minimum over the paths, and with a skippable M between the halo
@@ -500,59 +349,28 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
         const f32x4* const vB_e = vB + ct * VS;
         const f32x4* const vA_o = vA + (1 - ct) * VS;
         const f32x4* const vB_o = vB + (1 - ct) * VS;
-        W6S_STAMP(1);
         __syncthreads();                                  // V(0) and W(1) complete
-        W6S_STAMP(2);
         if (DM && ct != 0) M(0, vA, vB);
         auto trip = [&](const int c, auto LAST) {
             constexpr bool last = decltype(LAST)::value;
-            W6S_STAMP_P(c, 0);
             T(c, std::integral_constant<int, 0>{});
-            W6S_STAMP_P(c, 1);
-#if !(W6S_ABL & 32)
             if (ct != 0) __syncthreads();
-#endif
-            W6S_STAMP_P(c, 2);
             if (DM) M(c + ct, vA_e, vB_e);
-            W6S_STAMP_P(c, 3);
-#if !(W6S_ABL & 32)
             if (ct == 0) __syncthreads();
-#endif
-            W6S_STAMP_P(c + 1, 0);
             T(c + 1, std::integral_constant<int, 1>{});
-            W6S_STAMP_P(c + 1, 1);
-#if !(W6S_ABL & 32)
             if (ct != 0) __syncthreads();
-#endif
-            W6S_STAMP_P(c + 1, 2);
             if (DM) {
                 if (!last) M(c + 1 + ct, vA_o, vB_o);
                 else if (ct == 0) M(c + 1, vA_o, vB_o);
             }
-            W6S_STAMP_P(c + 1, 3);
-#if !(W6S_ABL & 32)
             if (ct == 0) __syncthreads();
-#endif
         };
         int c = 0;
         for (; c + 2 < nchunks; c += 2) trip(c, std::false_type{});        // nchunks is even: Cin is a multiple of 16 (validate)
         trip(c, std::true_type{});
     };
-    if (do_m) loop(std::true_type{});
+    if (act) loop(std::true_type{});
     else loop(std::false_type{});
-#else
-    if (act) {
-        for (int c = 0; c < nchunks; c += 2) {
-            period(c, std::integral_constant<int, 0>{}, std::true_type{});
-            period(c + 1, std::integral_constant<int, 1>{}, std::true_type{});
-        }
-    } else {
-        for (int c = 0; c < nchunks; c += 2) {
-            period(c, std::integral_constant<int, 0>{}, std::false_type{});
-            period(c + 1, std::integral_constant<int, 1>{}, std::false_type{});
-        }
-    }
-#endif
 
     // ---- epilogue (conv_wino6.hip's, per cout tile: wave group ct works in its own 64 KiB of the exchange area) ----------------------
     // A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1].  Row pass in registers: per accumulator entry the wave's 6 + 3
@@ -563,9 +381,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     const bool cvalid = act && co < a.Cout;
     float sc = P.scale[min(co, a.Cout - 1)];
     float sh = P.shift[min(co, a.Cout - 1)];
-    W6S_STAMP(42);
     __syncthreads();
-    W6S_STAMP(43);
     asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %0\n\tv_mov_b32 %1, %1" : "+v"(sc), "+v"(sh) : : "memory");
     f32x2* ex2 = reinterpret_cast<f32x2*>(smem) + ct * (64 * 1024 / 8);        // exchange: [src wave][dst wave][value 0..7][lane] pairs = 64 KiB
     const float lo = co < a.relu_upto ? 0.f : __builtin_nanf("");      // max(v, NaN) = v: lanes without the ReLU
@@ -705,10 +521,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
         }
         if (q == 0) __syncthreads();                        // the exchange buffer is reused by round 1
     }
-    W6S_STAMP(49);
-#ifdef W6S_TRACE
-    if (trc) trc[62] = __builtin_amdgcn_s_memrealtime();
-#endif
     gs += gs2.x + gs2.y;
     gss += gss2.x + gss2.y;
     // fused GroupNorm statistics of the NEXT layer's normalisation (fcos.py:182-186): one {sum, sumsq} record per

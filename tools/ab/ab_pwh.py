@@ -1,4 +1,4 @@
-"""Same-session timing of conv_pw builds on the fp16-split form (tune 12): ab_pwh.py [--rounds R] <lib.so> [<lib.so> ...]  (ablation builds: times only)"""
+"""Same-session timing of conv_pw builds on the fp16-split form (tune 12): ab_pwh.py [--rounds R] <lib.so> [<lib.so> ...]  (times only; the outputs are not checked)"""
 import sys, os, subprocess
 SHAPES = [("OSA2_cat", 200, 320, 768, 256), ("OSA3_cat", 100, 160, 1056, 512), ("OSA4_cat", 50, 80, 1472, 768), ("OSA5_cat", 25, 40, 1888, 1024)]
 if sys.argv[1] != "--one":

@@ -1,5 +1,5 @@
-"""Same-session timing of conv_wino6s builds (ablations, variants): ab_wino6s.py [--rounds R] [--sc 64] <lib.so> [<lib.so> ...]
-One subprocess per (round, library), interleaved, best-of per shape.  Results of ablation builds are wrong by design; only times count."""
+"""Same-session timing of conv_wino6s in library builds (tools/ab/build_variant.sh): ab_wino6s.py [--rounds R] [--sc 64] <lib.so> [<lib.so> ...]
+One subprocess per (round, library), interleaved, best-of per shape.  Only times are compared; the outputs are not checked."""
 import sys, os, subprocess
 SHAPES = [("OSA2_x", 200, 320, 128, 128), ("OSA3_x", 100, 160, 160, 160), ("OSA4_x", 50, 80, 192, 192), ("fpn_p3", 100, 160, 256, 256), ("roi", 14, 14, 256, 256)]
 if sys.argv[1] != "--one":
