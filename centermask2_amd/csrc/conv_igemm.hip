@@ -1017,13 +1017,16 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         a.ws = d->splitk_ws;          // split-K slabs
         a.ksplit = d->splitk > 1 ? d->splitk : 1;
         a.cout_pad = cmk_conv_cout_pad(d->Cout);
-        if (a.ksplit > 1) {           // F(4x4) with split-K (32-cout form, map tiles): partial sums + the reduce kernel of the direct path
-            if (d->tune_sc == 64 || d->tune_wn != 1 || n != 1) return fail(CMK_EINVAL, "conv: Winograd split-K needs tune_sc 16, tune_wn 1, one problem%s", "");
-            return launch_wino6(a, 0, st);
+        if (d->tune_sc != 0 && d->tune_sc != 16 && d->tune_sc != 32 && d->tune_sc != 64)
+            return fail(CMK_EINVAL, "conv: tune_wm 6 takes tune_sc 16 (32 couts per workgroup), 32 (paired) or 64 (shared V)%s", "");
+        const bool pair = d->tune_sc == 32;      // 64 couts per workgroup, halo and pass 1 shared by the two cout tiles
+        if (a.ksplit > 1) {           // F(4x4) with split-K (conv_wino6.hip forms, map tiles): partial sums + the reduce kernel of the direct path
+            if (d->tune_sc == 64 || d->tune_wn != 1 || n != 1) return fail(CMK_EINVAL, "conv: Winograd split-K needs tune_sc 16 or 32, tune_wn 1, one problem%s", "");
+            return launch_wino6(a, 0, pair, st);
         }
         if (d->tune_wn != 1 && d->tune_wn != 2) return fail(CMK_EINVAL, "conv: tune_wm 6 takes tune_wn 1 (12x40 map tiles) or 2 (pairs of RoI maps up to 16x14)%s", "");
         if (d->tune_sc == 64) return launch_wino6s(a, d->tune_wn == 2 ? 1 : 0, st);      // 64 couts per workgroup, shared frequency image
-        return launch_wino6(a, d->tune_wn == 2 ? 1 : 0, st);
+        return launch_wino6(a, d->tune_wn == 2 ? 1 : 0, pair, st);
     }
     a.ksplit = d->splitk > 1 ? d->splitk : 1;
     a.ws = d->splitk_ws;

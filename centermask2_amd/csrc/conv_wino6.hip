@@ -31,6 +31,13 @@
 //     NHWC stores, GroupNorm statistics — on pairs of accumulator registers with packed fp32, interior tiles stored through a scalar-walked
 //     base + one lane offset per tile (~460 VALU instructions per wave; the scalar form took ~1080 and 12.4 us beside a partner's MFMAs).
 //
+// Paired form (conv_wino6p_kernel, cmk.h tune_sc 32): ONE workgroup of 8 waves per CU covers a spatial tile x 64 couts — waves 0-3 are
+// cout tile 2j, waves 4-7 cout tile 2j+1, each wave exactly a conv_wino6 wave (9 frequencies x 32 tiles x 32 couts, pass 2 in its own
+// registers, the same weights, the same barrier per chunk).  Only what every cout tile of a spatial tile used to repeat is shared: the
+// halo loads, pass 1 and the fused input affine run once per 64 couts, spread over all 512 threads — thread = (pass-1 item, channel
+// pair), so each holds half a conv_wino6 thread's halo registers and does half its pass-1 work.  The W image is the same (two buffers),
+// the two halves use disjoint epilogue exchange areas.  Same values in the same order: bit-identical to conv_wino6_kernel.
+//
 // Reference call sites replaced: the same 3x3 stride-1 convs as the 2x2 kernel (vovnet.py:205-219, d2 FPN outputs, fcos.py:169-200,
 // sam.py:58-70, maskiou_head.py:81-88).
 #include <type_traits>
@@ -40,27 +47,41 @@
 namespace cmk {
 
 constexpr int W6_EX_FLOATS = 4 * 4 * 2 * 8 * 64;       // epilogue exchange: [src wave][dst wave][value][lane][register pair of the round] = 64 KiB
-template <int GEO> constexpr int w6_lds_bytes() { return (2 * W6G<GEO>::WB * 16 > W6_EX_FLOATS * 4) ? 2 * W6G<GEO>::WB * 16 : W6_EX_FLOATS * 4; }
+// PAIR: one exchange area per cout tile
+template <int GEO, bool PAIR = false> constexpr int w6_lds_bytes() {
+    return (2 * W6G<GEO>::WB * 16 > (PAIR ? 2 : 1) * W6_EX_FLOATS * 4) ? 2 * W6G<GEO>::WB * 16 : (PAIR ? 2 : 1) * W6_EX_FLOATS * 4;
+}
 static_assert(2 * w6_lds_bytes<0>() <= LDS_CU && 2 * w6_lds_bytes<1>() <= LDS_CU, "two workgroups per CU");
+static_assert(w6_lds_bytes<0, true>() <= LDS_CU && w6_lds_bytes<1, true>() <= LDS_CU, "paired form: one workgroup per CU");
 
 // AFF: the producer's GroupNorm+ReLU is applied to the input in pass 1 (FCOS tower convs 2-4 and the predictors)
-template <bool AFF, int GEO>
-__global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
+// PAIR: the paired form (header); false = conv_wino6_kernel
+template <bool AFF, int GEO, bool PAIR>
+__device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
     using G = W6G<GEO>;
     constexpr int W6_AP = G::AP, W6_WB = G::WB;
+    constexpr int NT = PAIR ? 512 : 256;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     f32x4* sW = reinterpret_cast<f32x4*>(smem);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = PAIR ? (wid & 3) : wid;                     // the wave's place in its cout tile: what conv_wino6 calls the wave
+    const int half = PAIR ? (wid >> 2) : 0;                      // PAIR: which of the workgroup's two cout tiles
     const int hh = lane >> 5, li = lane & 31;
 
     // XCD-aware order, as in the other conv kernels: the grid_y cout tiles of one spatial tile go to the same XCD, back to back
+    // (PAIR: the ceil(grid_y / 2) pairs of them)
+    const int gy = PAIR ? (a.grid_y + 1) >> 1 : a.grid_y;
     const int xq = blockIdx.x >> 3, xcd = blockIdx.x & 7;
     // (the opposite, weight-stationary mapping — XCD k takes the cout tiles == k mod 8 of every spatial tile so that its L2 holds 1/8 of
     // U — was measured 3-4 % slower on the 256 -> 256 layers: every XCD then reads the whole input)
-    const int bx = (xq / a.grid_y) * 8 + xcd, by = xq % a.grid_y;
+    const int bx = (xq / gy) * 8 + xcd, by = xq % gy;
+    // this wave's 32-cout tile.  PAIR with an odd number of tiles: the upper half of the last pair has none; it reads the weights of the
+    // last tile (ct), computes, and stores nothing (co0 >= Cout)
+    const int ctile = PAIR ? 2 * by + half : by;
+    const int ct = PAIR ? min(ctile, a.grid_y - 1) : by;
     if (bx >= a.total_tiles) return;
     int pi = 0;
 #pragma unroll
@@ -79,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     } else {                      // a pair of whole images
         n = tile * 2; oh0 = 0; ow0 = 0;
     }
-    const int co0 = by * 32;
+    const int co0 = ctile * 32;
     // split-K (a.ksplit > 1, blockIdx.y): this workgroup owns the 8-channel chunks [c_lo, nchunks) of the conv's Cin / 8 and leaves raw partial
     // sums in a.ws (see the epilogue); for launches of about one round of workgroups whose life is one long chunk loop (the first conv of a
     // stage-4 / stage-5 OSA block: 512..1024 input channels on 50x80 / 25x40 maps) two or four workgroups share that loop
@@ -88,14 +109,17 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     const int nchunks = (int)((long)(ks + 1) * (a.Cin >> 3) / a.ksplit);       // END of this workgroup's chunk range (even bounds: host)
 
     // ---- pass 1 item of this thread ----------------------------------------------------------------------------------------------
+    // PAIR: thread = (item tid / 2, channel pair p_h = tid % 2 of its quad); lanes 4k..4k+3 then load the 32 contiguous bytes of a column
     int p_img, p_q, p_t, p_col;
     bool p_active;
-    G::item_of(tid, p_img, p_q, p_t, p_col, p_active);
-    // buffer resource over the image this thread stages (GEO 1: wave-uniform, waves 0-1 the first image of the pair, waves 2-3 the second;
-    // an image index past the batch gets an empty resource: every load returns 0): {base, num_records = bytes of the image, raw dword format}
+    G::item_of(PAIR ? (tid >> 1) : tid, p_img, p_q, p_t, p_col, p_active);
+    const int p_h = PAIR ? (tid & 1) : 0;
+    // buffer resource over the image this thread stages (GEO 1: wave-uniform, waves 0-1 the first image of the pair, waves 2-3 the second
+    // — PAIR: waves 0-3, 4-7; an image index past the batch gets an empty resource: every load returns 0): {base, num_records = bytes of
+    // the image, raw dword format}
     i32x4 rsrc;
     {
-        const int img_n = n + (GEO == 1 ? (wave >> 1) : 0);
+        const int img_n = n + (GEO == 1 ? (PAIR ? (wid >> 2) : (wave >> 1)) : 0);
         const unsigned long long base = (unsigned long long)(P.x + (long)min(img_n, P.N - 1) * H * W * a.x_cs);
         rsrc.x = __builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
         rsrc.y = __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffffull));
@@ -106,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     const int ih0 = oh0 - 1 + 4 * p_t, iw = ow0 - 1 + p_col;
     // byte offset of input row 0 of the item; rows above/below the image are out of the resource's range by themselves, a column
     // outside the image would alias the neighbouring row, so it is pushed out of range
-    const int voff0 = (iw >= 0 && iw < W) ? (ih0 * W + iw) * a.x_cs * 4 + (a.x_co + p_q * 4) * 4 : (int)0x80000000;
+    const int voff0 = (iw >= 0 && iw < W) ? (ih0 * W + iw) * a.x_cs * 4 + (a.x_co + p_q * 4 + p_h * 2) * 4 : (int)0x80000000;
     unsigned okm = 0;                                              // AFF only: relu(0*s + b) != 0, so padding needs the mask
     if (AFF) {
 #pragma unroll
@@ -114,16 +138,23 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     }
     // scale/shift of the fused input affine: wave-uniform base (per chunk) + one 32-bit lane offset (two 64-bit lane pointers cost the
     // variant the registers it does not have)
-    const unsigned aff_off = AFF ? (unsigned)(min(n + p_img, P.N - 1) * a.Cin + p_q * 4) : 0u;
+    const unsigned aff_off = AFF ? (unsigned)(min(n + p_img, P.N - 1) * a.Cin + p_q * 4 + p_h * 2) : 0u;
     const f32x2 five = {5.0f, 5.0f};                   // the one transform coefficient that is not an inline constant: an SGPR pair
-    f32x4 d[6];
-    f32x4 in_sc = {1.f, 1.f, 1.f, 1.f}, in_sh = {0.f, 0.f, 0.f, 0.f};
+    // the thread's halo samples: 4 channels (a quad), PAIR 2 (a pair)
+    using DV = std::conditional_t<PAIR, f32x2, f32x4>;
+    DV d[6];
+    DV in_sc, in_sh;
+    if constexpr (PAIR) { in_sc = f32x2{1.f, 1.f}; in_sh = f32x2{0.f, 0.f}; }
+    else { in_sc = f32x4{1.f, 1.f, 1.f, 1.f}; in_sh = f32x4{0.f, 0.f, 0.f, 0.f}; }
     auto load_D = [&](int chunk) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) d[i] = w6_buffer_load(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
+        for (int i = 0; i < 6; ++i) {
+            if constexpr (PAIR) d[i] = w6_buffer_load2(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
+            else d[i] = w6_buffer_load(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
+        }
         if (AFF) {
-            in_sc = *reinterpret_cast<const f32x4*>(P.in_scale + chunk * 8 + aff_off);
-            in_sh = *reinterpret_cast<const f32x4*>(P.in_shift + chunk * 8 + aff_off);
+            in_sc = *reinterpret_cast<const DV*>(P.in_scale + chunk * 8 + aff_off);
+            in_sh = *reinterpret_cast<const DV*>(P.in_shift + chunk * 8 + aff_off);
         }
     };
     const int p_dst = w6_slot<GEO>(p_q, (GEO == 1 ? 4 * p_img : 0) + p_t, 0, p_col);
@@ -134,18 +165,22 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 const float kinf = ((okm >> i) & 1u) ? __builtin_inff() : 0.f;
-                const f32x4 v = __builtin_elementwise_fma(d[i], in_sc, in_sh);
-                d[i] = f32x4{__builtin_amdgcn_fmed3f(v.x, 0.f, kinf), __builtin_amdgcn_fmed3f(v.y, 0.f, kinf),
-                             __builtin_amdgcn_fmed3f(v.z, 0.f, kinf), __builtin_amdgcn_fmed3f(v.w, 0.f, kinf)};
+                const DV v = __builtin_elementwise_fma(d[i], in_sc, in_sh);
+                if constexpr (PAIR) d[i] = f32x2{__builtin_amdgcn_fmed3f(v.x, 0.f, kinf), __builtin_amdgcn_fmed3f(v.y, 0.f, kinf)};
+                else d[i] = f32x4{__builtin_amdgcn_fmed3f(v.x, 0.f, kinf), __builtin_amdgcn_fmed3f(v.y, 0.f, kinf),
+                                  __builtin_amdgcn_fmed3f(v.z, 0.f, kinf), __builtin_amdgcn_fmed3f(v.w, 0.f, kinf)};
             }
         }
-        f32x2* dst = reinterpret_cast<f32x2*>(wbuf + p_dst);
+        f32x2* dst = reinterpret_cast<f32x2*>(wbuf + p_dst) + p_h;
         if (GEO == 1 && !p_active) return;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {                 // channel pairs: 12 packed instructions and 6 ds_write_b64 each
+        for (int h = 0; h < (PAIR ? 1 : 2); ++h) {    // channel pairs: 12 packed instructions and 6 ds_write_b64 each
             f32x2 e[6];
 #pragma unroll
-            for (int i = 0; i < 6; ++i) e[i] = h ? f32x2{d[i].z, d[i].w} : f32x2{d[i].x, d[i].y};
+            for (int i = 0; i < 6; ++i) {
+                if constexpr (PAIR) e[i] = d[i];
+                else e[i] = h ? f32x2{d[i].z, d[i].w} : f32x2{d[i].x, d[i].y};
+            }
             f32x2 w0, w1, w2, w3, w4, w5;
             w6_half_first(e[0], e[1], e[2], e[3], e[4], five, w0, w1, w2);
             w6_half_second(e[1], e[2], e[3], e[4], e[5], five, w3, w4, w5);
@@ -167,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     const f32x4* wB3 = wB + (halfB ? 1 : 3 * G::CK);
     // U image: [chunk][cout tile][wave][9 slots][lane 64][4 floats]; slot k < 6: frequency (rowA, k); k >= 6: (rowB, 3*halfB + k - 6);
     // lane = 32*hh + li holds channels 8*chunk + 4*hh .. +3 of output channel 32*tile + li
-    const float* u_wave = P.w + ((long)by * 4 + wave) * (9 * 256);       // wave-uniform: the loads take it as a scalar base, lane * 16 B as offset
+    const float* u_wave = P.w + ((long)ct * 4 + wave) * (9 * 256);       // wave-uniform: the loads take it as a scalar base, lane * 16 B as offset
     const long u_chunk = (long)a.grid_y * (36 * 256);
     const int u_lane_off = lane * 4;
     f32x4 ub[3][3];
@@ -182,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     if (GEO == 1) {
         // halo columns 15..17 (image columns >= 14) are zero for every image this geometry accepts: their W slots are cleared here, once,
         // in both buffers, and pass 1 never touches them
-        for (int i = tid; i < 2 * 2 * G::RG * 6 * 3; i += 256) {
+        for (int i = tid; i < 2 * 2 * G::RG * 6 * 3; i += NT) {
             const int c3 = i % 3, rest = i / 3;
             const int a6 = rest % 6, r2 = rest / 6;
             const int r = r2 % G::RG, qb = r2 / G::RG;          // qb = buffer * 2 + quad
@@ -192,15 +227,15 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     // ---- prologue ----------------------------------------------------------------------------------------------------------------
     // the halos of chunks 0 and 1 and the first weights are requested together: one memory round trip before the first MFMA
     load_D(c_lo);
-    f32x4 d_first[6];
+    DV d_first[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) d_first[i] = d[i];
-    f32x4 sc_first = in_sc, sh_first = in_sh;
+    DV sc_first = in_sc, sh_first = in_sh;
     load_D(min(c_lo + 1, nchunks - 1));
     load_U(c_lo * 3, 0);
     load_U(min(c_lo * 3 + 1, total_steps - 1), 1);
     {
-        f32x4 d_keep[6], sc_keep = in_sc, sh_keep = in_sh;
+        DV d_keep[6], sc_keep = in_sc, sh_keep = in_sh;
 #pragma unroll
         for (int i = 0; i < 6; ++i) { d_keep[i] = d[i]; d[i] = d_first[i]; }
         in_sc = sc_first; in_sh = sh_first;
@@ -273,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
         // AHEAD (variants without the fused input affine): the LDS reads of half-step k+1 are issued in front of the MFMAs of half-step k.
         // With the affine its scale/shift registers leave no room for the second sample set (6 spilled registers, reloaded every period):
         // there each half-step reads its own samples.
-        constexpr bool AHEAD = !AFF;
+        constexpr bool AHEAD = !AFF || PAIR;
         load_U(min(step + 2, total_steps - 1), 2);
         X5 xa = rd(wA + wcur, false, 0), xb;
         if (AHEAD) xb = rd(wA + wcur, false, 1);
@@ -326,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     // stores of interior tiles take a wave-uniform (row, column) base from the scalar unit plus one lane offset per tile: a VALU instruction
     // issued here waits for a gap in the MFMA stream of the other workgroup on the SIMD and takes the slot from it (trace: this epilogue
     // ran 12.4 us next to a partner, 5.6 us alone), so the epilogue is priced in VALU instructions — 3x fewer than the scalar form.
-    f32x2* ex2 = reinterpret_cast<f32x2*>(smem);        // exchange: [src wave][dst wave][value 0..7][lane] pairs = 64 KiB
+    f32x2* ex2 = reinterpret_cast<f32x2*>(smem + half * W6_EX_FLOATS);        // exchange: [src wave][dst wave][value 0..7][lane] pairs = 64 KiB (PAIR: per half)
     const float lo = (co < a.relu_upto && !raw) ? 0.f : __builtin_nanf("");      // max(v, NaN) = v: lanes without the ReLU
     const f32x2 sc2 = {sc, sc}, sh2 = {sh, sh};
     auto fma2 = [](f32x2 x, float k, f32x2 y) { return __builtin_elementwise_fma(x, f32x2{k, k}, y); };
@@ -478,13 +513,27 @@ __global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
     }
 }
 
-template <int GEO>
+template <bool AFF, int GEO>
+__global__ __launch_bounds__(256, 2) void conv_wino6_kernel(const ConvArgs a) {
+    conv_wino6_body<AFF, GEO, false>(a);
+}
+
+// the paired form: 8 waves, one workgroup per CU (two waves per SIMD: the register budget of a conv_wino6 wave)
+template <bool AFF, int GEO>
+__global__ __launch_bounds__(512, 2) void conv_wino6p_kernel(const ConvArgs a) {
+    conv_wino6_body<AFF, GEO, true>(a);
+}
+
+template <int GEO, bool PAIR>
 static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
     static DeviceOnce once;
-    int rc = once.run([]() {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6_kernel<false, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, w6_lds_bytes<GEO>());
+    const auto k_plain = PAIR ? conv_wino6p_kernel<false, GEO> : conv_wino6_kernel<false, GEO>;
+    const auto k_aff = PAIR ? conv_wino6p_kernel<true, GEO> : conv_wino6_kernel<true, GEO>;
+    constexpr int lds = w6_lds_bytes<GEO, PAIR>();
+    int rc = once.run([&]() {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6_kernel<true, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, w6_lds_bytes<GEO>());
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_aff), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         return e == hipSuccess ? CMK_OK : fail(CMK_ELAUNCH, "conv_wino6: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     });
     if (rc) return rc;
@@ -501,28 +550,32 @@ static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
             blocks += cdiv(p.N, 2);
         }
     }
-    a.grid_y = cdiv(a.Cout, 32);
+    a.grid_y = cdiv(a.Cout, 32);          // 32-cout tiles (the packed weights' layout); PAIR: the grid walks pairs of them
     a.total_tiles = blocks;
     if (a.ksplit < 1) a.ksplit = 1;
-    const dim3 grid(((blocks + 7) / 8) * 8 * a.grid_y, a.ksplit);
-    if (a.p[0].in_scale)
-        hipLaunchKernelGGL((conv_wino6_kernel<true, GEO>), grid, dim3(256), w6_lds_bytes<GEO>(), st, a);
-    else
-        hipLaunchKernelGGL((conv_wino6_kernel<false, GEO>), grid, dim3(256), w6_lds_bytes<GEO>(), st, a);
-    return check_launch("conv_wino6");
+    const dim3 grid(((blocks + 7) / 8) * 8 * (PAIR ? cdiv(a.grid_y, 2) : a.grid_y), a.ksplit);
+    if constexpr (PAIR) {
+        if (a.p[0].in_scale) hipLaunchKernelGGL((conv_wino6p_kernel<true, GEO>), grid, dim3(512), lds, st, a);
+        else hipLaunchKernelGGL((conv_wino6p_kernel<false, GEO>), grid, dim3(512), lds, st, a);
+    } else {
+        if (a.p[0].in_scale) hipLaunchKernelGGL((conv_wino6_kernel<true, GEO>), grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((conv_wino6_kernel<false, GEO>), grid, dim3(256), lds, st, a);
+    }
+    return check_launch(PAIR ? "conv_wino6p" : "conv_wino6");
 }
 
-// geo 0: 12x40-pixel tiles of one image; geo 1: pairs of whole maps of at most 16 rows x 14 columns (one problem, no fused GN statistics)
-int launch_wino6(ConvArgs& a, int geo, hipStream_t st) {
+// geo 0: 12x40-pixel tiles of one image; geo 1: pairs of whole maps of at most 16 rows x 14 columns (one problem, no fused GN statistics);
+// pair: the paired form (64 couts per workgroup)
+int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st) {
     for (int i = 0; i < a.nprob; ++i)       // the epilogue's stores take a 32-bit byte offset inside the output image (GEO 1: inside a pair of images)
         if ((long)(geo == 0 ? 1 : 2) * a.p[i].H * a.p[i].W * std::max(a.y_cs, a.cout_pad) * 4 >= (1L << 32))
             return fail(CMK_EINVAL, "conv_wino6: an output image of 4 GiB or more%s", "");
     if (a.ksplit > 1 && (a.nprob != 1 || a.gn_ws || !a.ws || ((a.Cin >> 3) % (2 * a.ksplit)) || a.cout_pad < cdiv(a.Cout, 32) * 32))
         return fail(CMK_EINVAL, "conv_wino6: split-K takes one problem, no GroupNorm statistics, a workspace and Cin / 8 chunks %% (2 * splitk) == 0%s", "");
-    if (geo == 0) return launch_wino6_geo<0>(a, st);
+    if (geo == 0) return pair ? launch_wino6_geo<0, true>(a, st) : launch_wino6_geo<0, false>(a, st);
     if (a.nprob != 1 || a.p[0].H > 16 || a.p[0].W > 14 || a.gn_ws)
         return fail(CMK_EINVAL, "conv_wino6: the RoI-pair geometry takes one problem of maps up to 16x14 and produces no GroupNorm statistics%s", "");
-    return launch_wino6_geo<1>(a, st);
+    return pair ? launch_wino6_geo<1, true>(a, st) : launch_wino6_geo<1, false>(a, st);
 }
 
 }  // namespace cmk

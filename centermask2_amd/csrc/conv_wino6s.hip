@@ -30,8 +30,6 @@
 
 namespace cmk {
 
-__device__ f32x2 w6s_buffer_load2(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
-
 template <int GEO> struct W6S {
     using G = W6G<GEO>;
     static constexpr int V_SLOTS = 36 * 64;                  // one V buffer in 16-byte slots: [36 frequencies][channel quad 2][tile 32]
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     f32x2 in_sc = {1.f, 1.f}, in_sh = {0.f, 0.f};
     auto load_D = [&](int chunk) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) d[i] = w6s_buffer_load2(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
+        for (int i = 0; i < 6; ++i) d[i] = w6_buffer_load2(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
         if (AFF) {
             in_sc = *reinterpret_cast<const f32x2*>(P.in_scale + chunk * 8 + aff_off);
             in_sh = *reinterpret_cast<const f32x2*>(P.in_shift + chunk * 8 + aff_off);

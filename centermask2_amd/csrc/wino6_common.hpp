@@ -1,5 +1,5 @@
-// Shared by the two Winograd F(4x4,3x3) kernels (conv_wino6.hip: 32 couts per workgroup, two workgroups per CU; conv_wino6s.hip: 64 couts
-// per workgroup with the frequency image V shared through LDS): tile geometries, the conflict-free W-image slot function and the
+// Shared by the Winograd F(4x4,3x3) kernels (conv_wino6.hip: 32 couts per workgroup, two workgroups per CU, and its paired form, 64 couts
+// per workgroup from one shared W image; conv_wino6s.hip: 64 couts per workgroup with the frequency image V shared through LDS): tile geometries, the conflict-free W-image slot function and the
 // packed-fp32 half transforms.
 #pragma once
 #include "conv_args.hpp"
@@ -11,6 +11,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // bounds-checked 16-byte load: lanes whose byte offset lies outside [0, num_records) of the resource get 0
 __device__ f32x4 w6_buffer_load(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
+__device__ f32x2 w6_buffer_load2(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");      // 8 bytes
 
 // Two tilings of the 32 MFMA rows (a workgroup's 32 tiles of 4x4 outputs):
 //   GEO 0  maps: 3 x 10 tiles of ONE image (12 x 40 pixels: every map width of the model is a multiple of 40); rows 30, 31 carry no tile;

@@ -316,6 +316,8 @@ def _variant_on_menu(tv) -> bool:
     wm, sc, wn, sk = _variant4(tv)
     if wm == 6 and sc == 64:          # F(4x4,3x3), shared-V form (conv_wino6s.hip)
         return wn in (1, 2) and sk == 1
+    if wm == 6:                       # F(4x4,3x3): 32 couts per workgroup (sc 16) or the paired form (sc 32, conv_wino6p_kernel)
+        return sc in (16, 32) and wn in (1, 2) and sk in (1, 2, 4, 8)
     if wm == 10:                      # pointwise GEMM from bf16-split products: only where the caller opted in
         return ALLOW_SPLIT_BF16 and sc == 32 and wn == 4 and sk == 1
     if wm == 12:                      # pointwise GEMM from fp16-split products (two pieces, three products)
@@ -395,8 +397,9 @@ def _tune(descs, n, key) -> None:
         cands += [(5, 16, 2, 1)]                  # fused Winograd F(2x2,3x3)
         cands += [(6, 16, 1, 1), (6, 16, 2, 1)]   # fused Winograd F(4x4,3x3): map tiles / pairs of RoI maps (the library rejects what does not apply)
         cands += [(6, 64, 1, 1), (6, 64, 2, 1)]   # ... its shared-V form: 64 couts per workgroup from one frequency image (conv_wino6s.hip)
+        cands += [(6, 32, 1, 1), (6, 32, 2, 1)]   # ... its paired form: 64 couts per workgroup sharing the halo loads and pass 1
         if small and d0.ksize == 3:
-            cands += [(6, 16, 1, sk) for sk in (2, 4)]      # ... with the chunk loop split over 2 / 4 workgroups (launches of about one round)
+            cands += [(6, sc, 1, sk) for sc in (16, 32) for sk in (2, 4)]      # ... with the chunk loop split over 2 / 4 workgroups (launches of about one round)
     if TUNE_ONLY is not None:
         cands = [_variant4(tv) for tv in TUNE_ONLY(key)]
     times = {}
@@ -932,9 +935,10 @@ def executed_flops(taps: int, stride: int, tv, shapes, cin_pad: int, cout: int) 
     if wm == 5:      # workgroup = 8x16 outputs x 64 couts: 256 MFMAs of 4096 FLOP per 16-channel chunk
         return float(sum(n * cd(h, 8) * cd(w, 16) for n, h, w in shapes) * cd(cout, 64) * (cin_pad // 16) * 256 * 4096)
     if wm == 6:      # workgroup = 12x40 outputs (wn 1) or two whole RoI maps (wn 2) x 32 couts: 144 MFMAs per 8-channel chunk
-        # (the shared-V form, sc 64, runs two such cout tiles per workgroup; a wave group without a tile issues no MFMAs: the same count)
+        # (the shared-V form, sc 64, runs two such cout tiles per workgroup; a wave group without a tile issues no MFMAs: the same count;
+        # the paired form, sc 32, runs the idle half of an odd last pair on the last tile's weights: ceil(cout / 64) pairs)
         wgs = sum(cd(n, 2) for n, h, w in shapes) if wn == 2 else sum(n * cd(h, 12) * cd(w, 40) for n, h, w in shapes)
-        return float(wgs * cd(cout, 32) * (cin_pad // 8) * 144 * 4096)
+        return float(wgs * (2 * cd(cout, 64) if sc == 32 else cd(cout, 32)) * (cin_pad // 8) * 144 * 4096)
     if wm == 11:     # direct 3x3 on split products (conv_sp3.hip), priced in fp32-equivalent FLOPs (x 3 products on the 16-bit pipe): tiles of geometry wn
         th, tw, ct = ((8, 32, 128), (4, 32, 256), (16, 16, 128), (8, 16, 256))[wn]
         if sc == 21 or (wn == 0 and cout <= 64):
@@ -958,7 +962,7 @@ def _kernel_name(taps, stride, tv, aff=False, pool=False, upres=False, cout=None
     if tv[0] == 5:
         return "conv_wino4r_kernel<{}>".format("true" if aff else "false")
     if tv[0] == 6:
-        return "conv_wino6{}_kernel<{}, {}>".format("s" if tv[1] == 64 else "", "true" if aff else "false", 1 if tv[2] == 2 else 0)
+        return "conv_wino6{}_kernel<{}, {}>".format({64: "s", 32: "p"}.get(tv[1], ""), "true" if aff else "false", 1 if tv[2] == 2 else 0)
     wm, sc, wn = tv[:3]
     sk = "true" if (len(tv) > 3 and tv[3] > 1) else "false"
     if wm == 8:

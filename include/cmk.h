@@ -98,7 +98,11 @@ typedef struct {
      * tune_sc == 64 with tune_wm == 6 selects the "shared V" form of the same arithmetic (conv_wino6s.hip; tune_sc 16 or 0 = conv_wino6.hip): one
      * 8-wave workgroup per CU computes 64 output channels of a spatial tile from ONE frequency image of the input kept in LDS, so the halo is
      * fetched and transformed once per 64 channels instead of once per 32; same packed weights, same K order: bit-identical results.  It is
-     * the faster form for launches of about one round of workgroups (the 50x80 maps of stage 4, vovnet.py:90-98); the start-up tuner decides. */
+     * the faster form for launches of about one round of workgroups (the 50x80 maps of stage 4, vovnet.py:90-98); the start-up tuner decides.
+     * tune_sc == 32 with tune_wm == 6 selects the paired form (conv_wino6.hip, conv_wino6p_kernel): one 8-wave workgroup per CU covers 64 couts
+     * as two conv_wino6 cout tiles that share the halo loads, the column transform and the fused input affine; each wave's own work, the packed
+     * weights, the GroupNorm records and split-K (tune_wn 1) are those of tune_sc 16: bit-identical results.  Other tune_sc values than
+     * 0, 16, 32 and 64 are refused. */
     const float* w_wino6;
     /* optional fused average-pool partial sums of the (scaled, shifted, ReLU'd) OUTPUT, for the eSE gate of the OSA aggregation conv
      * (vovnet.py:255-256 avg_pool over the conv the block just produced): only the pointwise GEMM kernel produces them — ask
