@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """CenterMask2 V2-39-eSE-FPN inference throughput on MI355X (BASELINE.json metric: images/sec at 3x800x1280).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the whole hot path (VoVNetV2-39-eSE + FPN -> FCOS head/decode/NMS/top-50 -> CenterROIHeads with
@@ -10,9 +10,12 @@ results left as padded device buffers.  Images shard across ranks (weak scaling,
 model); each step ends with one RCCL all-gather of the fixed-stride per-image results.
 --dump-outputs DIR: rank 0 writes what the last timed step returned (the padded result buffers and the gathered records) as DIR/<name>.npy,
 so that two builds can be compared output for output on the same seeded inputs (dump_outputs below).
-Rank 0 prints ONE JSON line, with
+Rank 0 prints ONE JSON line.  A plain run does only what `value` / `ms_per_step` need: set up, warm up, time the K steps, dump if asked,
+print.  --full adds everything else the bench measures, after the timed steps and never into `value`:
   roofline     — the dominant kernel (the fp32 Winograd F(4x4,3x3) conv on the matrix pipe) measured live with HIP events on the launch stream;
-  cpu_baseline — the oracle (CPU restatement of the reference path, kind "port") timed on this host's cores on a bounded sample.
+  cpu_baseline — the oracle (CPU restatement of the reference path, kind "port") timed on this host's cores on a bounded sample,
+                 and ap_delta against its detections (--no-cpu-baseline drops both);
+  sustained / fed / plugin_api, v99, split_gemm / split_direct3x3 (+ *_v99) — the extra runs (--no-extras drops them).
 """
 import argparse
 import json
@@ -277,7 +280,7 @@ def cpu_baseline_leg(sd, conv_body, budget_s=25.0):
 
 def other_body_leg(body, dev, B, steps=5, warmup=2, keep=None):
     """BASELINE config 5's per-GPU workload (the V-99-eSE body, 8 x 3x800x1280) through the same graph-replay step, a bounded number of
-    steps — an extra key of the default run, so that the driver's bench record carries it; never `value`."""
+    steps — an extra key of a --full run; never `value`."""
     from centermask2_amd import ops, synthetic as S
     saved = dict(ops._TUNED)
     try:
@@ -417,8 +420,11 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="images per GPU per step")
     ap.add_argument("--body", default="V-39-eSE")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sustained (>= 5 s) and host-fed runs that follow the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what `value` does not need: the roofline leg, the CPU baseline and AP delta, "
+                         "and the extra runs (sustained, host-fed, plugin API, V-99-eSE, opt-in split paths)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the AP delta")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra runs that follow the timed region")
     ap.add_argument("--no-autotune", action="store_true", help="use the library's cost model instead of the measured conv tile-variant table")
     ap.add_argument("--tune-file", default=None, help="conv variant table (default: centermask2_amd/tuned/mi355x_<body>_b<B>_800x1280.json)")
     ap.add_argument("--save-tuned", action="store_true", help="write the variant table after start-up tuning")
@@ -514,9 +520,10 @@ def main():
             arrays["records"] = exchange.gathered if world > 1 else rec
             dumped = dump_outputs(args.dump_outputs, arrays)
 
-        # ---- beyond the contract's K steps (extra keys, never `value`): a sustained run and a run fed from the host -------------
+        # ---- --full, beyond the contract's K steps (extra keys, never `value`): a sustained run and a run fed from the host -----
+        extras = args.full and not args.no_extras
         sustained = fed = plugin_api = None
-        if rank == 0 and world == 1 and not args.no_extras:
+        if rank == 0 and world == 1 and extras:
             # (1) >= 5 s of back-to-back steps: the K-step window above is well under a second, too short for the chip to settle
             # into the clock it holds under this load
             n_s, t0s = 0, time.perf_counter()
@@ -592,9 +599,9 @@ def main():
 
         result = None
         if rank == 0:
-            roof = roofline_leg(model, x, sizes)
+            roof = roofline_leg(model, x, sizes) if args.full else None
             cpu, ap = None, None
-            if not (args.no_cpu_baseline or world > 1):
+            if args.full and not (args.no_cpu_baseline or world > 1):
                 cpu, oracle_results = cpu_baseline_leg(sd, args.body)
                 ap = ap_delta_leg(out, [r for r in oracle_results if r[0] < B])
             total_images = world * B * args.steps
@@ -613,18 +620,19 @@ def main():
                            "collective": collective_description(rec.shape[1], world),
                            "candidates_per_image": cand, "detections_per_image": dets,
                            "weights": "seeded random-init, reference state-dict keys"},
-                "roofline": roof,
             }
+            if roof is not None:
+                result["roofline"] = roof
             if dumped is not None:
                 result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
             if sustained is not None:
                 result["sustained"] = sustained
                 result["fed"] = fed
                 result["plugin_api"] = plugin_api
-            if args.body == "V-39-eSE" and world == 1 and not args.no_extras and args.path == "fp32":
+            if args.body == "V-39-eSE" and world == 1 and extras and args.path == "fp32":
                 v99_out = {}
                 result["v99"] = other_body_leg("V-99-eSE", dev, B, keep=v99_out)
-            if world == 1 and not args.no_extras and args.path == "fp32":      # (--path split IS the opt-in path: nothing to report beside it)
+            if world == 1 and extras and args.path == "fp32":      # (--path split IS the opt-in path: nothing to report beside it)
                 result["split_gemm"] = split_gemm_leg(args.body, dev, B, out)
                 result["split_direct3x3"] = split_gemm_leg(args.body, dev, B, out, level=2)
                 if args.body == "V-39-eSE":

@@ -5,7 +5,7 @@ R=$1; shift
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 for r in $(seq 1 $R); do
   for L in "$@"; do
-    CMK_LIB=$(readlink -f $L) python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+    CMK_LIB=$(readlink -f $L) python3 $ROOT/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys
 d=json.load(sys.stdin); pk=d['roofline']['per_kernel']
 print('%-28s %7.2f img/s  ' % ('$(basename $L)', d['value']) + '  '.join('%s %.2f' % (k.replace('conv_','').replace('_kernel',''), v['ms']) for k,v in list(pk.items())[:5]))"

@@ -8,7 +8,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT $ROOT/profiles
 export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-extras $*"
+ARGS="--steps 3 --warmup 1 --full --no-cpu-baseline --no-extras $*"
 cd /tmp
 echo "== kernel trace + stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python3 $ROOT/bench.py $ARGS > $OUT/bench_under_stats.json 2> $OUT/stats.err || tail -3 $OUT/stats.err
 echo "== pmc mfma";  rocprofv3 --kernel-trace --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE -d $OUT/mfma -o m -- python3 $ROOT/bench.py $ARGS > $OUT/bench_under_mfma.json 2> $OUT/mfma.err || tail -3 $OUT/mfma.err
