@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void ese_scale_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// GroupNorm(32, C) + ReLU in place on a dense (N,HW,C) tensor (fcos.py:182-186).
+// GroupNorm(32, C) (+ ReLU) in place on a dense (N,HW,C) tensor (fcos.py:182-186).
 // Stage 1: per (image, pixel chunk) fp64 sum / sum-of-squares per group (fixed order).  Stage 2: normalise.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, double* __restrict__ ws, int HW, int C, int groups,
@@ -361,10 +361,12 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     }
 }
 
+// RELU false: GroupNorm alone, stored unclamped, so a NaN makes its group NaN as in torch (a clamp fmaxf(v, -inf) would give -inf).
+// RELU true: fmaxf(v, 0) maps NaN to 0, as the GroupNorm + ReLU the conv kernels fuse into their input staging does.
+template <bool RELU>
 __global__ __launch_bounds__(256) void gn_apply_kernel(float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       const double* __restrict__ ws, int HW, int C, int groups, int chunks, float eps,
-                                                      int blocks_per_image, float lo) {
-    // lo: 0 = GroupNorm + ReLU, -inf = GroupNorm alone (max(v, -inf) = v)
+                                                      int blocks_per_image) {
     __shared__ float s_mean[64], s_rstd[64];
     const int n = blockIdx.y;
     if (threadIdx.x < groups) {
@@ -392,10 +394,11 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(float* __restrict__ x, co
         f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c);
         f32x4 be = *reinterpret_cast<const f32x4*>(beta + c);
         f32x4 o;
-        o.x = fmaxf((v.x - mean) * rstd * ga.x + be.x, lo);
-        o.y = fmaxf((v.y - mean) * rstd * ga.y + be.y, lo);
-        o.z = fmaxf((v.z - mean) * rstd * ga.z + be.z, lo);
-        o.w = fmaxf((v.w - mean) * rstd * ga.w + be.w, lo);
+        o.x = (v.x - mean) * rstd * ga.x + be.x;
+        o.y = (v.y - mean) * rstd * ga.y + be.y;
+        o.z = (v.z - mean) * rstd * ga.z + be.z;
+        o.w = (v.w - mean) * rstd * ga.w + be.w;
+        if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
         *reinterpret_cast<f32x4*>(xn + i * 4) = o;
     }
 }
@@ -627,20 +630,20 @@ extern "C" int cmk_upsample2x_add_nhwc(float* y, const float* coarse, int N, int
 }
 
 static int groupnorm_inplace(float* x, const float* gamma, const float* beta, double* ws, int ws_chunks, int N, int HW, int C, int groups, float eps,
-                             float lo, void* stream);
+                             bool relu, void* stream);
 
 extern "C" int cmk_groupnorm_relu_nhwc(float* x, const float* gamma, const float* beta, double* ws, int ws_chunks, int N, int HW, int C,
                                        int groups, float eps, void* stream) {
-    return groupnorm_inplace(x, gamma, beta, ws, ws_chunks, N, HW, C, groups, eps, 0.f, stream);
+    return groupnorm_inplace(x, gamma, beta, ws, ws_chunks, N, HW, C, groups, eps, true, stream);
 }
 
 extern "C" int cmk_groupnorm_nhwc(float* x, const float* gamma, const float* beta, double* ws, int ws_chunks, int N, int HW, int C,
                                   int groups, float eps, void* stream) {
-    return groupnorm_inplace(x, gamma, beta, ws, ws_chunks, N, HW, C, groups, eps, -INFINITY, stream);
+    return groupnorm_inplace(x, gamma, beta, ws, ws_chunks, N, HW, C, groups, eps, false, stream);
 }
 
 static int groupnorm_inplace(float* x, const float* gamma, const float* beta, double* ws, int ws_chunks, int N, int HW, int C, int groups, float eps,
-                             float lo, void* stream) {
+                             bool relu, void* stream) {
     if (!x || !gamma || !beta || !ws) return fail(CMK_EINVAL, "groupnorm: null pointer%s", "");
     if ((C & 3) || C > 1024 || groups < 1 || groups > 64 || C % groups || ((C / groups) & 3) || 256 % (C >> 2) || ws_chunks < 1)
         return fail(CMK_EINVAL, "groupnorm: unsupported C/groups%s", "");
@@ -650,8 +653,8 @@ static int groupnorm_inplace(float* x, const float* gamma, const float* beta, do
     long total = (long)HW * (C >> 2);
     int bpi = stream_grid(total);
     if (bpi > 1024) bpi = 1024;
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(bpi, N), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, ws, HW, C, groups, ws_chunks, eps,
-                       bpi, lo);
+    hipLaunchKernelGGL(relu ? gn_apply_kernel<true> : gn_apply_kernel<false>, dim3(bpi, N), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, ws,
+                       HW, C, groups, ws_chunks, eps, bpi);
     return check_launch("gn_apply");
 }
 

@@ -136,16 +136,41 @@ def test_ese_with_identity(dev, c, h, w):
     _close(out.nchw(), ref, 1e-5)
 
 
-@pytest.mark.parametrize("h,w", [(100, 160), (13, 20), (7, 10), (1, 1)])
-def test_groupnorm_relu(dev, h, w):
-    x = _rand((2, 256, h, w), 41, 3.0) + 1.5
-    gamma = torch.rand(256, generator=torch.Generator().manual_seed(42)) + 0.5
-    beta = _rand((256,), 43, 0.1)
-    ref = F.relu(F.group_norm(x, 32, gamma, beta, eps=1e-5))
+GN_CASES = [pytest.param(h, w, 256, 32, True, False, id="{}-{}".format(h, w)) for h, w in [(100, 160), (13, 20), (7, 10), (1, 1)]] + [
+    pytest.param(h, w, c, groups, relu, nan, id="{}-{}-C{}-G{}{}{}".format(h, w, c, groups, "" if relu else "-norelu", "-nan" if nan else ""))
+    for h, w, c, groups, relu, nan in [
+        (100, 160, 256, 32, False, False), (13, 20, 256, 32, False, False), (1, 1, 256, 32, False, False),
+        (13, 20, 256, 8, True, False), (13, 20, 256, 8, False, False), (25, 40, 64, 16, True, False), (25, 40, 64, 16, False, False),
+        (25, 40, 1024, 32, True, False), (25, 40, 1024, 32, False, False),
+        (13, 20, 256, 32, False, True), (7, 10, 64, 16, False, True), (25, 40, 1024, 32, False, True)]]
+
+
+@pytest.mark.parametrize("h,w,c,groups,relu,nan", GN_CASES)
+def test_groupnorm_relu(dev, h, w, c, groups, relu, nan):
+    """GroupNorm (+ ReLU) in place against float64 F.group_norm.  nan: one NaN in image 1, group 3 makes exactly that (image, group)
+    NaN, as in torch's GroupNorm (FPN / mask head NORM "GN" without ReLU); every other value still matches."""
+    from .helpers import close
+    x = _rand((2, c, h, w), 41, 3.0) + 1.5
+    gamma = torch.rand(c, generator=torch.Generator().manual_seed(42)) + 0.5
+    beta = _rand((c,), 43, 0.1)
+    if nan:
+        x[1, 3 * (c // groups) + 1, h // 2, w // 3] = float("nan")
+    ref = F.group_norm(x.double(), groups, gamma.double(), beta.double(), eps=1e-5)
+    if relu:
+        ref = F.relu(ref)
     t = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    ops.groupnorm_relu_(t, gamma.to(dev), beta.to(dev))
+    ops.groupnorm_relu_(t, gamma.to(dev), beta.to(dev), groups, relu=relu)
     torch.cuda.synchronize()
-    _close(t.permute(0, 3, 1, 2), ref, 2e-5)
+    got = t.permute(0, 3, 1, 2).cpu()
+    what = "groupnorm C={} G={}{}".format(c, groups, "" if relu else " no relu")
+    if nan:
+        hole = torch.zeros_like(ref, dtype=torch.bool)
+        hole[1, 3 * (c // groups):4 * (c // groups)] = True
+        assert torch.equal(torch.isnan(ref), hole)
+        assert torch.equal(torch.isnan(got), hole), "a NaN must make exactly its (image, group) NaN"
+        got, ref = got[~hole], ref[~hole]
+    _close(got, ref, 2e-5)
+    close(got, ref, 2e-5, what)
 
 
 def test_conv_multi_level_launch(dev):

@@ -285,6 +285,59 @@ def test_inference_with_pre_and_postprocess(dev, model):
     assert len(raw[0]) > 0
 
 
+def test_mixed_size_batch_matches_oracle(dev, model):
+    """One padded batch of three images of different sizes (zeros outside each image, ops.preprocess_images' convention) through
+    inference_padded + results_from_padded against the oracle on the same tensor and sizes: labels and locations exact, boxes and
+    scores as in the V-99 batch test.  Masks and mask scores on the oracle's boxes (forward_with_given_boxes, each Instances with its
+    own image size), every ROI compared: the ROI level rule reads each image's own area (pooler.py:70-77), and the test asserts that
+    with these sizes the padded area would put some ROIs on another level."""
+    import os
+    from centermask2_amd import synthetic as S
+    from centermask2_amd.structures import Boxes, Instances
+    from oracle import centermask_oracle as O
+    H, W = 640, 768
+    sizes = [(640, 768), (384, 512), (224, 320)]
+    x = S.make_synthetic_images(len(sizes), H, W, seed0=2024)
+    for i, (h, w) in enumerate(sizes):
+        x[i, :, h:, :] = 0
+        x[i, :, :, w:] = 0
+    sd = S.make_synthetic_state_dict("V-39-eSE", 0)
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    refs = O.centermask_inference(sd, x, sizes)
+    moved = 0
+    for (h, w), r in zip(sizes, refs):
+        b = r["boxes"]
+        own = O.assign_boxes_to_levels_by_ratio(b, torch.full((b.shape[0],), float(h * w)))
+        moved += int((own != O.assign_boxes_to_levels_by_ratio(b, torch.full((b.shape[0],), float(H * W)))).sum())
+    assert moved > 0, "the image sizes must change some ROI's level"
+    xd = x.to(dev)
+    with torch.no_grad():
+        out = model.inference_padded(xd, sizes)
+        feats = model.backbone(xd)
+    torch.cuda.synchronize()
+    res = model.results_from_padded(out, sizes)
+    assert len(res) == len(sizes)
+    given = []
+    for i, (inst, want) in enumerate(zip(res, refs)):
+        assert tuple(inst.image_size) == sizes[i]
+        assert len(inst) == want["scores"].shape[0] > 0
+        pg = match_detections(want["scores"], want["classes"], want["locations"], inst.scores, inst.pred_classes, inst.locations).to(dev)
+        assert torch.equal(inst.pred_classes[pg].cpu(), want["classes"]) and torch.equal(inst.locations[pg].cpu(), want["locations"])
+        close(inst.pred_boxes.tensor[pg], want["boxes"], 2e-5, "mixed sizes boxes")
+        close_abs(inst.scores[pg], want["scores"], 1e-4, "mixed sizes scores")
+        g = Instances(sizes[i])
+        g.pred_boxes = Boxes(want["boxes"].to(dev))
+        g.pred_classes = want["classes"].to(dev)
+        g.scores = want["scores"].to(dev)
+        given.append(g)
+    got = model.roi_heads.forward_with_given_boxes(feats, given)
+    torch.cuda.synchronize()
+    for i, (inst, want) in enumerate(zip(got, refs)):
+        assert tuple(inst.image_size) == sizes[i]
+        close_abs(inst.pred_masks, want["pred_masks"], 1e-3, "mixed sizes pred_masks on the oracle's boxes")
+        close_abs(inst.mask_scores, want["mask_scores"], 1e-3, "mixed sizes mask_scores on the oracle's boxes")
+
+
 def test_zero_detections_and_capacity_overflow(dev):
     """Edge cases of the detection tail: no score above 0.05 anywhere (empty Instances with the right field shapes, the ROI
     heads run on zero valid slots), and more candidates than the workspace capacity (re-run with a larger one, never truncated)."""
