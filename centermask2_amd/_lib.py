@@ -55,6 +55,8 @@ SIGNATURES = {
     "cmk_split_packed_halves": (c_int64, [c_int, c_int]),
     "cmk_splith_packed_halves": (c_int64, [c_int, c_int]),
     "cmk_conv_gn_records": (c_int, [c_int, c_int, c_int]),
+    "cmk_deform_conv3x3_nhwc": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "cmk_dwconv3x3_nhwc": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "cmk_stem_conv_nchw3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "cmk_maxpool3x3s2_ceil_nhwc": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

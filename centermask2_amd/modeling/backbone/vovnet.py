@@ -9,6 +9,11 @@ MI355X layout: NHWC fp32.  An OSA block owns ONE buffer of in_ch + 5*stage_ch ch
 max pool, or the previous block's eSE scale) writes channels [0,in_ch), each 3x3 conv writes its own slice and the
 1x1 aggregation reads the whole buffer — torch.cat (vovnet.py:324) never happens.  FrozenBN is folded into the conv
 epilogue (scale/shift), ReLU too.
+
+Deformable stages (MODEL.VOVNET.STAGE_WITH_DCN, vovnet.py:289-298, :432-436): each 3x3 layer of a non-depthwise block of such a
+stage is a DFConv3x3 (vovnet.py:132-201).  Its offset conv runs on the ordinary conv path (bias as the epilogue shift) into a
+scratch NHWC tensor, and the deformable kernel reads that raw output (sigmoid of the mask logits fused) and writes the layer's
+concat slice with the FrozenBN fold and ReLU in its epilogue.
 """
 from collections import OrderedDict
 
@@ -72,6 +77,42 @@ def _dw_layer(src: View, packed, dst: View) -> None:
     ops.conv2d(ops.dwconv3x3(src, w9c, stride=stride), pw, dst, relu=True)
 
 
+class DFConv3x3(nn.Module):
+    """Parameter holders of vovnet.py:132-201: '<module>_<postfix>/conv_offset' (3x3 with bias, Cin -> 18*dg, or 27*dg modulated),
+    '/conv' (d2 DeformConv / ModulatedDeformConv, bias=False: weight only) and '/norm' (FrozenBN)."""
+
+    def __init__(self, in_ch, out_ch, module_name, postfix, with_modulated_dcn=False, deformable_groups=1):
+        super().__init__()
+        if not ops.deform_groups_supported(in_ch, deformable_groups):
+            raise NotImplementedError("MODEL.VOVNET.DEFORMABLE_GROUPS={} with {} input channels: the deformable conv kernel takes "
+                                      "1, 2 or 4 groups of a multiple of 8 channels".format(deformable_groups, in_ch))
+        self.modulated = bool(with_modulated_dcn)
+        self.dg = deformable_groups
+        base = "{}_{}".format(module_name, postfix)
+        off = nn.Conv2d(in_ch, (27 if self.modulated else 18) * deformable_groups, kernel_size=3, padding=1, bias=True)
+        nn.init.zeros_(off.weight)                  # vovnet.py:166-169
+        nn.init.zeros_(off.bias)
+        conv = nn.Conv2d(in_ch, out_ch, kernel_size=3, padding=1, bias=False)
+        nn.init.kaiming_normal_(conv.weight)
+        self.add_module(base + "/conv_offset", off)
+        self.add_module(base + "/conv", conv)
+        self.add_module(base + "/norm", FrozenBatchNorm2d(out_ch))
+        self.base = base
+
+    def pack(self, dev):
+        """-> (PackedConv of the offset conv (scale 1, bias as shift), PackedDeformConv with the FrozenBN folded, dg, modulated)."""
+        off, conv, norm = getattr(self, self.base + "/conv_offset"), getattr(self, self.base + "/conv"), getattr(self, self.base + "/norm")
+        scale, shift = ops.fold_frozen_bn(norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps)
+        return (ops.PackedConv(off.weight, None, off.bias, dev), ops.PackedDeformConv(conv.weight, scale, shift, dev),
+                self.dg, self.modulated)
+
+
+def _dcn_layer(src: View, packed, dst: View) -> None:
+    """offset conv into a scratch tensor, then the deformable conv + BN + ReLU into the destination slice (vovnet.py:185-201)."""
+    pc_off, pd, dg, modulated = packed
+    ops.deform_conv3x3(src, ops.conv_out(src, pc_off).t, pd, dst, dg, modulated, relu=True)
+
+
 def _fold(seq: nn.Module, name: str):
     conv, norm = getattr(seq, name + "/conv"), getattr(seq, name + "/norm")
     scale, shift = ops.fold_frozen_bn(norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps)
@@ -85,10 +126,12 @@ class eSEModule(nn.Module):
 
 
 class _OSA_module(nn.Module):
-    def __init__(self, in_ch, stage_ch, concat_ch, layer_per_block, module_name, identity=False, depthwise=False):
+    def __init__(self, in_ch, stage_ch, concat_ch, layer_per_block, module_name, identity=False, depthwise=False, dcn_config=None):
         super().__init__()
+        dcn_config = dcn_config or {}
         self.identity = identity
         self.depthwise = depthwise
+        self.with_dcn = bool(dcn_config.get("stage_with_dcn", False)) and not depthwise     # vovnet.py:292-298: depthwise wins
         self.isReduced = False
         self.in_ch, self.stage_ch, self.concat_ch, self.module_name = in_ch, stage_ch, concat_ch, module_name
         self.layers = nn.ModuleList()
@@ -99,6 +142,9 @@ class _OSA_module(nn.Module):
         for i in range(layer_per_block):
             if depthwise:
                 seq = nn.Sequential(OrderedDict(_dw_pw_bn(stage_ch, module_name, i)))
+            elif self.with_dcn:
+                seq = DFConv3x3(c, stage_ch, module_name, i, dcn_config.get("with_modulated_dcn", False),
+                                dcn_config.get("deformable_groups", 1))
             else:
                 seq = nn.Sequential(OrderedDict(_conv_bn(c, stage_ch, module_name, i, 3)))
             self.layers.append(seq)
@@ -109,14 +155,15 @@ class _OSA_module(nn.Module):
 
 
 class _OSA_stage(nn.Sequential):
-    def __init__(self, in_ch, stage_ch, concat_ch, block_per_stage, layer_per_block, stage_num, depthwise=False):
+    def __init__(self, in_ch, stage_ch, concat_ch, block_per_stage, layer_per_block, stage_num, depthwise=False, dcn_config=None):
         super().__init__()
         self.stage_num = stage_num
         name = "OSA{}_1".format(stage_num)
-        self.add_module(name, _OSA_module(in_ch, stage_ch, concat_ch, layer_per_block, name, depthwise=depthwise))
+        self.add_module(name, _OSA_module(in_ch, stage_ch, concat_ch, layer_per_block, name, depthwise=depthwise, dcn_config=dcn_config))
         for i in range(block_per_stage - 1):
             name = "OSA{}_{}".format(stage_num, i + 2)
-            self.add_module(name, _OSA_module(concat_ch, stage_ch, concat_ch, layer_per_block, name, identity=True, depthwise=depthwise))
+            self.add_module(name, _OSA_module(concat_ch, stage_ch, concat_ch, layer_per_block, name, identity=True, depthwise=depthwise,
+                                              dcn_config=dcn_config))
 
     def blocks(self):
         return [m for m in self.children() if isinstance(m, _OSA_module)]
@@ -130,8 +177,9 @@ class VoVNet(Backbone):
             raise NotImplementedError("unknown VoVNet body {}".format(body))
         if cfg.MODEL.VOVNET.NORM != "FrozenBN":
             raise NotImplementedError("MODEL.VOVNET.NORM={} (inference path folds FrozenBN)".format(cfg.MODEL.VOVNET.NORM))
-        if any(cfg.MODEL.VOVNET.STAGE_WITH_DCN):
-            raise NotImplementedError("deformable convs are disabled in the reference config and not built")
+        stage_with_dcn = tuple(cfg.MODEL.VOVNET.STAGE_WITH_DCN)
+        if len(stage_with_dcn) != 4:
+            raise ValueError("MODEL.VOVNET.STAGE_WITH_DCN needs one flag per stage (4), got {}".format(stage_with_dcn))
         assert input_ch == 3, "stem kernel reads a 3-channel image"
         spec = _STAGE_SPECS[body]
         stem_ch = spec["stem"]
@@ -155,7 +203,10 @@ class VoVNet(Backbone):
             name = "stage%d" % (i + 2)
             self.stage_names.append(name)
             self.add_module(name, _OSA_stage(in_ch_list[i], spec["stage_conv_ch"][i], spec["stage_out_ch"][i],
-                                             spec["block_per_stage"][i], spec["layer_per_block"], i + 2, depthwise=self.depthwise))
+                                             spec["block_per_stage"][i], spec["layer_per_block"], i + 2, depthwise=self.depthwise,
+                                             dcn_config={"stage_with_dcn": bool(stage_with_dcn[i]),          # vovnet.py:432-436
+                                                         "with_modulated_dcn": bool(cfg.MODEL.VOVNET.WITH_MODULATED_DCN),
+                                                         "deformable_groups": int(cfg.MODEL.VOVNET.DEFORMABLE_GROUPS)}))
             self._out_feature_channels[name] = spec["stage_out_ch"][i]
             if i != 0:
                 stride *= 2
@@ -181,6 +232,9 @@ class VoVNet(Backbone):
                 for i, seq in enumerate(blk.layers):
                     if blk.depthwise:
                         P["{}_{}".format(mn, i)] = _fold_dw(seq, "{}_{}".format(mn, i), dev)
+                        continue
+                    if blk.with_dcn:
+                        P["{}_{}".format(mn, i)] = seq.pack(dev)
                         continue
                     conv, sc, sh = _fold(seq, "{}_{}".format(mn, i))
                     P["{}_{}".format(mn, i)] = ops.PackedConv(conv.weight, sc, sh, dev)
@@ -237,6 +291,8 @@ class VoVNet(Backbone):
                     dst = View(cat, off, blk.stage_ch)
                     if blk.depthwise:
                         _dw_layer(src, P["{}_{}".format(mn, i)], dst)
+                    elif blk.with_dcn:
+                        _dcn_layer(src, P["{}_{}".format(mn, i)], dst)
                     else:
                         ops.conv2d(src, P["{}_{}".format(mn, i)], dst, relu=True)
                     src, off = dst, off + blk.stage_ch

@@ -625,6 +625,41 @@ def linear(x2d: torch.Tensor, pc: PackedConv, relu: bool = False) -> torch.Tenso
     return y.reshape(r, pc.cout)
 
 
+class PackedDeformConv:
+    """Device-resident weights of a deformable 3x3 conv (DFConv3x3 '/conv', vovnet.py:132-201) in the direct conv packing, plus the
+    folded FrozenBN scale/shift.  No Winograd forms: the deformable kernel samples its input per tap."""
+
+    def __init__(self, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], device):
+        self.cout, self.cin, k, k2 = weight.shape
+        assert k == k2 == 3, "deformable conv: 3x3 weights expected, got {}".format(tuple(weight.shape))
+        if self.cin % 16:
+            raise _lib.CmkError("deformable conv: Cin = {} must be a multiple of 16".format(self.cin))
+        self.w = pack_conv_weight(weight).to(device)
+        self.scale = (torch.ones(self.cout) if scale is None else scale.detach().float().cpu()).contiguous().to(device)
+        self.shift = (torch.zeros(self.cout) if shift is None else shift.detach().float().cpu()).contiguous().to(device)
+
+
+def deform_groups_supported(cin: int, dg: int) -> bool:
+    """What cmk_deform_conv3x3_nhwc takes: dg in {1, 2, 4}, Cin % 16 == 0 and (Cin/dg) % 8 == 0."""
+    return dg in (1, 2, 4) and cin % 16 == 0 and (cin // dg) % 8 == 0
+
+
+def deform_conv3x3(x: View, offsets: torch.Tensor, packed: PackedDeformConv, y: View, dg: int, modulated: bool, relu: bool = True) -> None:
+    """d2 DeformConv / ModulatedDeformConv 3x3 (stride 1, pad 1, no bias) + folded FrozenBN (+ ReLU) into the slice y.
+    offsets: the offset conv's raw NHWC output (N,H,W,>= 18*dg | 27*dg) in d2's layout; with `modulated` its channels
+    [18*dg, 27*dg) are mask logits, the sigmoid is applied by the kernel."""
+    lib = _lib.load()
+    _need_gpu(x.t, "deform_conv3x3")
+    _need_gpu(offsets, "deform_conv3x3 offsets")
+    n, h, w = x.nhw
+    assert x.c == packed.cin and y.c == packed.cout, (x.c, y.c, packed.cin, packed.cout)
+    assert y.nhw == (n, h, w) and offsets.dim() == 4 and tuple(offsets.shape[:3]) == (n, h, w) and offsets.is_contiguous()
+    check(lib.cmk_deform_conv3x3_nhwc(x.t.data_ptr(), x.cs, x.co, offsets.data_ptr(), offsets.shape[3], packed.w.data_ptr(),
+                                      packed.scale.data_ptr(), packed.shift.data_ptr(), y.t.data_ptr(), y.cs, y.co, n, h, w,
+                                      packed.cin, packed.cout, dg, int(bool(modulated)), int(bool(relu)), _stream()),
+          "cmk_deform_conv3x3_nhwc")
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # backbone pieces
 # ---------------------------------------------------------------------------------------------------------------

@@ -35,8 +35,11 @@ PIXEL_MEAN = (103.53, 116.28, 123.675)  # deploy_utils.py:81 (BGR), std 1
 
 
 def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_ch: int = 256,
-                       mask_dim: int = 256, pooler_res: int = 14) -> "OrderedDict[str, Tuple[int, ...]]":
-    """Every state-dict entry of the full model in the reference's key names (SURVEY §5 'checkpoint')."""
+                       mask_dim: int = 256, pooler_res: int = 14, stage_with_dcn=(False, False, False, False),
+                       with_modulated_dcn: bool = False, deformable_groups: int = 1) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Every state-dict entry of the full model in the reference's key names (SURVEY §5 'checkpoint').
+    stage_with_dcn / with_modulated_dcn / deformable_groups: MODEL.VOVNET.STAGE_WITH_DCN etc.; the 3x3 layers of a flagged stage are
+    DFConv3x3 (vovnet.py:132-201: '/conv_offset' with bias, '/conv', '/norm'), except in the depth-wise bodies (vovnet.py:292-298)."""
     spec = STAGE_SPECS[conv_body]
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
 
@@ -74,6 +77,11 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
             for i in range(spec["layer_per_block"]):
                 if dw:
                     dw_pw_bn(p + "layers.{}.{}_{}".format(i, mod, i), stage_ch)
+                elif stage_with_dcn[si]:
+                    q = p + "layers.{}.{}_{}".format(i, mod, i)
+                    s[q + "/conv_offset.weight"] = ((27 if with_modulated_dcn else 18) * deformable_groups, cin, 3, 3)
+                    s[q + "/conv_offset.bias"] = ((27 if with_modulated_dcn else 18) * deformable_groups,)
+                    conv_bn(q, cin, stage_ch, 3)
                 else:
                     conv_bn(p + "layers.{}.{}_{}".format(i, mod, i), cin, stage_ch, 3)
                 cin = stage_ch
@@ -150,6 +158,8 @@ def synthetic_tensor(name: str, shape: Iterable[int], seed: int = 0) -> torch.Te
         return randn(0.1)
     if name.endswith("/dw_conv3x3.weight"):
         return randn(1.0 / 3.0)                       # no ReLU between the dw and pw convs: unit gain
+    if "/conv_offset." in name:                       # DFConv3x3 offsets (and mask logits): a few pixels, mostly fractional
+        return randn(1.5 / math.sqrt(shape[1] * 9)) if leaf == "weight" else randn(0.5)
     if ".scales." in name:
         return rand(SYNTH["scale_lo"], SYNTH["scale_hi"])
     if "ese.fc.weight" in name:
@@ -187,14 +197,14 @@ def synthetic_tensor(name: str, shape: Iterable[int], seed: int = 0) -> torch.Te
     return randn(0.1)                                 # remaining biases
 
 
-def make_synthetic_state_dict(conv_body: str = "V-39-eSE", seed: int = 0, shapes=None) -> Dict[str, torch.Tensor]:
+def make_synthetic_state_dict(conv_body: str = "V-39-eSE", seed: int = 0, shapes=None, **dcn) -> Dict[str, torch.Tensor]:
     """Deep bodies (stages of >= 3 OSA blocks: V-57, V-99) get the FrozenBN affine of every identity block's 1x1 aggregation scaled by
-    1/sqrt(blocks in the stage).  Each identity block computes x + eSE(concat(x)); with unit-gain random branches the activations grow
+    1/sqrt(blocks in the stage).  dcn: the DCN keywords of model_param_shapes (default off).  Each identity block computes x + eSE(concat(x)); with unit-gain random branches the activations grow
     geometrically over 9 blocks (V-99: |p3| up to 450) and the fp32 arithmetic of the REFERENCE itself then sits 1.6e-4 (features),
     2e-3 (logits) and 0.9 px (boxes) away from a float64 evaluation (tools/diag_v99.py) — no fp32 implementation could be compared
     with it at 1e-3.  A trained network keeps its residual branches small; so does this scaling (|p3| <= 33, fp32 vs fp64 7e-7)."""
     import re
-    shapes = shapes if shapes is not None else model_param_shapes(conv_body)
+    shapes = shapes if shapes is not None else model_param_shapes(conv_body, **dcn)
     sd = OrderedDict((k, synthetic_tensor(k, v, seed).float().contiguous()) for k, v in shapes.items())
     blocks = STAGE_SPECS[conv_body]["block_per_stage"]
     for k in sd:

@@ -166,6 +166,19 @@ int cmk_conv_gn_tiles(int H, int W);
 /* {sum, sumsq} records per image written through cmk_conv_desc.gn_ws by the Winograd kernel tune_wm (5 or 6) on an H x W map */
 int cmk_conv_gn_records(int H, int W, int tune_wm);
 
+/* ---- deformable 3x3 conv of the VoVNet DCN stages (DFConv3x3.forward vovnet.py:185-201: d2 DeformConv / ModulatedDeformConv,
+ * stride 1, pad 1, dilation 1, groups 1, no bias; wired in at vovnet.py:292-298 when MODEL.VOVNET.STAGE_WITH_DCN is set),
+ * folded FrozenBN and optional ReLU:  y = act( deform_conv(x, offsets[, mask]) * scale[c] + shift[c] ).
+ * x, y are NHWC channel-slice views as above (x: 16-byte aligned, x_cs and x_co multiples of 4); w is packed exactly like
+ * cmk_conv_desc.w for a 3x3 conv (cmk_conv_packed_floats(Cout, Cin, 3) floats).  offsets is the raw (N,H,W,off_cs) output of the
+ * offset conv: for deformable group g and tap k = 3i+j channel g*18 + 2k holds dy and g*18 + 2k + 1 holds dx; with modulated != 0
+ * channel 18*dg + g*9 + k holds the mask LOGIT (the sigmoid is applied here).  Input channel c belongs to group c / (Cin/dg).  The
+ * sample (h-1+i+dy, w-1+j+dx) is bilinear with corners outside the map read as 0, and 0 outside (-1,H) x (-1,W).
+ * Supported: Cin % 16 == 0, dg in {1, 2, 4} with (Cin/dg) % 8 == 0, off_cs >= 18*dg (27*dg modulated). */
+int cmk_deform_conv3x3_nhwc(const float* x, int x_cs, int x_co, const float* offsets, int off_cs, const float* w,
+                            const float* scale, const float* shift, float* y, int y_cs, int y_co, int N, int H, int W,
+                            int Cin, int Cout, int dg, int modulated, int relu, void* stream);
+
 /* ---- depth-wise 3x3, pad 1, stride 1|2, no bias / norm / activation (vovnet.py:110-119 'dw_conv3x3', the dw half of the
  * depth-wise VoVNet bodies V-19-slim-dw-eSE / V-19-dw-eSE vovnet.py:30-48).  x, y are NHWC channel-slice views
  * (pixel stride *_cs, offset *_co floats); w is tap-major [9][C]. ------------------------------------------------ */
