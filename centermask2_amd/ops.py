@@ -943,6 +943,26 @@ def mask_iou_score(iou: torch.Tensor, scores: torch.Tensor, cls: torch.Tensor) -
     return out
 
 
+def keypoint_decode(dec: View, boxes: torch.Tensor, counts: torch.Tensor, num_keypoints: int) -> torch.Tensor:
+    """Keypoint heatmap decode (keypoint_head.py:89-116, 219-224 -> d2 heatmaps_to_keypoints; cmk_keypoint_decode).  dec: the packed
+    score_lowres output, a view (N*topk, S, S, >= 4K) with channel (2py+px)*K + k; boxes (N, topk, 4); counts (N,) int32 on the device.
+    Returns (N, topk, K, 3) = (x, y, score); slots past counts[n] are zeros."""
+    lib = _lib.load()
+    _need_gpu(dec.t, "keypoint_decode")
+    _need_gpu(boxes, "keypoint_decode boxes")
+    n, topk = boxes.shape[0], boxes.shape[1]
+    r, s = dec.t.shape[0], dec.t.shape[1]
+    assert boxes.dim() == 3 and boxes.shape[2] == 4 and boxes.is_contiguous(), tuple(boxes.shape)
+    assert counts.dtype == torch.int32 and counts.is_cuda and counts.numel() == n
+    assert r == n * topk and dec.t.shape[2] == s and dec.c == 4 * num_keypoints, (tuple(dec.t.shape), dec.c, n, topk, num_keypoints)
+    ws_len = lib.cmk_keypoint_decode_ws_len(r, num_keypoints)
+    ws = torch.empty((max(ws_len, 1),), dtype=torch.float32, device=boxes.device)
+    out = torch.empty((n, topk, num_keypoints, 3), dtype=torch.float32, device=boxes.device)
+    check(lib.cmk_keypoint_decode(dec.t.data_ptr(), dec.cs, dec.co, s, num_keypoints, boxes.data_ptr(), counts.data_ptr(), n, topk,
+                                  ws.data_ptr(), ws_len, out.data_ptr(), _stream()), "cmk_keypoint_decode")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # optional per-launch timing (bench.py's roofline leg): events on the launch stream around every conv
 # ---------------------------------------------------------------------------------------------------------------

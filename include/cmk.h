@@ -294,6 +294,23 @@ int cmk_mask_pool_concat(const float* masks /* (R,2S,2S) */, float* y, int y_cs,
 int cmk_mask_iou_score(const float* iou /* (R, classes_stride) */, int iou_cs, const float* scores, const int64_t* cls,
                        float* mask_scores, int R, void* stream);
 
+/* ---- keypoint R-CNN heatmap decode (the tail of KRCNNConvDeconvUpsampleHead.layers keypoint_head.py:219-224 — bilinear x2 — and
+ * keypoint_rcnn_inference keypoint_head.py:89-116 -> detectron2 heatmaps_to_keypoints, source absent: restated from its published
+ * behaviour; reached from CenterROIHeads._forward_keypoint center_heads.py:520-553).  No caller in this library's model path yet.
+ * dec: the score_lowres ConvTranspose2d(k4, s2, p1) output in packed form, an NHWC view (N*topk, S, S, dec_cs) whose channels
+ * [dec_co, dec_co + 4K) hold phase (py, px) of keypoint k at (2py+px)*K + k, i.e. map28[2a+py][2b+px] = dec[a][b][(2py+px)K + k].
+ * Per valid (RoI, keypoint), fp32: map56 = upsample_bilinear2d(map28, x2, align_corners=False) (in LDS); the map resized to
+ * Hc x Wc = ceil(max(y1-y0, 1)) x ceil(max(x1-x0, 1)) by upsample_bicubic2d (align_corners=False, A = -0.75, scale 4S/Hc in fp32,
+ * source not clamped, taps clamped), evaluated on the fly; its FIRST maximum in row-major order (a NaN counts as the largest value,
+ * as in torch.argmax) at (yi, xi); out (N*topk, K, 3) = (x, y, score) with x = (xi + 0.5) * (w / Wc) + x0, y likewise, and
+ * score = 1 / sum(exp(map56 - max)) — the reference's columns [0, 1, 3] of heatmaps_to_keypoints.  Rows past counts[n] are written as
+ * zeros.  Static launch (at most 8 workgroups per (RoI, keypoint), one per 8192 output pixels, then one combine launch), fixed-order
+ * reductions, ties to the lower index: deterministic.  boxes (N, topk, 4) xyxy.  S in [1, 16], K >= 1.
+ * ws: cmk_keypoint_decode_ws_len(N * topk, K) 4-byte words of workspace (0 for bad arguments). */
+int64_t cmk_keypoint_decode_ws_len(int R, int K);
+int cmk_keypoint_decode(const float* dec, int dec_cs, int dec_co, int S, int K, const float* boxes, const int32_t* counts, int N, int topk,
+                        float* ws, int64_t ws_len, float* out, void* stream);
+
 /* ---- input side: (x - mean) / std of one CHW image (uint8 if src_is_u8 else float32) into its zero-padded slot
  * (3,H,W) of the batched NCHW tensor (deploy_utils.py:76-98; d2 preprocess_image + ImageList.from_tensors).  mean3 / std3
  * are HOST arrays of 3 floats. ------------------------------------------------------------------------------------- */
