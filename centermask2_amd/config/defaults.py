@@ -37,12 +37,14 @@ _TABLE = dict(
         ROI_MASK_HEAD=dict(NAME="MaskRCNNConvUpsampleHead", POOLER_RESOLUTION=14, POOLER_SAMPLING_RATIO=0, POOLER_TYPE="ROIAlignV2",
                            NUM_CONV=0, CONV_DIM=256, NORM="", CLS_AGNOSTIC_MASK=False, ASSIGN_CRITERION="area"),
         ROI_MASKIOU_HEAD=dict(NAME="MaskIoUHead", CONV_DIM=256, NUM_CONV=4),
-        ROI_KEYPOINT_HEAD=dict(NAME="KRCNNConvDeconvUpsampleHead", IN_FEATURES=["p2", "p3", "p4", "p5"], ASSIGN_CRITERION="ratio"),
+        ROI_KEYPOINT_HEAD=dict(NAME="KRCNNConvDeconvUpsampleHead", IN_FEATURES=["p2", "p3", "p4", "p5"], ASSIGN_CRITERION="ratio",
+                               POOLER_RESOLUTION=14, POOLER_SAMPLING_RATIO=0, POOLER_TYPE="ROIAlignV2", CONV_DIMS=(512,) * 8, NUM_KEYPOINTS=17,
+                               MIN_KEYPOINTS_PER_IMAGE=1, NORMALIZE_LOSS_BY_VISIBLE_KEYPOINTS=True, LOSS_WEIGHT=1.0),      # last three: (train)
     ),
     INPUT=dict(MIN_SIZE_TRAIN=(800,), MIN_SIZE_TEST=800, MAX_SIZE_TEST=1333, FORMAT="BGR"),
     DATASETS=dict(TRAIN=(), TEST=()),
     DATALOADER=dict(NUM_WORKERS=4),
-    TEST=dict(DETECTIONS_PER_IMAGE=100),
+    TEST=dict(DETECTIONS_PER_IMAGE=100, KEYPOINT_OKS_SIGMAS=[]),
     SOLVER=dict(CHECKPOINT_PERIOD=5000, IMS_PER_BATCH=16, BASE_LR=0.001, STEPS=(30000,), MAX_ITER=40000),
 )
 

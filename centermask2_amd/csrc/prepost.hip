@@ -71,6 +71,29 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const float* __restri
     }
 }
 
+// The same record with the keypoints of a KEYPOINT_ON model in front of the count:
+// [box 4K | score K | mask_score K | loc 2K | cls K | mask K*S*S | keypoints K*Kp*3 (x, y, score) | count].  grid = (blocks, N)
+__global__ __launch_bounds__(256) void pack_records_kp_kernel(const float* __restrict__ box, const float* __restrict__ score, const float* __restrict__ mscore,
+                                                             const float* __restrict__ loc, const int64_t* __restrict__ cls, const float* __restrict__ masks,
+                                                             const float* __restrict__ kps, const int32_t* __restrict__ counts, int K, int SS, int KP3,
+                                                             float* __restrict__ rec, int width) {
+    const int n = blockIdx.y;
+    float* r = rec + (long)n * width;
+    const int o_score = 4 * K, o_ms = 5 * K, o_loc = 6 * K, o_cls = 8 * K, o_mask = 9 * K, o_kp = 9 * K + K * SS, o_cnt = o_kp + K * KP3;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < width; i += gridDim.x * 256) {
+        float v;
+        if (i < o_score) v = box[(long)n * 4 * K + i];
+        else if (i < o_ms) v = score[(long)n * K + (i - o_score)];
+        else if (i < o_loc) v = mscore[(long)n * K + (i - o_ms)];
+        else if (i < o_cls) v = loc[(long)n * 2 * K + (i - o_loc)];
+        else if (i < o_mask) v = (float)cls[(long)n * K + (i - o_cls)];
+        else if (i < o_kp) v = masks[(long)n * K * SS + (i - o_mask)];
+        else if (i < o_cnt) v = kps[(long)n * K * KP3 + (i - o_kp)];
+        else v = (float)counts[n];
+        r[i] = v;
+    }
+}
+
 }  // namespace cmk
 
 using namespace cmk;
@@ -83,6 +106,20 @@ extern "C" int cmk_pack_records(const float* box, const float* score, const floa
     hipLaunchKernelGGL(pack_records_kernel, dim3(cdiv(width, 256 * 4), N), dim3(256), 0, (hipStream_t)stream, box, score, mask_scores, loc, cls, masks,
                        counts, K, mask_hw * mask_hw, rec, width);
     return check_launch("pack_records");
+}
+
+extern "C" int cmk_pack_records_kp(const float* box, const float* score, const float* mask_scores, const float* loc, const int64_t* cls,
+                                   const float* masks, const float* keypoints, const int32_t* counts, int N, int K, int mask_hw, int num_keypoints,
+                                   float* rec, void* stream) {
+    if (!box || !score || !mask_scores || !loc || !cls || !masks || !keypoints || !counts || !rec)
+        return fail(CMK_EINVAL, "pack_records_kp: null pointer%s", "");
+    if (N < 1 || N > 65535 || K < 1 || mask_hw < 1 || num_keypoints < 1) return fail(CMK_EINVAL, "pack_records_kp: bad shape%s", "");
+    const long lwidth = (long)K * (9 + (long)mask_hw * mask_hw + 3L * num_keypoints) + 1;
+    if (lwidth > 0x7fffffffL) return fail(CMK_EINVAL, "pack_records_kp: record too wide%s", "");
+    const int width = (int)lwidth;
+    hipLaunchKernelGGL(pack_records_kp_kernel, dim3(cdiv(width, 256 * 4), N), dim3(256), 0, (hipStream_t)stream, box, score, mask_scores, loc, cls,
+                       masks, keypoints, counts, K, mask_hw * mask_hw, 3 * num_keypoints, rec, width);
+    return check_launch("pack_records_kp");
 }
 
 extern "C" int cmk_preprocess_chw(const void* src, int src_is_u8, float* dst, int h, int w, int H, int W, const float* mean3,

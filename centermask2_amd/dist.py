@@ -10,7 +10,7 @@ from typing import Dict, List, Tuple
 import torch
 import torch.distributed as dist
 
-RECORD_FIELDS = ("box", "score", "mask_scores", "loc", "cls", "pred_masks", "counts")
+RECORD_FIELDS = ("box", "score", "mask_scores", "loc", "cls", "pred_masks", "counts")      # + "pred_keypoints" before "counts" with KEYPOINT_ON
 
 
 def shard_range(num_images: int, rank: int, world: int) -> Tuple[int, int]:
@@ -20,37 +20,53 @@ def shard_range(num_images: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < extra else 0)
 
 
-def record_width(topk: int, mask_hw: int = 28) -> int:
-    return topk * (4 + 1 + 1 + 2 + 1 + mask_hw * mask_hw) + 1
+def record_width(topk: int, mask_hw: int = 28, num_keypoints: int = 0) -> int:
+    return topk * (4 + 1 + 1 + 2 + 1 + mask_hw * mask_hw + 3 * num_keypoints) + 1
 
 
 def pack_records(out: Dict[str, torch.Tensor], rec: torch.Tensor = None) -> torch.Tensor:
-    """(n, record_width) float32: [box 4K | score K | mask_score K | loc 2K | cls K | mask 784K | count].
-    On the GPU this is ONE kernel (cmk_pack_records) writing straight into `rec` — pass the all-gather send buffer to reuse it every
-    step; on CPU tensors (the gloo tests of the exchange logic) the same layout is assembled with torch ops."""
+    """(n, record_width) float32: [box 4K | score K | mask_score K | loc 2K | cls K | mask 784K | count], and with `pred_keypoints` in
+    `out` (a KEYPOINT_ON model) [... | mask 784K | keypoints 3*Kp*K | count].
+    On the GPU this is ONE kernel (cmk_pack_records / cmk_pack_records_kp) writing straight into `rec` — pass the all-gather send buffer
+    to reuse it every step; on CPU tensors (the gloo tests of the exchange logic) the same layout is assembled with torch ops."""
     n, k = out["score"].shape
+    kps = out.get("pred_keypoints")
+    if "pred_masks" not in out or "mask_scores" not in out:
+        raise NotImplementedError("pack_records: the record carries pred_masks and mask_scores; a model without them ({}) has no record "
+                                  "layout".format("keypoint-only, MASK_ON / MASKIOU_ON False" if kps is not None else "MASK_ON / MASKIOU_ON False"))
     hw = out["pred_masks"].shape[-1]
+    nkp = 0 if kps is None else kps.shape[2]
     if not out["score"].is_cuda:
         return torch.cat([out["box"].reshape(n, -1), out["score"], out["mask_scores"], out["loc"].reshape(n, -1),
-                          out["cls"].to(torch.float32), out["pred_masks"].reshape(n, -1),
-                          out["counts"].to(torch.float32).reshape(n, 1)], dim=1).contiguous()
+                          out["cls"].to(torch.float32), out["pred_masks"].reshape(n, -1)] +
+                         ([] if kps is None else [kps.reshape(n, -1)]) +
+                         [out["counts"].to(torch.float32).reshape(n, 1)], dim=1).contiguous()
     from . import _lib, ops
     if rec is None:
-        rec = torch.empty((n, record_width(k, hw)), dtype=torch.float32, device=out["score"].device)
-    assert rec.shape == (n, record_width(k, hw)) and rec.is_contiguous()
+        rec = torch.empty((n, record_width(k, hw, nkp)), dtype=torch.float32, device=out["score"].device)
+    assert rec.shape == (n, record_width(k, hw, nkp)) and rec.is_contiguous()
     ops._need_gpu(out["score"], "pack_records")
+    if kps is not None:
+        ops._need_gpu(kps, "pack_records keypoints")
+        assert kps.shape == (n, k, nkp, 3) and kps.is_contiguous() and nkp >= 1, tuple(kps.shape)
+        _lib.check(_lib.load().cmk_pack_records_kp(out["box"].data_ptr(), out["score"].data_ptr(), out["mask_scores"].data_ptr(),
+                                                   out["loc"].data_ptr(), out["cls"].data_ptr(), out["pred_masks"].data_ptr(), kps.data_ptr(),
+                                                   out["counts"].data_ptr(), n, k, hw, nkp, rec.data_ptr(), ops._stream()), "cmk_pack_records_kp")
+        return rec
     _lib.check(_lib.load().cmk_pack_records(out["box"].data_ptr(), out["score"].data_ptr(), out["mask_scores"].data_ptr(), out["loc"].data_ptr(),
                                             out["cls"].data_ptr(), out["pred_masks"].data_ptr(), out["counts"].data_ptr(), n, k, hw,
                                             rec.data_ptr(), ops._stream()), "cmk_pack_records")
     return rec
 
 
-def unpack_records(rec: torch.Tensor, topk: int, mask_hw: int = 28) -> Dict[str, torch.Tensor]:
+def unpack_records(rec: torch.Tensor, topk: int, mask_hw: int = 28, num_keypoints: int = 0) -> Dict[str, torch.Tensor]:
     n = rec.shape[0]
     k, o = topk, 0
     out = {}
+    assert rec.shape[1] == record_width(topk, mask_hw, num_keypoints), (tuple(rec.shape), topk, mask_hw, num_keypoints)
+    kp_field = (("pred_keypoints", 3 * num_keypoints * k, (n, k, num_keypoints, 3)),) if num_keypoints else ()
     for name, width, shape in (("box", 4 * k, (n, k, 4)), ("score", k, (n, k)), ("mask_scores", k, (n, k)), ("loc", 2 * k, (n, k, 2)),
-                               ("cls", k, (n, k)), ("pred_masks", k * mask_hw * mask_hw, (n, k, 1, mask_hw, mask_hw)), ("counts", 1, (n,))):
+                               ("cls", k, (n, k)), ("pred_masks", k * mask_hw * mask_hw, (n, k, 1, mask_hw, mask_hw))) + kp_field + (("counts", 1, (n,)),):
         out[name] = rec[:, o:o + width].reshape(shape)
         o += width
     out["cls"] = out["cls"].round().to(torch.int64)

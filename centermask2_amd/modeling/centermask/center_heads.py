@@ -1,7 +1,8 @@
-"""CenterROIHeads (mask -> mask-IoU cascade on FCOS boxes) on HIP kernels.
+"""CenterROIHeads (mask -> mask-IoU -> keypoint cascade on FCOS boxes) on HIP kernels.
 
 Mirrors the inference half of centermask2/centermask/modeling/centermask/:
   center_heads.py:295-355,384-517  CenterROIHeads.__init__/forward/forward_with_given_boxes/_forward_mask/_forward_maskiou
+  center_heads.py:358-382,520-553  _init_keypoint_head / _forward_keypoint (MODEL.KEYPOINT_ON)   -> keypoint_head.py + ops.keypoint_decode
   pooler.py:70-118,155-189,290-366  ROIPooler with ROIAlignV2 + "ratio" level assignment  -> ops.roi_align_ratio
   sam.py:12-97                      SpatialAttentionMaskHead                               -> MFMA convs + ops.spatial_attention_
   mask_head.py:174-216              mask_rcnn_inference (class-selected sigmoid)           -> ops.mask_predict
@@ -22,6 +23,7 @@ from ...ops import View
 from ...registry import ROI_HEADS_REGISTRY, ROI_MASK_HEAD_REGISTRY, ROI_MASKIOU_HEAD_REGISTRY
 from ...structures import Boxes, Instances, ShapeSpec
 from ..base import HipModule, NormConv2d, fold_norm, get_norm
+from .keypoint_head import build_keypoint_head
 
 __all__ = ["CenterROIHeads", "ROIPooler", "SpatialAttentionMaskHead", "MaskIoUHead", "build_mask_head", "build_maskiou_head"]
 
@@ -238,9 +240,7 @@ class CenterROIHeads(HipModule):
         self.feature_channels = {k: v.channels for k, v in input_shape.items()}
         self._init_mask_head(cfg)
         self._init_mask_iou_head(cfg)
-        self.keypoint_on = cfg.MODEL.KEYPOINT_ON
-        if self.keypoint_on:
-            raise NotImplementedError("MODEL.KEYPOINT_ON (False in the reference config)")
+        self._init_keypoint_head(cfg)
 
     def _build_packed(self, dev):
         return {}
@@ -265,6 +265,27 @@ class CenterROIHeads(HipModule):
         pooler_resolution = cfg.MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION
         self.maskiou_head = build_maskiou_head(cfg, ShapeSpec(channels=in_channels, width=pooler_resolution, height=pooler_resolution))
 
+    def _init_keypoint_head(self, cfg):        # center_heads.py:358-382
+        self.keypoint_on = cfg.MODEL.KEYPOINT_ON
+        if not self.keypoint_on:
+            return
+        self.kp_in_features = cfg.MODEL.ROI_KEYPOINT_HEAD.IN_FEATURES
+        absent = [f for f in self.kp_in_features if f not in self.feature_strides]
+        if absent:
+            raise ValueError("MODEL.ROI_KEYPOINT_HEAD.IN_FEATURES names {} but the backbone produces {} (the CenterMask FCOS backbones start "
+                             "at p3: set IN_FEATURES to p3..p5, or build a backbone with p2)".format(absent, sorted(self.feature_strides)))
+        if not 1 <= len(self.kp_in_features) <= 4:
+            raise NotImplementedError("MODEL.ROI_KEYPOINT_HEAD.IN_FEATURES: the ROIAlign kernel takes 1 to 4 pyramid levels, got {}".format(
+                len(self.kp_in_features)))
+        pooler_resolution = cfg.MODEL.ROI_KEYPOINT_HEAD.POOLER_RESOLUTION
+        pooler_scales = tuple(1.0 / self.feature_strides[k] for k in self.kp_in_features)
+        in_channels = [self.feature_channels[f] for f in self.kp_in_features][0]
+        self.keypoint_pooler = ROIPooler(output_size=pooler_resolution, scales=pooler_scales,
+                                         sampling_ratio=cfg.MODEL.ROI_KEYPOINT_HEAD.POOLER_SAMPLING_RATIO,
+                                         pooler_type=cfg.MODEL.ROI_KEYPOINT_HEAD.POOLER_TYPE,
+                                         assign_crit=cfg.MODEL.ROI_KEYPOINT_HEAD.ASSIGN_CRITERION)
+        self.keypoint_head = build_keypoint_head(cfg, ShapeSpec(channels=in_channels, width=pooler_resolution, height=pooler_resolution))
+
     def _img_area(self, image_sizes, dev):
         key = (tuple(tuple(hw) for hw in image_sizes), str(dev))
         cache = self.__dict__.setdefault("_img_area_cache", {})
@@ -275,9 +296,10 @@ class CenterROIHeads(HipModule):
     # -- device-only core ----------------------------------------------------------------------------------------
     def forward_padded(self, features, det: dict, image_sizes, want=()) -> dict:
         """det: padded detections (box (N,K,4), score, cls int64, counts int32).  Adds pred_masks (N,K,1,28,28) and
-        mask_scores (N,K).  `want` may name intermediates to keep: 'roi_feat', 'levels', 'mask_logits', 'maskiou'."""
+        mask_scores (N,K), and with KEYPOINT_ON pred_keypoints (N,K,Kp,3).  `want` may name intermediates to keep: 'roi_feat', 'levels',
+        'mask_logits', 'maskiou', 'kp_roi_feat', 'kp_logits'."""
         if not self.mask_on:
-            return det
+            return self._forward_keypoint_padded(features, det, image_sizes, dict(det), want) if self.keypoint_on else det
         feats = [ops.as_view(features[f]) for f in self.in_features]
         dev = feats[0].t.device
         n, k = det["box"].shape[0], det["box"].shape[1]
@@ -312,6 +334,29 @@ class CenterROIHeads(HipModule):
             out["levels"] = levels
         if sel_logits is not None:
             out["mask_logits_selected"] = sel_logits
+        if self.keypoint_on:
+            self._forward_keypoint_padded(features, det, image_sizes, out, want)
+        return out
+
+    def _forward_keypoint_padded(self, features, det: dict, image_sizes, out: dict, want=()) -> dict:
+        """center_heads.py:520-553 + keypoint_head.py:89-116 on the padded buffers: ROIAlign with the keypoint pooler -> conv_fcn* ->
+        packed score_lowres -> decode.  Adds out["pred_keypoints"] (N,K,Kp,3) = (x, y, score), zeros past counts; 'kp_roi_feat' keeps the
+        pooled (N*K,S,S,C) features, 'kp_logits' the packed (N*K,S,S,4Kp) score_lowres output."""
+        feats = [ops.as_view(features[f]) for f in self.kp_in_features]
+        dev = feats[0].t.device
+        n, k = det["box"].shape[0], det["box"].shape[1]
+        pool = self.keypoint_pooler
+        s = pool.output_size
+        roi = torch.empty((n * k, s, s, feats[0].c), dtype=torch.float32, device=dev)
+        ops.roi_align_ratio(feats, pool.scales, det["box"], det["counts"], self._img_area(image_sizes, dev), s, pool.sampling_ratio, roi,
+                            pool.min_level, aligned=pool.aligned, assign_by_area=pool.assign_crit == "area",
+                            canonical_box_size=pool.canonical_box_size, canonical_level=pool.canonical_level)
+        dec = self.keypoint_head.features(View(roi))
+        out["pred_keypoints"] = ops.keypoint_decode(dec, det["box"], det["counts"], self.keypoint_head.num_keypoints)
+        if "kp_roi_feat" in want:
+            out["kp_roi_feat"] = roi
+        if "kp_logits" in want:
+            out["kp_logits"] = dec.t
         return out
 
     # -- reference API ---------------------------------------------------------------------------------------------
@@ -323,8 +368,8 @@ class CenterROIHeads(HipModule):
         return self.forward_with_given_boxes(features, proposals), {}
 
     def forward_with_given_boxes(self, features, instances: List[Instances]) -> List[Instances]:
-        """center_heads.py:413-444: adds pred_masks and mask_scores in place; with zero boxes overall the reference returns
-        without mask_scores (center_heads.py:513-514) — here an empty tensor is attached instead."""
+        """center_heads.py:413-444: adds pred_masks, mask_scores and (KEYPOINT_ON) pred_keypoints in place; with zero boxes overall the
+        reference returns without mask_scores (center_heads.py:513-514) — here an empty tensor is attached instead."""
         assert not self.training
         dev = next(iter(features.values())).device
         batch = lazy_batch_of(instances)
@@ -347,4 +392,6 @@ class CenterROIHeads(HipModule):
                 it.pred_masks = out["pred_masks"][i, :m]
             if self.mask_on and self.maskiou_on:
                 it.mask_scores = out["mask_scores"][i, :m]
+            if self.keypoint_on:
+                it.pred_keypoints = out["pred_keypoints"][i, :m]
         return instances

@@ -239,7 +239,7 @@ class LazyBatch:
 
     def __init__(self, det: dict, image_sizes, fcos):
         self.det, self.image_sizes, self.fcos = det, [tuple(hw) for hw in image_sizes], fcos
-        self.out = None          # ROI-head outputs over the same padded buffers (pred_masks, mask_scores), if any
+        self.out = None          # ROI-head outputs over the same padded buffers (pred_masks, mask_scores, pred_keypoints), if any
         self.redo = None         # det -> ROI-head outputs, for the overflow re-run
         self.counts = None       # per-image detection counts on the host, once resolved
 
@@ -263,7 +263,7 @@ class LazyBatch:
         f = {"pred_boxes": Boxes(det["box"][i, :k]), "scores": det["score"][i, :k], "pred_classes": det["cls"][i, :k],
              "locations": det["loc"][i, :k]}
         if self.out is not None:
-            for name in ("pred_masks", "mask_scores"):
+            for name in ("pred_masks", "mask_scores", "pred_keypoints"):
                 if name in self.out:
                     f[name] = self.out[name][i, :k]
         return f

@@ -68,7 +68,7 @@ class GeneralizedRCNN(nn.Module):
     # -- device-only fast path --------------------------------------------------------------------------------------
     def inference_padded(self, images: torch.Tensor, image_sizes: Sequence[Tuple[int, int]], want=()) -> dict:
         """images: preprocessed (N,3,H,W) on the GPU.  Returns padded device buffers (box, score, cls, loc, counts,
-        pred_masks, mask_scores, cand_counts, overflow); no host synchronisation happens here.  `overflow` (N bools on the device)
+        pred_masks, mask_scores, cand_counts, overflow; pred_keypoints with KEYPOINT_ON); no host synchronisation happens here.  `overflow` (N bools on the device)
         says whether an image had more FCOS candidates than the capacity the buffers were sized for: results_from_padded()
         — the caller's sync point — then re-runs the detection tail and the ROI heads with a larger capacity."""
         features = self.backbone(images)
@@ -87,6 +87,8 @@ class GeneralizedRCNN(nn.Module):
                 it.pred_masks = out["pred_masks"][i, :m]
             if "mask_scores" in out:
                 it.mask_scores = out["mask_scores"][i, :m]
+            if "pred_keypoints" in out:
+                it.pred_keypoints = out["pred_keypoints"][i, :m]
         return insts
 
     # -- reference API ----------------------------------------------------------------------------------------------

@@ -5,6 +5,8 @@
   detector_postprocess_d2  detectron2's detector_postprocess, which GeneralizedRCNN._postprocess calls (tester.py:73): boxes scale by
                            (out_w / image_size[1], out_h / image_size[0]) of the Instances they came with.
 Both then clip to the image, drop empty boxes and paste the 28x28 masks into full-image bitmasks at 0.5 (cmk_paste_masks).
+pred_keypoints (KEYPOINT_ON): detector_postprocess_d2 scales x and y as detectron2 does; the deployment path's detector_postprocess has no
+keypoint handling in the reference (deploy_utils.py:129-158) and hands the field on filtered but unscaled, as that code would.
 """
 import numpy as np
 import torch
@@ -53,6 +55,11 @@ def detector_postprocess_d2(results: Instances, output_height: int, output_width
     results = results[output_boxes.nonempty()]
     if results.has("pred_masks"):
         results.pred_masks = ops.paste_masks(results.pred_masks[:, 0, :, :], results.pred_boxes.tensor, output_height, output_width, mask_threshold)
+    if results.has("pred_keypoints"):         # d2: x and y scale like the boxes, after the non-empty filter, without clipping
+        kp = results.pred_keypoints.clone()
+        kp[:, :, 0] *= scale_x
+        kp[:, :, 1] *= scale_y
+        results.pred_keypoints = kp
     return results
 
 

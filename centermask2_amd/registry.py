@@ -3,7 +3,8 @@
 The reference registers its plugins into detectron2 registries
 (`BACKBONE_REGISTRY` vovnet.py:492,527; `PROPOSAL_GENERATOR_REGISTRY` fcos.py:28;
 `ROI_HEADS_REGISTRY` center_heads.py:295; local `Registry("ROI_MASK_HEAD")`
-mask_head.py:17, `Registry("ROI_MASKIOU_HEAD")` maskiou_head.py:10) and its scripts
+mask_head.py:17, `Registry("ROI_MASKIOU_HEAD")` maskiou_head.py:10, `Registry("ROI_KEYPOINT_HEAD")`
+keypoint_head.py:14) and its scripts
 poke `_obj_map` directly (tester.py:157).  detectron2 is a third-party package whose
 source is not in the reference tree; this is a from-scratch class with the same
 call surface (`register` as decorator or call, `get`, `_obj_map`, `in`, iteration).
@@ -65,6 +66,7 @@ PROPOSAL_GENERATOR_REGISTRY = (
 )
 ROI_HEADS_REGISTRY = _d2_registry("detectron2.modeling.roi_heads.roi_heads", "ROI_HEADS_REGISTRY") or Registry("ROI_HEADS")
 META_ARCH_REGISTRY = _d2_registry("detectron2.modeling.meta_arch.build", "META_ARCH_REGISTRY") or Registry("META_ARCH")
-# local registries in the reference (mask_head.py:17, maskiou_head.py:10)
+# local registries in the reference (mask_head.py:17, maskiou_head.py:10, keypoint_head.py:14)
 ROI_MASK_HEAD_REGISTRY = Registry("ROI_MASK_HEAD")
 ROI_MASKIOU_HEAD_REGISTRY = Registry("ROI_MASKIOU_HEAD")
+ROI_KEYPOINT_HEAD_REGISTRY = Registry("ROI_KEYPOINT_HEAD")

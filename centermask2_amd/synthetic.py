@@ -36,8 +36,11 @@ PIXEL_MEAN = (103.53, 116.28, 123.675)  # deploy_utils.py:81 (BGR), std 1
 
 def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_ch: int = 256,
                        mask_dim: int = 256, pooler_res: int = 14, stage_with_dcn=(False, False, False, False),
-                       with_modulated_dcn: bool = False, deformable_groups: int = 1) -> "OrderedDict[str, Tuple[int, ...]]":
+                       with_modulated_dcn: bool = False, deformable_groups: int = 1, keypoint_on: bool = False,
+                       keypoint_conv_dims=(512,) * 8, num_keypoints: int = 17) -> "OrderedDict[str, Tuple[int, ...]]":
     """Every state-dict entry of the full model in the reference's key names (SURVEY §5 'checkpoint').
+    keypoint_on / keypoint_conv_dims / num_keypoints: MODEL.KEYPOINT_ON and MODEL.ROI_KEYPOINT_HEAD.{CONV_DIMS, NUM_KEYPOINTS}: the
+    `roi_heads.keypoint_head.*` entries of KRCNNConvDeconvUpsampleHead (keypoint_head.py:198-208), after everything else.
     stage_with_dcn / with_modulated_dcn / deformable_groups: MODEL.VOVNET.STAGE_WITH_DCN etc.; the 3x3 layers of a flagged stage are
     DFConv3x3 (vovnet.py:132-201: '/conv_offset' with bias, '/conv', '/norm'), except in the depth-wise bodies (vovnet.py:292-298)."""
     spec = STAGE_SPECS[conv_body]
@@ -129,6 +132,14 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
     s[q + "maskiou_fc2.bias"] = (1024,)
     s[q + "maskiou.weight"] = (num_classes, 1024)
     s[q + "maskiou.bias"] = (num_classes,)
+    if keypoint_on:
+        kp, cin = "roi_heads.keypoint_head.", fpn_ch
+        for i, c in enumerate(keypoint_conv_dims, 1):
+            s[kp + "conv_fcn{}.weight".format(i)] = (c, cin, 3, 3)
+            s[kp + "conv_fcn{}.bias".format(i)] = (c,)
+            cin = c
+        s[kp + "score_lowres.weight"] = (cin, num_keypoints, 4, 4)          # ConvTranspose2d: (Cin, Cout, kh, kw)
+        s[kp + "score_lowres.bias"] = (num_keypoints,)
     return s
 
 
@@ -181,6 +192,8 @@ def synthetic_tensor(name: str, shape: Iterable[int], seed: int = 0) -> torch.Te
         return randn(SYNTH["maskiou_std"])
     if name.endswith("maskiou.bias"):
         return randn(0.05, 0.5)
+    if "score_lowres" in name:                        # ConvTranspose2d k4 s2: every output pixel sums Cin * 4 taps -> logits of order 1
+        return randn(3.0 * math.sqrt(1.0 / (4 * shape[0]))) if leaf == "weight" else randn(0.1)
     if "_tower." in name and len(shape) == 1 and int(name.split(".")[-2]) % 3 == 1:   # GroupNorm affine
         return rand(0.5, 1.5) if leaf == "weight" else randn(0.1)
     if "fpn_lateral" in name and len(shape) == 4:
@@ -199,7 +212,7 @@ def synthetic_tensor(name: str, shape: Iterable[int], seed: int = 0) -> torch.Te
 
 def make_synthetic_state_dict(conv_body: str = "V-39-eSE", seed: int = 0, shapes=None, **dcn) -> Dict[str, torch.Tensor]:
     """Deep bodies (stages of >= 3 OSA blocks: V-57, V-99) get the FrozenBN affine of every identity block's 1x1 aggregation scaled by
-    1/sqrt(blocks in the stage).  dcn: the DCN keywords of model_param_shapes (default off).  Each identity block computes x + eSE(concat(x)); with unit-gain random branches the activations grow
+    1/sqrt(blocks in the stage).  dcn: the DCN and keypoint keywords of model_param_shapes (default off).  Each identity block computes x + eSE(concat(x)); with unit-gain random branches the activations grow
     geometrically over 9 blocks (V-99: |p3| up to 450) and the fp32 arithmetic of the REFERENCE itself then sits 1.6e-4 (features),
     2e-3 (logits) and 0.9 px (boxes) away from a float64 evaluation (tools/diag_v99.py) — no fp32 implementation could be compared
     with it at 1e-3.  A trained network keeps its residual branches small; so does this scaling (|p3| <= 33, fp32 vs fp64 7e-7)."""

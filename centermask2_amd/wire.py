@@ -114,6 +114,11 @@ def instances_to_coco_json(instances, img_id: int) -> List[Dict]:
     classes = instances.pred_classes.tolist()
     rles = [rle_encode(m) for m in instances.pred_masks] if instances.has("pred_masks") else None
     mask_scores = instances.mask_scores.tolist() if instances.has("mask_scores") else None
+    keypoints = None
+    if instances.has("pred_keypoints"):        # coco_evaluation.py:418-425: COCO's keypoint coordinates are pixel indices
+        kp = instances.pred_keypoints.detach().cpu().clone()
+        kp[:, :, :2] -= 0.5
+        keypoints = kp.flatten(1).tolist()      # x, y, score per keypoint
     results = []
     for k in range(n):
         r = {"image_id": img_id, "category_id": classes[k], "bbox": boxes[k], "score": scores[k]}
@@ -121,6 +126,8 @@ def instances_to_coco_json(instances, img_id: int) -> List[Dict]:
             r["segmentation"] = rles[k]
             if mask_scores is not None:
                 r["mask_score"] = mask_scores[k]
+        if keypoints is not None:
+            r["keypoints"] = keypoints[k]
         results.append(r)
     return results
 

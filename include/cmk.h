@@ -296,7 +296,7 @@ int cmk_mask_iou_score(const float* iou /* (R, classes_stride) */, int iou_cs, c
 
 /* ---- keypoint R-CNN heatmap decode (the tail of KRCNNConvDeconvUpsampleHead.layers keypoint_head.py:219-224 — bilinear x2 — and
  * keypoint_rcnn_inference keypoint_head.py:89-116 -> detectron2 heatmaps_to_keypoints, source absent: restated from its published
- * behaviour; reached from CenterROIHeads._forward_keypoint center_heads.py:520-553).  No caller in this library's model path yet.
+ * behaviour; reached from CenterROIHeads._forward_keypoint center_heads.py:520-553).
  * dec: the score_lowres ConvTranspose2d(k4, s2, p1) output in packed form, an NHWC view (N*topk, S, S, dec_cs) whose channels
  * [dec_co, dec_co + 4K) hold phase (py, px) of keypoint k at (2py+px)*K + k, i.e. map28[2a+py][2b+px] = dec[a][b][(2py+px)K + k].
  * Per valid (RoI, keypoint), fp32: map56 = upsample_bilinear2d(map28, x2, align_corners=False) (in LDS); the map resized to
@@ -328,6 +328,13 @@ int cmk_paste_masks(const float* masks, const float* boxes, int R, int S, int H,
  * [box 4K | score K | mask_score K | loc 2K | class K (as float) | mask K*hw*hw | count], K*(9 + hw*hw) + 1 floats. */
 int cmk_pack_records(const float* box, const float* score, const float* mask_scores, const float* loc, const int64_t* cls,
                      const float* masks, const int32_t* counts, int N, int K, int mask_hw, float* rec /* N * width */, void* stream);
+
+/* The same record for a KEYPOINT_ON model, the keypoints in front of the count (cmk_pack_records is unchanged; no new ABI version):
+ * [box 4K | score K | mask_score K | loc 2K | class K | mask K*hw*hw | keypoints K*Kp*3 (x, y, score) | count],
+ * K*(9 + hw*hw + 3*Kp) + 1 floats.  keypoints (N, K, Kp, 3).  N in [1, 65535], K, hw, Kp >= 1. */
+int cmk_pack_records_kp(const float* box, const float* score, const float* mask_scores, const float* loc, const int64_t* cls,
+                        const float* masks, const float* keypoints, const int32_t* counts, int N, int K, int mask_hw, int num_keypoints,
+                        float* rec /* N * width */, void* stream);
 
 #ifdef __cplusplus
 }
