@@ -31,6 +31,7 @@ _TABLE = dict(
         PROPOSAL_GENERATOR=dict(NAME="RPN", MIN_SIZE=0),
         FCOS=_FCOS,
         VOVNET=_VOVNET,
+        RESNETS=dict(OUT_FEATURES=["res4"]),      # detectron2's default; the MobileNetV2 builders name their features through it (mobilenet.py:154)
         ROI_HEADS=dict(NAME="Res5ROIHeads", NUM_CLASSES=80, IN_FEATURES=["res4"], IOU_THRESHOLDS=[0.5], IOU_LABELS=[0, 1],
                        BATCH_SIZE_PER_IMAGE=512, POSITIVE_FRACTION=0.25, SCORE_THRESH_TEST=0.05, NMS_THRESH_TEST=0.5,
                        PROPOSAL_APPEND_GT=True),

@@ -1,2 +1,3 @@
 from .fpn import FPN, LastLevelP6, LastLevelP6P7
 from .vovnet import VoVNet, build_fcos_vovnet_fpn_backbone, build_vovnet_backbone
+from .mobilenet import MobileNetV2, build_fcos_mobilenetv2_fpn_backbone, build_mnv2_backbone, build_mobilenetv2_fpn_backbone

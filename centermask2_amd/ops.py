@@ -697,6 +697,23 @@ def dwconv3x3(x: View, w9c: torch.Tensor, y: Optional[View] = None, stride: int 
     return y
 
 
+def dwconv3x3_bn_act(x: View, w9c: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, y: Optional[View] = None, stride: int = 1,
+                     in_max: float = float("inf"), out_min: float = float("-inf"), out_max: float = float("inf")) -> View:
+    """Depth-wise 3x3 (pad 1) of an inverted-residual block with its surroundings fused (mobilenet.py:38-76):
+    y = clamp(dw3x3(min(x, in_max)) * scale + shift, out_min, out_max).  in_max = 6 finishes the producer's ReLU6 (its conv ran with the
+    plain ReLU epilogue), scale/shift is the folded FrozenBN, [0, 6] the block's own ReLU6; the infinite defaults switch a clamp off."""
+    lib = _lib.load()
+    _need_gpu(x.t, "dwconv3x3_bn_act")
+    n, h, w = x.nhw
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if y is None:
+        y = View(torch.empty((n, ho, wo, x.c), dtype=torch.float32, device=x.t.device))
+    assert y.nhw == (n, ho, wo) and y.c == x.c and tuple(w9c.shape) == (9, x.c) and tuple(scale.shape) == tuple(shift.shape) == (x.c,)
+    check(lib.cmk_dwconv3x3_bn_act_nhwc(x.t.data_ptr(), x.cs, x.co, w9c.data_ptr(), scale.data_ptr(), shift.data_ptr(), in_max, out_min, out_max,
+                                        y.t.data_ptr(), y.cs, y.co, n, h, w, x.c, stride, _stream()), "cmk_dwconv3x3_bn_act_nhwc")
+    return y
+
+
 def maxpool3x3s2_ceil(x: View, y: Optional[View] = None, gate: Optional[torch.Tensor] = None) -> View:
     lib = _lib.load()
     _need_gpu(x.t, "maxpool3x3s2_ceil")

@@ -33,18 +33,64 @@ STAGE_SPECS = {
 
 PIXEL_MEAN = (103.53, 116.28, 123.675)  # deploy_utils.py:81 (BGR), std 1
 
+MOBILENETV2 = "MobileNetV2"             # conv_body name of the CenterMask-Lite body (mobilenet.py:79-130); it has no MODEL.VOVNET entry
+# mobilenet.py:87-96 (t, c, n, s) and the channel counts of res2..res5 (:156-158)
+MNV2_SETTING = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
+MNV2_OUT_CHANNELS = {"res2": 24, "res3": 32, "res4": 96, "res5": 320}
+
+
+def mobilenetv2_param_shapes(prefix: str = "") -> "OrderedDict[str, Tuple[int, ...]]":
+    """State-dict entries of the bare MobileNetV2 body in the reference's key names and order (mobilenet.py:22-27, 38-70)."""
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+
+    def bn(key: str, c: int) -> None:
+        for n in ("weight", "bias", "running_mean", "running_var"):
+            s["{}.{}".format(key, n)] = (c,)
+
+    s[prefix + "features.0.0.weight"] = (32, 3, 3, 3)
+    bn(prefix + "features.0.1", 32)
+    cin, idx = 32, 1
+    for t, c, n, _ in MNV2_SETTING:
+        for _ in range(n):
+            p, hidden, i = prefix + "features.{}.conv.".format(idx), cin * t, 0
+            if t != 1:
+                s[p + "0.weight"] = (hidden, cin, 1, 1)
+                bn(p + "1", hidden)
+                i = 3
+            s[p + "{}.weight".format(i)] = (hidden, 1, 3, 3)
+            bn(p + str(i + 1), hidden)
+            s[p + "{}.weight".format(i + 3)] = (c, hidden, 1, 1)
+            bn(p + str(i + 4), c)
+            cin, idx = c, idx + 1
+    return s
+
 
 def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_ch: int = 256,
                        mask_dim: int = 256, pooler_res: int = 14, stage_with_dcn=(False, False, False, False),
                        with_modulated_dcn: bool = False, deformable_groups: int = 1, keypoint_on: bool = False,
-                       keypoint_conv_dims=(512,) * 8, num_keypoints: int = 17) -> "OrderedDict[str, Tuple[int, ...]]":
+                       keypoint_conv_dims=(512,) * 8, num_keypoints: int = 17, fpn_in=("res3", "res4", "res5"), top_levels: int = 2,
+                       num_tower_convs: int = 4, mask_num_conv: int = 4, maskiou_num_conv: int = 4) -> "OrderedDict[str, Tuple[int, ...]]":
     """Every state-dict entry of the full model in the reference's key names (SURVEY §5 'checkpoint').
     keypoint_on / keypoint_conv_dims / num_keypoints: MODEL.KEYPOINT_ON and MODEL.ROI_KEYPOINT_HEAD.{CONV_DIMS, NUM_KEYPOINTS}: the
     `roi_heads.keypoint_head.*` entries of KRCNNConvDeconvUpsampleHead (keypoint_head.py:198-208), after everything else.
     stage_with_dcn / with_modulated_dcn / deformable_groups: MODEL.VOVNET.STAGE_WITH_DCN etc.; the 3x3 layers of a flagged stage are
-    DFConv3x3 (vovnet.py:132-201: '/conv_offset' with bias, '/conv', '/norm'), except in the depth-wise bodies (vovnet.py:292-298)."""
-    spec = STAGE_SPECS[conv_body]
+    DFConv3x3 (vovnet.py:132-201: '/conv_offset' with bias, '/conv', '/norm'), except in the depth-wise bodies (vovnet.py:292-298).
+    conv_body "MobileNetV2": the CenterMask-Lite body behind build_fcos_mobilenetv2_fpn_backbone, FPN laterals over `fpn_in`
+    (MODEL.FPN.IN_FEATURES) and `top_levels` (MODEL.FCOS.TOP_LEVELS) top convs.  num_tower_convs / mask_num_conv / maskiou_num_conv:
+    MODEL.FCOS.NUM_{CLS,BOX}_CONVS, MODEL.ROI_MASK_HEAD.NUM_CONV, MODEL.ROI_MASKIOU_HEAD.NUM_CONV; fpn_ch and mask_dim the widths."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    if conv_body == MOBILENETV2:
+        s.update(mobilenetv2_param_shapes("backbone.bottom_up."))
+        _fpn_shapes(s, [(int(f[3:]), MNV2_OUT_CHANNELS[f]) for f in fpn_in], fpn_ch, top_levels)
+    else:
+        _vovnet_shapes(s, STAGE_SPECS[conv_body], stage_with_dcn, with_modulated_dcn, deformable_groups)
+        _fpn_shapes(s, list(zip((3, 4, 5), STAGE_SPECS[conv_body]["stage_out_ch"][1:])), fpn_ch, 2)
+    _head_shapes(s, num_classes, fpn_ch, mask_dim, pooler_res, num_tower_convs, mask_num_conv, maskiou_num_conv, keypoint_on,
+                 keypoint_conv_dims, num_keypoints)
+    return s
+
+
+def _vovnet_shapes(s, spec, stage_with_dcn, with_modulated_dcn, deformable_groups) -> None:
 
     def conv_bn(prefix: str, cin: int, cout: int, k: int) -> None:
         s[prefix + "/conv.weight"] = (cout, cin, k, k)
@@ -92,17 +138,24 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
             s[p + "ese.fc.weight"] = (concat_ch, concat_ch, 1, 1)
             s[p + "ese.fc.bias"] = (concat_ch,)
             in_ch = concat_ch
-    for lvl, cin in zip((3, 4, 5), spec["stage_out_ch"][1:]):
+
+
+def _fpn_shapes(s, levels, fpn_ch, top_levels) -> None:
+    for lvl, cin in levels:
         s["backbone.fpn_lateral{}.weight".format(lvl)] = (fpn_ch, cin, 1, 1)
         s["backbone.fpn_lateral{}.bias".format(lvl)] = (fpn_ch,)
         s["backbone.fpn_output{}.weight".format(lvl)] = (fpn_ch, fpn_ch, 3, 3)
         s["backbone.fpn_output{}.bias".format(lvl)] = (fpn_ch,)
-    for n in ("p6", "p7"):
+    for n in ("p6", "p7")[:top_levels]:
         s["backbone.top_block.{}.weight".format(n)] = (fpn_ch, fpn_ch, 3, 3)
         s["backbone.top_block.{}.bias".format(n)] = (fpn_ch,)
+
+
+def _head_shapes(s, num_classes, fpn_ch, mask_dim, pooler_res, num_tower_convs, mask_num_conv, maskiou_num_conv, keypoint_on,
+                 keypoint_conv_dims, num_keypoints) -> None:
     h = "proposal_generator.fcos_head."
     for tower in ("cls_tower", "bbox_tower"):
-        for k in range(4):
+        for k in range(num_tower_convs):
             s[h + "{}.{}.weight".format(tower, 3 * k)] = (fpn_ch, fpn_ch, 3, 3)
             s[h + "{}.{}.bias".format(tower, 3 * k)] = (fpn_ch,)
             s[h + "{}.{}.weight".format(tower, 3 * k + 1)] = (fpn_ch,)
@@ -113,7 +166,7 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
     for l in range(5):
         s[h + "scales.{}.scale".format(l)] = (1,)
     m = "roi_heads.mask_head."
-    for k in range(4):
+    for k in range(mask_num_conv):
         s[m + "mask_fcn{}.weight".format(k + 1)] = (mask_dim, fpn_ch if k == 0 else mask_dim, 3, 3)
         s[m + "mask_fcn{}.bias".format(k + 1)] = (mask_dim,)
     s[m + "spatialAtt.conv.weight"] = (1, 2, 3, 3)
@@ -122,7 +175,7 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
     s[m + "predictor.weight"] = (num_classes, mask_dim, 1, 1)
     s[m + "predictor.bias"] = (num_classes,)
     q = "roi_heads.maskiou_head."
-    for k in range(4):
+    for k in range(maskiou_num_conv):
         s[q + "maskiou_fcn{}.weight".format(k + 1)] = (mask_dim, fpn_ch + 1 if k == 0 else mask_dim, 3, 3)
         s[q + "maskiou_fcn{}.bias".format(k + 1)] = (mask_dim,)
     res = pooler_res // 2
@@ -140,7 +193,6 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
             cin = c
         s[kp + "score_lowres.weight"] = (cin, num_keypoints, 4, 4)          # ConvTranspose2d: (Cin, Cout, kh, kw)
         s[kp + "score_lowres.bias"] = (num_keypoints,)
-    return s
 
 
 # Frozen fixture constants (chosen once with the oracle so that every fixture image yields a few
@@ -161,6 +213,14 @@ def synthetic_tensor(name: str, shape: Iterable[int], seed: int = 0) -> torch.Te
     randn = lambda std=1.0, mean=0.0: torch.randn(shape, generator=g) * std + mean
     rand = lambda lo, hi: torch.rand(shape, generator=g) * (hi - lo) + lo
     leaf = name.rsplit(".", 1)[-1]
+    if "features." in name:                           # the MobileNetV2 body (mobilenet.py): 'features.N[.conv].K.<leaf>', BN and conv told apart by rank
+        if name.endswith("features.0.1.running_var"):
+            return rand(0.5, 1.5) * 400.0             # pixel-scale inputs, as stem_1 below
+        if len(shape) == 1:
+            return rand(0.5, 1.5) if leaf in ("weight", "running_var") else randn(0.1)
+        fan_in = shape[1] * shape[2] * shape[3]
+        project = ".conv." in name and shape[2] == 1 and int(name.split(".")[-2]) in (3, 6)      # the linear 1x1 that ends a block
+        return randn(math.sqrt((1.0 if project else 2.0) / fan_in))                            # a ReLU6 follows every other conv
     if name.endswith("stem_1/norm.running_var"):
         return rand(0.5, 1.5) * 400.0                 # pixel-scale inputs (std ~20) are normalised by the first BN
     if name.endswith("norm.weight") or name.endswith("norm.running_var"):     # '/norm.' and the dw bodies' '/pw_norm.'
@@ -219,6 +279,8 @@ def make_synthetic_state_dict(conv_body: str = "V-39-eSE", seed: int = 0, shapes
     import re
     shapes = shapes if shapes is not None else model_param_shapes(conv_body, **dcn)
     sd = OrderedDict((k, synthetic_tensor(k, v, seed).float().contiguous()) for k, v in shapes.items())
+    if conv_body == MOBILENETV2:
+        return sd
     blocks = STAGE_SPECS[conv_body]["block_per_stage"]
     for k in sd:
         m = re.search(r"stage(\d)\.OSA\d_(\d+)\.concat\..*norm\.(weight|bias)$", k)

@@ -185,6 +185,15 @@ int cmk_deform_conv3x3_nhwc(const float* x, int x_cs, int x_co, const float* off
 int cmk_dwconv3x3_nhwc(const float* x, int x_cs, int x_co, const float* w, float* y, int y_cs, int y_co,
                        int N, int H, int W, int C, int stride, void* stream);
 
+/* ---- depth-wise 3x3 of a MobileNetV2 inverted-residual block (mobilenet.py:38-76) with its surroundings fused:
+ *   y = clamp(dw3x3(min(x, in_max)) * scale[c] + shift[c], out_min, out_max),  pad 1, stride 1|2, C % 4 == 0.
+ * min(x, in_max) finishes the ReLU6 of the producer (the stem / expand 1x1 run with the plain ReLU epilogue); scale/shift is the
+ * folded FrozenBN; the padding is zeros of the clamped input.  in_max = +inf, out_min = -inf, out_max = +inf switch the clamps
+ * off.  A NaN propagates (torch.nn.ReLU6).  x, y: NHWC channel-slice views; w tap-major [9][C]; all pointers 16-byte aligned. */
+int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, const float* w, const float* scale, const float* shift,
+                              float in_max, float out_min, float out_max, float* y, int y_cs, int y_co,
+                              int N, int H, int W, int C, int stride, void* stream);
+
 /* ---- stem_1: 3x3 stride-2 conv on the NCHW 3-channel image (vovnet.py:409), BN-folded, ReLU, NHWC out -------- */
 int cmk_stem_conv_nchw3(const float* x, const float* w /* [27][Cout] */, const float* scale, const float* shift,
                         float* y, int N, int H, int W, int Cout, void* stream);
