@@ -1,2 +1,12 @@
 """centermask2_amd — MI355X-native CenterMask2 inference hot path (VoVNetV2-FPN, FCOS, CenterROIHeads)."""
 __version__ = "0.1.0"
+
+__all__ = ["Predictor", "load_weights", "__version__"]
+
+
+def __getattr__(name):
+    """`from centermask2_amd import Predictor, load_weights` without importing torch for users of the light submodules."""
+    if name in ("Predictor", "load_weights"):
+        from . import predictor
+        return getattr(predictor, name)
+    raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))

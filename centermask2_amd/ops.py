@@ -1076,6 +1076,145 @@ def preprocess_images(images: Sequence[torch.Tensor], mean, std, size_divisibili
     return out, sizes
 
 
+def resize_shortest_edge_shape(h: int, w: int, short: int, max_size: int) -> Tuple[int, int]:
+    """detectron2 ResizeShortestEdge.get_output_shape in Python floats -> (new_h, new_w).  Not postprocess.resize_scale: that one mirrors
+    the floor-based rule of deploy_utils.py:138-142."""
+    size = short * 1.0
+    scale = size / min(h, w)
+    if h < w:
+        newh, neww = size, scale * w
+    else:
+        newh, neww = scale * h, size
+    if max(newh, neww) > max_size:
+        s = max_size * 1.0 / max(newh, neww)
+        newh, neww = newh * s, neww * s
+    return int(newh + 0.5), int(neww + 0.5)
+
+
+RESIZE_BITS = 22          # Pillow's PRECISION_BITS for 8-bit bands (Resample.c: 32 - 8 - 2)
+
+
+def resize_coeffs(in_size: int, out_size: int):
+    """Pillow's bilinear tables for one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc), in float64 on the host — each
+    step a single IEEE operation in the order of the C source, nothing fused: (bounds (out, 2) int32 = first tap and tap count,
+    kk (out, ksize) int32 = weights scaled by 2^22, ksize)."""
+    import math
+    import numpy as np
+    if in_size < 1 or out_size < 1:
+        raise _lib.CmkError("resize_coeffs: sizes must be positive, got {} -> {}".format(in_size, out_size))
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)                 # (int) in C: truncation towards zero
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss))
+    w = np.where(x < xmax[:, None], w, 0.0)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for t in range(ksize):                                                          # the C loop's order of additions
+        ww = ww + w[:, t]
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    kk = (0.5 + w * float(1 << RESIZE_BITS)).astype(np.int64).astype(np.int32)      # bilinear weights are never negative
+    bounds = np.stack([xmin, xmax], axis=1).astype(np.int32)
+    return bounds, kk, ksize
+
+
+_RESIZE_TABLES = {}       # (device index, in, out) -> (bounds, kk, ksize) on that device: a size pair is uploaded once
+
+
+def _resize_tables(in_size: int, out_size: int, dev: torch.device):
+    key = (dev.index, in_size, out_size)
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        bounds, kk, ksize = resize_coeffs(in_size, out_size)
+        assert ksize == _lib.load().cmk_resize_ksize(in_size, out_size)
+        t = _RESIZE_TABLES[key] = (torch.from_numpy(bounds).to(dev), torch.from_numpy(kk).to(dev), ksize)
+    return t
+
+
+def _need_u8_hwc(im, what: str) -> None:
+    if not torch.is_tensor(im) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+        raise _lib.CmkError("{}: need (h,w,3) uint8 tensors, got {}".format(
+            what, "{} {}".format(im.dtype, tuple(im.shape)) if torch.is_tensor(im) else type(im).__name__))
+    if not im.is_cuda:
+        raise _lib.CmkError("{}: tensor is on {}; the resize runs on the GPU (no CPU fallback)".format(what, im.device))
+    _need_current_device(im, what)
+
+
+def _resize_h(lib, im: torch.Tensor, new_w: int, ws: torch.Tensor) -> torch.Tensor:
+    """Horizontal pass of one (h,w,3) image into the workspace ws (>= h*new_w*3 bytes); the image itself where the pass is skipped."""
+    h, w = int(im.shape[0]), int(im.shape[1])
+    if new_w == w:
+        return im
+    bx, kx, ksx = _resize_tables(w, new_w, im.device)
+    check(lib.cmk_resize_h_u8(im.data_ptr(), h, w, new_w, bx.data_ptr(), kx.data_ptr(), ksx, ws.data_ptr(), _stream()), "cmk_resize_h_u8")
+    return ws
+
+
+def _resize_v_args(h: int, new_h: int, dev: torch.device):
+    if new_h == h:
+        return None, None, 0, None
+    by, ky, ksy = _resize_tables(h, new_h, dev)
+    return by.data_ptr(), ky.data_ptr(), ksy, (by, ky)
+
+
+def resize_bilinear_u8(img: torch.Tensor, new_h: int, new_w: int) -> torch.Tensor:
+    """(h,w,3) uint8 on the GPU -> (new_h,new_w,3) uint8, byte for byte PIL.Image.resize((new_w, new_h), BILINEAR) (what detectron2's
+    ResizeTransform.apply_image runs on uint8 images)."""
+    _need_u8_hwc(img, "resize_bilinear_u8")
+    new_h, new_w = int(new_h), int(new_w)
+    if new_h < 1 or new_w < 1:
+        raise _lib.CmkError("resize_bilinear_u8: target size must be positive, got {}x{}".format(new_h, new_w))
+    lib = _lib.load()
+    img = img.contiguous()
+    h = int(img.shape[0])
+    ws = torch.empty((h * new_w * 3 + 3,), dtype=torch.uint8, device=img.device) if new_w != img.shape[1] else None
+    mid = _resize_h(lib, img, new_w, ws)
+    out = torch.empty((new_h, new_w, 3), dtype=torch.uint8, device=img.device)
+    by, ky, ksy, keep = _resize_v_args(h, new_h, img.device)
+    check(lib.cmk_resize_v_u8(mid.data_ptr(), h, new_h, new_w, by, ky, ksy, out.data_ptr(), _stream()), "cmk_resize_v_u8")
+    del keep
+    return out
+
+
+def resize_preprocess_images(images: Sequence[torch.Tensor], short: int, max_size: int, mean, std, size_divisibility: int = 32,
+                             fixed_size: Optional[int] = None, reverse_channels: bool = False):
+    """Raw (h,w,3) uint8 images on the GPU -> (N,3,H,W) float32: ResizeShortestEdge(short, max_size) as detectron2 runs it on uint8
+    images, then (x - mean) / std and zero padding right/bottom — the resize, preprocess_images' normalisation and its padding in two
+    launches per image (one where a pass is skipped).  Returns (batch, sizes) with the RESIZED (new_h, new_w) per image; H, W as in
+    preprocess_images.  reverse_channels: channel 2 of the image becomes plane 0 (BGR in, RGB model)."""
+    if len(images) == 0:
+        raise _lib.CmkError("resize_preprocess_images: no images")
+    for im in images:
+        _need_u8_hwc(im, "resize_preprocess_images")
+    lib = _lib.load()
+    dev = images[0].device
+    sizes = [resize_shortest_edge_shape(int(im.shape[0]), int(im.shape[1]), short, max_size) for im in images]
+    if fixed_size:
+        H = W = int(fixed_size)
+    else:
+        d = max(1, size_divisibility)
+        H = (max(s[0] for s in sizes) + d - 1) // d * d
+        W = (max(s[1] for s in sizes) + d - 1) // d * d
+    out = torch.empty((len(images), 3, H, W), dtype=torch.float32, device=dev)
+    need = max([int(im.shape[0]) * s[1] * 3 for im, s in zip(images, sizes) if s[1] != im.shape[1]] or [0])
+    ws = torch.empty((need + 3,), dtype=torch.uint8, device=dev) if need else None      # one workspace: the launches are ordered on the stream
+    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    for i, im in enumerate(images):
+        im = im.contiguous()
+        h = int(im.shape[0])
+        new_h, new_w = sizes[i]
+        mid = _resize_h(lib, im, new_w, ws)
+        by, ky, ksy, keep = _resize_v_args(h, new_h, dev)
+        check(lib.cmk_resize_v_preprocess(mid.data_ptr(), h, new_h, new_w, by, ky, ksy, out[i].data_ptr(), H, W, m3, s3,
+                                          int(bool(reverse_channels)), _stream()), "cmk_resize_v_preprocess")
+        del keep
+    return out, sizes
+
+
 def paste_masks(masks: torch.Tensor, boxes: torch.Tensor, height: int, width: int, threshold: float = 0.5) -> torch.Tensor:
     """(R,S,S) float masks + (R,4) boxes -> (R,height,width) bool bitmasks."""
     lib = _lib.load()

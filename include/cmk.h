@@ -326,6 +326,27 @@ int cmk_keypoint_decode(const float* dec, int dec_cs, int dec_co, int S, int K, 
 int cmk_preprocess_chw(const void* src, int src_is_u8, float* dst, int h, int w, int H, int W, const float* mean3,
                        const float* std3, void* stream);
 
+/* ---- input side, resize: detectron2's ResizeShortestEdge on a uint8 HWC image with 3 channels, i.e. PIL.Image.resize(BILINEAR), byte
+ * for byte (deploy_utils.py:60-73 does it on the CPU).  Separable: a horizontal pass (h,w,3) -> (h,new_w,3) rounded to uint8, then a
+ * vertical pass; the caller skips the horizontal pass when new_w == w, and a vertical entry given no tables (new_h == h, ksize_y 0) copies.
+ * Tables of one axis in -> out (DEVICE memory, computed on the host in double precision as Pillow's Resample.c does):
+ *   ksize        = cmk_resize_ksize(in, out) = int(ceil(max(in / out, 1))) * 2 + 1   (0 for sizes < 1)
+ *   bounds[2*i]  = first input index of output i,  bounds[2*i+1] = number of taps (<= ksize)
+ *   kk[i*ksize+t] = int(0.5 + weight * 2^22);      out = clamp((2^21 + sum_t in[lo + t] * kk[i*ksize + t]) >> 22, 0, 255)
+ * The kernels clamp the tap ranges to the source, so no table can make them read outside it.
+ *   cmk_resize_h_u8          dst: caller-owned (h,new_w,3) uint8, 4-byte aligned
+ *   cmk_resize_v_u8          src (h,new_w,3) -> dst (new_h,new_w,3) uint8: the pure resize
+ *   cmk_resize_v_preprocess  src (h,new_w,3) -> ((float)v - mean) / std into the image's zero-padded slot (3,H,W) of the NCHW batch, the
+ *                            same bits as cmk_preprocess_chw fed the resized image; reverse_channels swaps channels 0 and 2 first;
+ *                            mean3 / std3 are HOST arrays of 3 floats.  H, new_h <= 65535. ----------------------------------------- */
+int cmk_resize_ksize(int in_size, int out_size);
+int cmk_resize_h_u8(const uint8_t* src, int h, int w, int new_w, const int32_t* bounds_x, const int32_t* kk_x, int ksize_x, uint8_t* dst,
+                    void* stream);
+int cmk_resize_v_u8(const uint8_t* src, int h, int new_h, int new_w, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y, uint8_t* dst,
+                    void* stream);
+int cmk_resize_v_preprocess(const uint8_t* src, int h, int new_h, int new_w, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y,
+                            float* dst, int H, int W, const float* mean3, const float* std3, int reverse_channels, void* stream);
+
 /* ---- output side: paste (R,S,S) soft masks into (R,H,W) uint8 bitmasks at `threshold` (deploy_utils.py:151-156 ->
  * d2 ROIMasks.to_bitmasks: bilinear grid_sample, align_corners=False, zero padding); boxes (R,4) are the rescaled and
  * clipped output boxes. ------------------------------------------------------------------------------------------------ */
