@@ -31,6 +31,7 @@ class ConvDesc(Structure):
         ("pool_ws", c_void_p),
         ("w_split", c_void_p),
         ("w_splith", c_void_p), ("w_splith_scale", c_float),
+        ("splitk_tail", c_int), ("splitk_tail_tiles", c_int),
     ]
 
 
@@ -52,6 +53,9 @@ SIGNATURES = {
     "cmk_conv_cout_pad": (c_int, [c_int]),
     "cmk_wino_packed_floats": (c_int64, [c_int, c_int]),
     "cmk_wino6_packed_floats": (c_int64, [c_int, c_int]),
+    "cmk_wino6_tail_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "cmk_wino6_piece_bounds": (None, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "cmk_conv_tail_ws_floats": (c_int64, [POINTER(ConvDesc)]),
     "cmk_split_packed_halves": (c_int64, [c_int, c_int]),
     "cmk_splith_packed_halves": (c_int64, [c_int, c_int]),
     "cmk_conv_gn_records": (c_int, [c_int, c_int, c_int]),

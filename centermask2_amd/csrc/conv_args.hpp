@@ -34,7 +34,11 @@ struct ConvArgs {
     int cout_pad;
     int total_tiles;   // spatial tiles of all problems (XCD-aware kernels pad the grid to a multiple of 8 tiles)
     int ksplit;        // split-K: blockIdx.y owns an (even) range of the 16-channel chunks and writes raw partial sums to ws
-    float* ws;         // [ksplit][total_pix][cout_pad]
+    float* ws;         // [ksplit][total_pix][cout_pad]; with a tail (below): [tail_ksplit][tail images][H*W][cout_pad]
+    // conv_wino6, RoI-pair geometry: "tail split-K".  The last tail_tiles spatial tiles (pairs of images) are not run as one workgroup per
+    // (tile, cout tile) but as tail_ksplit short ones that share its chunk loop and leave raw partial sums in ws; their blocks follow the
+    // main_blocks blocks of the other tiles in the grid, so they are dispatched last and fill the ragged last round.  0 = off.
+    int tail_tiles, tail_ksplit, main_blocks;
     double* gn_ws;     // Winograd 2-WG form: per (spatial tile, row parity, group) partial {sum, sum of squares} of the outputs (fused GroupNorm statistics)
     int gn_cpg, gn_groups;
     int ga_stride;     // gather form (GA): stride of the 3x3 conv whose taps are walked as 9x more K chunks

@@ -993,6 +993,37 @@ static Variant resolve(const cmk_conv_desc* descs, int n, bool gn) {
     return choose_variant(descs, n, d->ksize * d->ksize, d->stride, cout32);
 }
 
+// Workgroup slots of the current device for the F(4x4) kernels: CUs x 2 (conv_wino6_kernel, two workgroups per CU) or x 1 (the paired
+// form); read once per device.  0 when no device answers (the tail is then off).
+static int wino6_slots(bool pair) {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    int n = __atomic_load_n(&cus[dev], __ATOMIC_ACQUIRE);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+        __atomic_store_n(&cus[dev], n, __ATOMIC_RELEASE);
+    }
+    return pair ? n : 2 * n;
+}
+
+// The tail of a descriptor (cmk.h splitk_tail): spatial tiles and ways, 0 / 0 when it is off or the plan finds no ragged round to fill.
+static void wino6_tail_of(const cmk_conv_desc* d, int& tiles, int& ways) {
+    tiles = ways = 0;
+    if (d->splitk_tail <= 1 || d->tune_wm != 6 || d->tune_wn != 2 || (d->tune_sc != 0 && d->tune_sc != 16 && d->tune_sc != 32)) return;
+    const int st = cdiv(d->N, 2), pairs = d->Cin >> 4;
+    if (d->splitk_tail_tiles > 0) {          // as given (tests; a caller with a plan of its own)
+        tiles = std::min(d->splitk_tail_tiles, st);
+        ways = d->splitk_tail;
+        return;
+    }
+    const bool pair = d->tune_sc == 32;
+    const int ct = cdiv(d->Cout, 32);
+    int pt = 0, pw = 0;
+    cmk_wino6_tail_plan(st, pair ? cdiv(ct, 2) : ct, pairs, wino6_slots(pair), &pt, &pw);
+    if (pt > 0) { tiles = pt; ways = std::min(d->splitk_tail, pw); }
+}
+
 // The launch of the explicit variant d->tune_wm/sc/wn (d: the first descriptor, resolved).  Returns with a.ksplit > 1 when the kernel left
 // split-K partial sums for run() to reduce.
 static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* descs, int n, hipStream_t st) {
@@ -1020,9 +1051,15 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         if (d->tune_sc != 0 && d->tune_sc != 16 && d->tune_sc != 32 && d->tune_sc != 64)
             return fail(CMK_EINVAL, "conv: tune_wm 6 takes tune_sc 16 (32 couts per workgroup), 32 (paired) or 64 (shared V)%s", "");
         const bool pair = d->tune_sc == 32;      // 64 couts per workgroup, halo and pass 1 shared by the two cout tiles
-        if (a.ksplit > 1) {           // F(4x4) with split-K (conv_wino6.hip forms, map tiles): partial sums + the reduce kernel of the direct path
-            if (d->tune_sc == 64 || d->tune_wn != 1 || n != 1) return fail(CMK_EINVAL, "conv: Winograd split-K needs tune_sc 16 or 32, tune_wn 1, one problem%s", "");
-            return launch_wino6(a, 0, pair, st);
+        if (d->splitk_tail > 1) {     // tail split-K (cmk.h splitk_tail): only the ragged last round of a RoI-pair launch is split
+            if (d->tune_sc == 64 || d->tune_wn != 2 || n != 1 || d->gn_ws || a.ksplit > 1)
+                return fail(CMK_EINVAL, "conv: Winograd tail split-K needs tune_sc 16 or 32, tune_wn 2, one problem, no GroupNorm statistics and no splitk beside it%s", "");
+            wino6_tail_of(d, a.tail_tiles, a.tail_ksplit);
+            if (a.tail_tiles > 0 && !d->splitk_ws) return fail(CMK_EINVAL, "conv: Winograd tail split-K needs a workspace (cmk_conv_tail_ws_floats)%s", "");
+        }
+        if (a.ksplit > 1) {           // F(4x4) with split-K (conv_wino6.hip forms): partial sums + the reduce kernel of the direct path
+            if (d->tune_sc == 64 || (d->tune_wn != 1 && d->tune_wn != 2) || n != 1) return fail(CMK_EINVAL, "conv: Winograd split-K needs tune_sc 16 or 32, tune_wn 1 or 2, one problem%s", "");
+            return launch_wino6(a, d->tune_wn == 2 ? 1 : 0, pair, st);       // (tune_wn 2: run as the tail that takes every tile)
         }
         if (d->tune_wn != 1 && d->tune_wn != 2) return fail(CMK_EINVAL, "conv: tune_wm 6 takes tune_wn 1 (12x40 map tiles) or 2 (pairs of RoI maps up to 16x14)%s", "");
         if (d->tune_sc == 64) return launch_wino6s(a, d->tune_wn == 2 ? 1 : 0, st);      // 64 couts per workgroup, shared frequency image
@@ -1111,7 +1148,17 @@ static int run(const cmk_conv_desc* descs, int n, void* stream) {
     dv.tune_wm = v.wm; dv.tune_sc = v.sc; dv.tune_wn = v.wn;
     hipStream_t st = (hipStream_t)stream;
     int rc = dispatch(a, &dv, descs, n, st);
-    if (rc || a.ksplit <= 1) return rc;
+    if (rc) return rc;
+    if (a.ksplit <= 1 && a.tail_ksplit > 1 && a.tail_tiles > 0) {
+        // tail split-K (conv_wino6, RoI pairs): the images of the tail's tiles are one contiguous range of pixels at the end of y; the
+        // slabs hold those images only.  Same fixed-order sum and epilogue as below, over that range.
+        const ConvProblem& p = a.p[0];
+        const long pix0 = (long)2 * (a.total_tiles - a.tail_tiles) * p.Ho * p.Wo, tpix = p.total_pix - pix0;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((tpix * (a.cout_pad >> 2) + 255) / 256, 256L * 32)), dim3(256), 0, st, a.ws, a.tail_ksplit,
+                           tpix, a.cout_pad, p.scale, p.shift, a.Cout, a.relu_upto, (const float*)nullptr, 0, 0, p.y + pix0 * a.y_cs, a.y_cs, a.y_co);
+        return check_launch("splitk_reduce (tail)");
+    }
+    if (a.ksplit <= 1) return rc;
     const ConvProblem& p = a.p[0];      // split-K (one problem): sum the partial sums and apply the epilogue
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((p.total_pix * (a.cout_pad >> 2) + 255) / 256, 256L * 32)), dim3(256), 0, st, a.ws, a.ksplit, p.total_pix,
                        a.cout_pad, p.scale, p.shift, a.Cout, a.relu_upto, a.res_mode == 1 ? a.res : nullptr, a.res_cs, a.res_co, p.y, a.y_cs,
@@ -1161,6 +1208,17 @@ extern "C" int cmk_conv_pool_rows(const cmk_conv_desc* d) {
     if (!d) return 0;
     const int mt = cmk::pointwise_mt(d, 1);
     return (mt && (long)d->H * d->W >= 32 * mt) ? 32 * mt : 0;
+}
+
+// floats of splitk_ws a descriptor's tail needs: ways x the tail's images x H*W x cout_pad; 0 when the tail is off
+extern "C" int64_t cmk_conv_tail_ws_floats(const cmk_conv_desc* d) {
+    if (!d) return 0;
+    int tiles = 0, ways = 0;
+    cmk::wino6_tail_of(d, tiles, ways);
+    if (tiles <= 0 || ways <= 1) return 0;
+    const int st = (d->N + 1) / 2;
+    const int64_t images = d->N - 2 * (int64_t)(st - tiles);
+    return (int64_t)ways * images * d->H * d->W * cmk_conv_cout_pad(d->Cout);
 }
 
 extern "C" int cmk_conv2d_nhwc(const cmk_conv_desc* d, void* stream) {

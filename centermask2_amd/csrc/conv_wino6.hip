@@ -77,12 +77,36 @@ __device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
     const int xq = blockIdx.x >> 3, xcd = blockIdx.x & 7;
     // (the opposite, weight-stationary mapping — XCD k takes the cout tiles == k mod 8 of every spatial tile so that its L2 holds 1/8 of
     // U — was measured 3-4 % slower on the 256 -> 256 layers: every XCD then reads the whole input)
-    const int bx = (xq / gy) * 8 + xcd, by = xq % gy;
+    int bx = (xq / gy) * 8 + xcd, by = xq % gy;
+    // split-K: this workgroup is piece ks of nsplit of its (spatial tile, cout tile): it owns a range of the conv's Cin / 8 chunks and leaves
+    // raw partial sums in a.ws (see the epilogue).  Two forms.  Whole launches (GEO 0, a.ksplit > 1, blockIdx.y): launches of about one round
+    // of workgroups whose life is one long chunk loop (the first conv of a stage-4 / stage-5 OSA block: 512..1024 input channels on 50x80 /
+    // 25x40 maps).  The TAIL of a launch (GEO 1, a.tail_ksplit > 1): the blocks from a.main_blocks on are the pieces of the last
+    // a.tail_tiles spatial tiles — (tile, cout tile, piece) decoded like the main part with the piece between them, so the pieces of a
+    // tile share its XCD — and being the last blocks of the grid they fill the ragged last round of the chip with short workgroups.
+    int ks = blockIdx.y, nsplit = a.ksplit;
+    int tile_end = a.total_tiles;       // GEO 1: the main part's tiles end where the tail's begin
+    int n_ws = 0;                       // GEO 1, tail: the first image of the tail (slab image indices are relative to it)
+    if constexpr (GEO == 1) {
+        ks = 0; nsplit = 1;
+        const int main_tiles = a.total_tiles - a.tail_tiles;
+        tile_end = main_tiles;
+        if ((int)blockIdx.x >= a.main_blocks) {
+            const int tb = (int)blockIdx.x - a.main_blocks;
+            const int tq = tb >> 3, q2 = tq / gy;
+            by = tq % gy;
+            nsplit = a.tail_ksplit;
+            ks = q2 % nsplit;
+            bx = main_tiles + (q2 / nsplit) * 8 + (tb & 7);
+            tile_end = a.total_tiles;
+            n_ws = 2 * main_tiles;
+        }
+    }
     // this wave's 32-cout tile.  PAIR with an odd number of tiles: the upper half of the last pair has none; it reads the weights of the
     // last tile (ct), computes, and stores nothing (co0 >= Cout)
     const int ctile = PAIR ? 2 * by + half : by;
     const int ct = PAIR ? min(ctile, a.grid_y - 1) : by;
-    if (bx >= a.total_tiles) return;
+    if (bx >= tile_end) return;
     int pi = 0;
 #pragma unroll
     for (int i = 1; i < MAXP; ++i)
@@ -101,12 +125,15 @@ __device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
         n = tile * 2; oh0 = 0; ow0 = 0;
     }
     const int co0 = ctile * 32;
-    // split-K (a.ksplit > 1, blockIdx.y): this workgroup owns the 8-channel chunks [c_lo, nchunks) of the conv's Cin / 8 and leaves raw partial
-    // sums in a.ws (see the epilogue); for launches of about one round of workgroups whose life is one long chunk loop (the first conv of a
-    // stage-4 / stage-5 OSA block: 512..1024 input channels on 50x80 / 25x40 maps) two or four workgroups share that loop
-    const int ks = blockIdx.y;
-    const int c_lo = (int)((long)ks * (a.Cin >> 3) / a.ksplit);
-    const int nchunks = (int)((long)(ks + 1) * (a.Cin >> 3) / a.ksplit);       // END of this workgroup's chunk range (even bounds: host)
+    // this workgroup's 8-channel chunks [c_lo, nchunks): nchunks is the END of the range.  GEO 0: even bounds (host); GEO 1: whole chunk pairs
+    // spread as evenly as possible (w6_piece_bounds), the same bounds wherever the host's rule holds
+    int c_lo, nchunks;
+    if constexpr (GEO == 1) {
+        w6_piece_bounds(a.Cin >> 3, nsplit, ks, c_lo, nchunks);
+    } else {
+        c_lo = (int)((long)ks * (a.Cin >> 3) / a.ksplit);
+        nchunks = (int)((long)(ks + 1) * (a.Cin >> 3) / a.ksplit);
+    }
 
     // ---- pass 1 item of this thread ----------------------------------------------------------------------------------------------
     // PAIR: thread = (item tid / 2, channel pair p_h = tid % 2 of its quad); lanes 4k..4k+3 then load the 32 contiguous bytes of a column
@@ -353,8 +380,12 @@ __device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
     asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %0\n\tv_mov_b32 %1, %1" : "+v"(sc), "+v"(sh) : : "memory");
     // split-K: raw partial sums (no scale / shift / ReLU) go to this split's slab of a.ws, laid out [pixel][cout_pad]; the reduce kernel of
     // conv_igemm.hip sums the slabs in a fixed order and applies the epilogue
-    const bool raw = a.ksplit > 1;
-    float* const ybuf = raw ? a.ws + (long)ks * P.total_pix * a.cout_pad : P.y;
+    // raw is a property of the WORKGROUP: with a tail (GEO 1) only its pieces are raw; their slabs hold the tail's images alone, so a piece
+    // stores image n at slab image n - n_ws, and the main part's workgroups store finished values to y as ever
+    const bool raw = nsplit > 1;
+    const long slab_pix = GEO == 1 ? (long)(P.N - n_ws) * H * W : P.total_pix;
+    float* const ybuf = raw ? a.ws + (long)ks * slab_pix * a.cout_pad : P.y;
+    const int n_st = n - n_ws;
     const int ycs = raw ? a.cout_pad : a.y_cs, yco = raw ? 0 : a.y_co;
     if (raw) { sc = 1.f; sh = 0.f; }
     // Everything below works on PAIRS of accumulator registers (r, r+1 = two tiles of the lane) with packed-fp32 instructions, and the
@@ -368,11 +399,11 @@ __device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
     const bool want_stats = a.gn_ws != nullptr;
     f32x2 gs2 = {0.f, 0.f}, gss2 = {0.f, 0.f};
     float gs = 0.f, gss = 0.f;
-    float* yimg = ybuf + (long)n * H * W * ycs + yco + co;
+    float* yimg = ybuf + (long)n_st * H * W * ycs + yco + co;
     // scalar side of the store addresses: image base (the pair's first image for GEO 1) and the byte strides of one pixel / one row
     unsigned long long ybase_s;
     {
-        const unsigned long long yb = (unsigned long long)(ybuf + (long)n * H * W * ycs);
+        const unsigned long long yb = (unsigned long long)(ybuf + (long)n_st * H * W * ycs);
         ybase_s = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(yb >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)yb);
     }
     const unsigned long long px_b = (unsigned long long)ycs * 4u, rowskip_b = (unsigned long long)(W - 3) * ycs * 4u;
@@ -553,7 +584,14 @@ static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
     a.grid_y = cdiv(a.Cout, 32);          // 32-cout tiles (the packed weights' layout); PAIR: the grid walks pairs of them
     a.total_tiles = blocks;
     if (a.ksplit < 1) a.ksplit = 1;
-    const dim3 grid(((blocks + 7) / 8) * 8 * (PAIR ? cdiv(a.grid_y, 2) : a.grid_y), a.ksplit);
+    const int gy = PAIR ? cdiv(a.grid_y, 2) : a.grid_y;
+    if (GEO == 1 && a.ksplit > 1) {       // split-K of a whole RoI launch is the tail that takes every tile
+        a.tail_tiles = blocks; a.tail_ksplit = a.ksplit; a.ksplit = 1;
+    }
+    if (GEO == 0 || a.tail_ksplit <= 1 || a.tail_tiles <= 0) a.tail_tiles = a.tail_ksplit = 0;
+    if (a.tail_tiles > blocks) a.tail_tiles = blocks;
+    a.main_blocks = ((blocks - a.tail_tiles + 7) / 8) * 8 * gy;
+    const dim3 grid(a.main_blocks + ((a.tail_tiles + 7) / 8) * 8 * gy * a.tail_ksplit, a.ksplit);
     if constexpr (PAIR) {
         if (a.p[0].in_scale) hipLaunchKernelGGL((conv_wino6p_kernel<true, GEO>), grid, dim3(512), lds, st, a);
         else hipLaunchKernelGGL((conv_wino6p_kernel<false, GEO>), grid, dim3(512), lds, st, a);
@@ -570,15 +608,47 @@ int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st) {
     for (int i = 0; i < a.nprob; ++i)       // the epilogue's stores take a 32-bit byte offset inside the output image (GEO 1: inside a pair of images)
         if ((long)(geo == 0 ? 1 : 2) * a.p[i].H * a.p[i].W * std::max(a.y_cs, a.cout_pad) * 4 >= (1L << 32))
             return fail(CMK_EINVAL, "conv_wino6: an output image of 4 GiB or more%s", "");
-    if (a.ksplit > 1 && (a.nprob != 1 || a.gn_ws || !a.ws || ((a.Cin >> 3) % (2 * a.ksplit)) || a.cout_pad < cdiv(a.Cout, 32) * 32))
-        return fail(CMK_EINVAL, "conv_wino6: split-K takes one problem, no GroupNorm statistics, a workspace and Cin / 8 chunks %% (2 * splitk) == 0%s", "");
+    // split-K of the map geometry keeps its even-split rule; the RoI-pair geometry gives every piece whole chunk pairs (w6_piece_bounds), so
+    // there any number of ways up to the pair count goes
+    if (a.ksplit > 1 && (a.nprob != 1 || a.gn_ws || !a.ws || (geo == 0 ? ((a.Cin >> 3) % (2 * a.ksplit)) != 0 : a.ksplit > (a.Cin >> 4)) ||
+                         a.cout_pad < cdiv(a.Cout, 32) * 32))
+        return fail(CMK_EINVAL, "conv_wino6: split-K takes one problem, no GroupNorm statistics, a workspace and Cin / 8 chunks %% (2 * splitk) == 0 (RoI pairs: splitk <= Cin / 16)%s", "");
+    if (a.tail_ksplit > 1 && a.tail_tiles > 0) {
+        if (geo != 1) return fail(CMK_EINVAL, "conv_wino6: tail split-K is a feature of the RoI-pair geometry (tune_wn 2)%s", "");
+        if (a.ksplit > 1 || a.nprob != 1 || a.gn_ws || !a.ws || a.tail_ksplit > (a.Cin >> 4) || a.cout_pad < cdiv(a.Cout, 32) * 32)
+            return fail(CMK_EINVAL, "conv_wino6: tail split-K takes one problem, no GroupNorm statistics, no split-K beside it, a workspace and at most Cin / 16 ways%s", "");
+    }
     if (geo == 0) return pair ? launch_wino6_geo<0, true>(a, st) : launch_wino6_geo<0, false>(a, st);
     if (a.nprob != 1 || a.p[0].H > 16 || a.p[0].W > 14 || a.gn_ws)
-        return fail(CMK_EINVAL, "conv_wino6: the RoI-pair geometry takes one problem of maps up to 16x14 and produces no GroupNorm statistics%s", "");
+        return fail(CMK_EINVAL, "conv_wino6: the RoI-pair geometry (with split-K or a split-K tail as without) takes one problem of maps up to 16x14 and produces no GroupNorm statistics%s", "");
     return pair ? launch_wino6_geo<1, true>(a, st) : launch_wino6_geo<1, false>(a, st);
 }
 
 }  // namespace cmk
+
+// Which tiles of a RoI-pair launch to split, and how many ways (cmk.h).  spatial_tiles x cout_tiles workgroups run on `slots` places at a
+// time; the last, ragged round leaves most of the chip idle for a whole workgroup life.  Its whole spatial tiles become the tail.
+extern "C" int cmk_wino6_tail_plan(int spatial_tiles, int cout_tiles, int chunk_pairs, int slots, int* tail_tiles, int* ways) {
+    if (!tail_tiles || !ways) return CMK_EINVAL;
+    *tail_tiles = *ways = 0;
+    if (spatial_tiles <= 0 || cout_tiles <= 0 || slots <= 0) return CMK_OK;
+    const long units = (long)spatial_tiles * cout_tiles;
+    if (units < slots) return CMK_OK;                          // under one round: ordinary split-K territory
+    const int tail_units = (int)(units % slots);
+    if (tail_units == 0 || 2 * tail_units > slots) return CMK_OK;   // no ragged round, or one that fills over half the chip as it is
+    const int tt = tail_units / cout_tiles;                    // whole spatial tiles
+    if (tt == 0) return CMK_OK;
+    for (int w = 8; w >= 2; w >>= 1)
+        if ((long)tt * cout_tiles * w <= slots && w <= chunk_pairs) {
+            *tail_tiles = tt; *ways = w;
+            break;
+        }
+    return CMK_OK;
+}
+
+extern "C" void cmk_wino6_piece_bounds(int chunks, int ways, int piece, int* c_lo, int* c_hi) {
+    cmk::w6_piece_bounds(chunks, ways, piece, *c_lo, *c_hi);
+}
 
 extern "C" int64_t cmk_wino6_packed_floats(int Cout, int Cin) {
     return (int64_t)((Cin + 7) / 8) * ((Cout + 31) / 32) * 36 * 256;

@@ -52,6 +52,15 @@ __device__ __forceinline__ int w6_slot(int q, int r, int a, int col) {
     return q * G::QP + r * G::TP + a * G::AP + (col & 3) * G::CK + (col >> 2);
 }
 
+// Tail split-K (conv_args.hpp): the 8-channel chunks [c_lo, c_hi) of piece `piece` of `ways`.  The chunk loop runs two periods per trip, so
+// a piece gets whole chunk PAIRS, spread as evenly as the count allows (floor bounds: sizes differ by at most one pair; 17 pairs of the
+// 272-channel MaskIoU conv in 8 ways = 2,2,2,2,2,2,2,3).  Where chunks % (2 * ways) == 0 these are the bounds of ordinary split-K.
+__host__ __device__ __forceinline__ void w6_piece_bounds(int chunks, int ways, int piece, int& c_lo, int& c_hi) {
+    const unsigned pairs = (unsigned)chunks >> 1;
+    c_lo = (int)(2u * ((unsigned)piece * pairs / (unsigned)ways));
+    c_hi = piece + 1 == ways ? chunks : (int)(2u * ((unsigned)(piece + 1) * pairs / (unsigned)ways));
+}
+
 // Packed-fp32 arithmetic spelled out.  The transforms are the minimal sequences of v_pk_* instructions (6 per half transform of two
 // channels); left to the compiler the same formulas came out as a mix of scalar FMAs, sign flips (v_xor) and register moves — 5.5 VALU
 // instructions per MFMA instead of 1.5.  One asm block per half transform: the compiler cannot see what kind of instruction wrote the

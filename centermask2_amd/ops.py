@@ -269,7 +269,8 @@ ALLOW_SPLIT_F16 = os.environ.get("CMK_ALLOW_SPLIT_F16", "0") == "1"   # OPT-IN: 
 PACK_WINO6 = True         # pack the F(4x4,3x3) weights too (4x the filter bank per 3x3 stride-1 conv)
 ALLOW_WINOGRAD = True     # let the tuner pick the Winograd F(2x2,3x3) kernel where it is faster (fp32, differs by rounding only)
 TUNE_LOG = []             # (key, {candidate: ms}) per tuned problem
-FORCE_VARIANT = None      # (wm, sc, wn[, splitk]) for every conv launched through the wrappers below (tests, A/B tools); None = table/tuner/default
+TAIL_TILES = 0            # tests: the tile count of a variant's tail split-K (cmk.h splitk_tail_tiles); 0 = the library's plan for the device
+FORCE_VARIANT = None      # (wm, sc, wn[, splitk[, tail ways]]) for every conv launched through the wrappers below (tests, A/B tools); None = table/tuner/default
 TUNE_ONLY = None          # callable(key) -> [(wm, sc, wn, splitk), ...]: the tuner's candidates for that problem instead of the whole menu (targeted
                           # re-tuning: tools/tune_sp3.py); TUNE_REPS timed launches per candidate, best of TUNE_ROUNDS interleaved rounds
 TUNE_REPS, TUNE_ROUNDS = 2, 1
@@ -300,7 +301,7 @@ def _str_to_key(s: str):
 
 
 def save_tuned(path: str) -> None:
-    """Write the measured variant table (problem -> [wm, sc, wn]) as JSON; shipped tables live in centermask2_amd/tuned/."""
+    """Write the measured variant table (problem -> [wm, sc, wn[, splitk[, tail ways]]]) as JSON; shipped tables live in centermask2_amd/tuned/."""
     import json
     with open(path, "w") as f:
         json.dump({_key_to_str(k): list(v) for k, v in sorted(_TUNED.items(), key=lambda kv: _key_to_str(kv[0]))}, f, indent=0)
@@ -311,9 +312,23 @@ def _variant4(tv) -> tuple:
     return tuple(tv[:3]) + (tv[3] if len(tv) > 3 else 1,)
 
 
+def _variant_tail(tv) -> int:
+    """The optional fifth element: the ways of the tail split-K of a RoI-pair Winograd launch (cmk.h splitk_tail); 0 = off."""
+    return int(tv[4]) if len(tv) > 4 and tv[4] > 1 else 0
+
+
+def _variant5(tv) -> tuple:
+    """(wm, sc, wn[, splitk[, tail]]) -> (wm, sc, wn, splitk) or, with a tail, (wm, sc, wn, splitk, tail)."""
+    t = _variant_tail(tv)
+    return _variant4(tv) + ((t,) if t else ())
+
+
 def _variant_on_menu(tv) -> bool:
-    """(wm, sc, wn[, splitk]) names a kernel this library has (older tables may carry variants that were removed since)."""
+    """(wm, sc, wn[, splitk[, tail]]) names a kernel this library has (older tables may carry variants that were removed since)."""
     wm, sc, wn, sk = _variant4(tv)
+    tail = _variant_tail(tv)
+    if tail and not (wm == 6 and sc in (16, 32) and wn == 2 and sk == 1 and tail in (2, 4, 8)):
+        return False                  # the tail is a feature of the RoI-pair F(4x4) forms alone
     if wm == 6 and sc == 64:          # F(4x4,3x3), shared-V form (conv_wino6s.hip)
         return wn in (1, 2) and sk == 1
     if wm == 6:                       # F(4x4,3x3): 32 couts per workgroup (sc 16) or the paired form (sc 32, conv_wino6p_kernel)
@@ -348,12 +363,22 @@ def _out_pixels(d) -> int:
 
 
 def _set_variant(descs, n, tv):
-    """Write a (wm, sc, wn[, splitk]) choice into the descriptors; returns the split-K workspace (keep it alive until the launch)."""
+    """Write a (wm, sc, wn[, splitk[, tail]]) choice into the descriptors; returns the split-K (or tail) workspace (keep it alive until
+    the launch)."""
     wm, sc, wn, sk = _variant4(tv)
+    tail = _variant_tail(tv)
     for i in range(n):
         descs[i].tune_wm, descs[i].tune_sc, descs[i].tune_wn = wm, sc, wn
         descs[i].splitk, descs[i].splitk_ws = 0, None
+        descs[i].splitk_tail, descs[i].splitk_tail_tiles = 0, 0
     ws = None
+    if tail:
+        d = descs[0]
+        d.splitk_tail, d.splitk_tail_tiles = tail, TAIL_TILES
+        floats = _lib.load().cmk_conv_tail_ws_floats(ctypes.byref(d))      # 0: no ragged round on this device, the launch runs without a tail
+        if floats > 0:
+            ws = torch.empty((floats,), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            d.splitk_ws = ws.data_ptr()
     if sk > 1:
         d = descs[0]
         ws = torch.empty((sk * _out_pixels(d) * _lib.load().cmk_conv_cout_pad(d.Cout),), dtype=torch.float32,
@@ -398,10 +423,15 @@ def _tune(descs, n, key) -> None:
         cands += [(6, 16, 1, 1), (6, 16, 2, 1)]   # fused Winograd F(4x4,3x3): map tiles / pairs of RoI maps (the library rejects what does not apply)
         cands += [(6, 64, 1, 1), (6, 64, 2, 1)]   # ... its shared-V form: 64 couts per workgroup from one frequency image (conv_wino6s.hip)
         cands += [(6, 32, 1, 1), (6, 32, 2, 1)]   # ... its paired form: 64 couts per workgroup sharing the halo loads and pass 1
+        if n == 1 and d0.ksize == 3:
+            for sc in (16, 32):                   # ... the RoI-pair forms with the ragged last round of workgroups split over K, where there is one
+                _set_variant(descs, n, (6, sc, 2, 1, 2))
+                if lib.cmk_conv_tail_ws_floats(ctypes.byref(descs[0])) > 0:
+                    cands += [(6, sc, 2, 1, t) for t in (2, 4, 8)]
         if small and d0.ksize == 3:
             cands += [(6, sc, 1, sk) for sc in (16, 32) for sk in (2, 4)]      # ... with the chunk loop split over 2 / 4 workgroups (launches of about one round)
     if TUNE_ONLY is not None:
-        cands = [_variant4(tv) for tv in TUNE_ONLY(key)]
+        cands = [_variant5(tv) for tv in TUNE_ONLY(key)]
     times = {}
     for _ in range(TUNE_ROUNDS):
         for tv in cands:
@@ -421,7 +451,7 @@ def _tune(descs, n, key) -> None:
             del ws
     for tv in cands:                              # first of equals wins, as before
         if times.get(tv, float("inf")) < best_ms:
-            best, best_ms = (tv[:3] if tv[3] == 1 else tv), times[tv]
+            best, best_ms = (tv[:3] if tv[3] == 1 and len(tv) == 4 else tv), times[tv]
     _TUNED[key] = best
     TUNE_LOG.append((key, {tv: times[tv] for tv in cands if tv in times}))
 

@@ -101,7 +101,7 @@ typedef struct {
      * the faster form for launches of about one round of workgroups (the 50x80 maps of stage 4, vovnet.py:90-98); the start-up tuner decides.
      * tune_sc == 32 with tune_wm == 6 selects the paired form (conv_wino6.hip, conv_wino6p_kernel): one 8-wave workgroup per CU covers 64 couts
      * as two conv_wino6 cout tiles that share the halo loads, the column transform and the fused input affine; each wave's own work, the packed
-     * weights, the GroupNorm records and split-K (tune_wn 1) are those of tune_sc 16: bit-identical results.  Other tune_sc values than
+     * weights, the GroupNorm records and split-K are those of tune_sc 16: bit-identical results.  Other tune_sc values than
      * 0, 16, 32 and 64 are refused. */
     const float* w_wino6;
     /* optional fused average-pool partial sums of the (scaled, shifted, ReLU'd) OUTPUT, for the eSE gate of the OSA aggregation conv
@@ -137,6 +137,18 @@ typedef struct {
      * No caller of this repository selects it by default (ops.ALLOW_SPLIT_F16); NULL = not available. */
     const void* w_splith;
     float w_splith_scale;
+    /* OPT-IN, tune_wm 6 with tune_wn 2 and tune_sc 16 | 32: "tail split-K".  A RoI-pair launch whose workgroups do not fill a whole number
+     * of rounds of the chip (400 RoIs x 256 couts: 1600 workgroups on 512 places = 3.125 rounds) spends its last round with most CUs idle
+     * for a whole workgroup life.  splitk_tail >= 2 runs the last splitk_tail_tiles spatial tiles (pairs of images) as splitk_tail short
+     * workgroups per (tile, cout tile), dispatched last in the same launch; each owns whole chunk pairs of Cin / 16, spread as evenly as
+     * possible (splitk_tail <= Cin / 16), and stores raw partial sums to splitk_ws (cmk_conv_tail_ws_floats(d) floats: the tail's images
+     * only); a reduce launch over those images sums them in a fixed order and applies scale / shift / ReLU.  The other images get the bits
+     * of the launch without a tail; the tail's images differ from it by fp32 rounding.  splitk_tail_tiles > 0 is taken as given (capped at
+     * the launch's tiles); 0 asks cmk_wino6_tail_plan with the current device's places (CUs x 2, paired form x 1) — the plan's tiles and at
+     * most its ways, and no tail at all where it finds no ragged round.  One problem, no gn_ws, no splitk beside it; tune_sc 64 refuses it.
+     * splitk_tail 0 | 1 = off: nothing is on unless the caller names it.
+     * (splitk > 1 with tune_wn 2 is the case "every tile is tail": splitk <= Cin / 16 ways, the full-size split-K workspace.) */
+    int splitk_tail; int splitk_tail_tiles;
 } cmk_conv_desc;
 int cmk_conv2d_nhwc(const cmk_conv_desc* d, void* stream);
 int cmk_conv_pool_rows(const cmk_conv_desc* d);
@@ -159,6 +171,15 @@ int64_t cmk_conv_packed_floats(int Cout, int Cin, int ksize);
 int cmk_conv_cout_pad(int Cout);
 int64_t cmk_wino_packed_floats(int Cout, int Cin);
 int64_t cmk_wino6_packed_floats(int Cout, int Cin);
+/* Tail split-K plan (cmk_conv_desc.splitk_tail), pure host arithmetic: spatial_tiles x cout_tiles workgroups on `slots` places at a time.
+ * tail_units = (spatial_tiles * cout_tiles) mod slots, rounded down to whole spatial tiles -> *tail_tiles; *ways = the largest of 8, 4, 2
+ * with tail_tiles * cout_tiles * ways <= slots and ways <= chunk_pairs (Cin / 16).  0 tiles / 0 ways when there is no ragged round, less
+ * than one full round, or a tail of more than half a round.  (200, 8, 16, 512) -> 8 tiles, 8 ways. */
+int cmk_wino6_tail_plan(int spatial_tiles, int cout_tiles, int chunk_pairs, int slots, int* tail_tiles, int* ways);
+/* the 8-channel chunks [*c_lo, *c_hi) of piece `piece` of `ways` of a conv of `chunks` chunks, as the RoI-pair kernel splits them */
+void cmk_wino6_piece_bounds(int chunks, int ways, int piece, int* c_lo, int* c_hi);
+/* floats of splitk_ws that the tail of d needs (reads the current device's CU count when splitk_tail_tiles is 0); 0 = the tail is off */
+int64_t cmk_conv_tail_ws_floats(const cmk_conv_desc* d);
 int64_t cmk_split_packed_halves(int Cout, int Cin);          /* 16-bit elements of cmk_conv_desc.w_split */
 int64_t cmk_splith_packed_halves(int Cout, int Cin);         /* 16-bit elements PER TAP of cmk_conv_desc.w_splith */
 /* spatial tiles per image of the fused-statistics conv (8 x 16 outputs each) */
