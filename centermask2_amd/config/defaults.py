@@ -31,7 +31,10 @@ _TABLE = dict(
         PROPOSAL_GENERATOR=dict(NAME="RPN", MIN_SIZE=0),
         FCOS=_FCOS,
         VOVNET=_VOVNET,
-        RESNETS=dict(OUT_FEATURES=["res4"]),      # detectron2's default; the MobileNetV2 builders name their features through it (mobilenet.py:154)
+        # detectron2's defaults; the MobileNetV2 builders name their features through OUT_FEATURES (mobilenet.py:154)
+        RESNETS=dict(DEPTH=50, OUT_FEATURES=["res4"], NUM_GROUPS=1, NORM="FrozenBN", WIDTH_PER_GROUP=64, STRIDE_IN_1X1=True, RES5_DILATION=1,
+                     RES2_OUT_CHANNELS=256, STEM_OUT_CHANNELS=64, DEFORM_ON_PER_STAGE=[False, False, False, False], DEFORM_MODULATED=False,
+                     DEFORM_NUM_GROUPS=1),
         ROI_HEADS=dict(NAME="Res5ROIHeads", NUM_CLASSES=80, IN_FEATURES=["res4"], IOU_THRESHOLDS=[0.5], IOU_LABELS=[0, 1],
                        BATCH_SIZE_PER_IMAGE=512, POSITIVE_FRACTION=0.25, SCORE_THRESH_TEST=0.05, NMS_THRESH_TEST=0.5,
                        PROPOSAL_APPEND_GT=True),

@@ -706,6 +706,32 @@ def stem_conv(x_nchw: torch.Tensor, w27: torch.Tensor, scale: torch.Tensor, shif
     return View(y)
 
 
+def pack_stem7_weight(weight: torch.Tensor) -> torch.Tensor:
+    """(Cout,3,7,7) weight of d2's BasicStem conv -> [147][Cout] with k = (kh*7 + kw)*3 + ci (what cmk_stem7x7_bn_relu_maxpool_nchw3 reads)."""
+    cout = weight.shape[0]
+    assert tuple(weight.shape) == (cout, 3, 7, 7), "the ResNet stem weight must be (Cout,3,7,7)"
+    return weight.detach().float().cpu().permute(2, 3, 1, 0).reshape(147, cout).contiguous()
+
+
+def stem7x7_bn_relu_maxpool(x_nchw: torch.Tensor, w147: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, y: Optional[View] = None) -> View:
+    """d2 BasicStem in one launch: max_pool2d(relu(conv7x7 s2 p3 (x) * scale + shift), 3, 2, 1) on the NCHW 3-channel image -> NHWC view
+    (csrc/stem7_pool.hip; the conv map is never written to memory)."""
+    lib = _lib.load()
+    _need_gpu(x_nchw, "stem7x7_bn_relu_maxpool")
+    x_nchw = x_nchw.contiguous()
+    n, c, h, w = x_nchw.shape
+    assert c == 3 and x_nchw.dtype == torch.float32
+    cout = w147.shape[1]
+    assert tuple(w147.shape) == (147, cout) and tuple(scale.shape) == tuple(shift.shape) == (cout,)
+    hp, wp = ((h - 1) // 2) // 2 + 1, ((w - 1) // 2) // 2 + 1
+    if y is None:
+        y = View(torch.empty((n, hp, wp, cout), dtype=torch.float32, device=x_nchw.device))
+    assert y.nhw == (n, hp, wp) and y.c == cout
+    check(lib.cmk_stem7x7_bn_relu_maxpool_nchw3(x_nchw.data_ptr(), w147.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.t.data_ptr(), y.cs, y.co,
+                                                n, h, w, cout, _stream()), "cmk_stem7x7_bn_relu_maxpool_nchw3")
+    return y
+
+
 def pack_dw_weight(weight: torch.Tensor) -> torch.Tensor:
     """(C,1,3,3) depth-wise weight -> tap-major [9][C] (the layout cmk_dwconv3x3_nhwc reads)."""
     c = weight.shape[0]

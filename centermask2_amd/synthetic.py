@@ -65,6 +65,35 @@ def mobilenetv2_param_shapes(prefix: str = "") -> "OrderedDict[str, Tuple[int, .
     return s
 
 
+RESNET_DEPTHS = {"R-50": 50, "R-101": 101, "R-152": 152}      # conv_body names of the detectron2 bottleneck ResNets (MODEL.RESNETS.DEPTH)
+RESNET_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+
+
+def resnet_param_shapes(depth: int = 50, prefix: str = "", last_stage: int = 5, res2_out: int = 256, width: int = 64) -> "OrderedDict[str, Tuple[int, ...]]":
+    """State-dict entries of detectron2's bottleneck ResNet up to res<last_stage>, in d2's key names and order (the shortcut of a stage's
+    first block is registered before its conv1)."""
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+
+    def conv_bn(key: str, cin: int, cout: int, k: int) -> None:
+        s[key + ".weight"] = (cout, cin, k, k)
+        for n in ("weight", "bias", "running_mean", "running_var"):
+            s["{}.norm.{}".format(key, n)] = (cout,)
+
+    conv_bn(prefix + "stem.conv1", 3, 64, 7)
+    cin, cout = 64, res2_out
+    for stage, blocks in zip(range(2, last_stage + 1), RESNET_BLOCKS[depth]):
+        for i in range(blocks):
+            p = "{}res{}.{}.".format(prefix, stage, i)
+            if cin != cout:
+                conv_bn(p + "shortcut", cin, cout, 1)
+            conv_bn(p + "conv1", cin, width, 1)
+            conv_bn(p + "conv2", width, width, 3)
+            conv_bn(p + "conv3", width, cout, 1)
+            cin = cout
+        cout, width = cout * 2, width * 2
+    return s
+
+
 def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_ch: int = 256,
                        mask_dim: int = 256, pooler_res: int = 14, stage_with_dcn=(False, False, False, False),
                        with_modulated_dcn: bool = False, deformable_groups: int = 1, keypoint_on: bool = False,
@@ -76,12 +105,16 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
     stage_with_dcn / with_modulated_dcn / deformable_groups: MODEL.VOVNET.STAGE_WITH_DCN etc.; the 3x3 layers of a flagged stage are
     DFConv3x3 (vovnet.py:132-201: '/conv_offset' with bias, '/conv', '/norm'), except in the depth-wise bodies (vovnet.py:292-298).
     conv_body "MobileNetV2": the CenterMask-Lite body behind build_fcos_mobilenetv2_fpn_backbone, FPN laterals over `fpn_in`
-    (MODEL.FPN.IN_FEATURES) and `top_levels` (MODEL.FCOS.TOP_LEVELS) top convs.  num_tower_convs / mask_num_conv / maskiou_num_conv:
+    (MODEL.FPN.IN_FEATURES) and `top_levels` (MODEL.FCOS.TOP_LEVELS) top convs.  conv_body "R-50" / "R-101" / "R-152": detectron2's
+    bottleneck ResNet behind build_fcos_resnet_fpn_backbone at d2's default widths, with the same `fpn_in` / `top_levels`.  num_tower_convs / mask_num_conv / maskiou_num_conv:
     MODEL.FCOS.NUM_{CLS,BOX}_CONVS, MODEL.ROI_MASK_HEAD.NUM_CONV, MODEL.ROI_MASKIOU_HEAD.NUM_CONV; fpn_ch and mask_dim the widths."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
     if conv_body == MOBILENETV2:
         s.update(mobilenetv2_param_shapes("backbone.bottom_up."))
         _fpn_shapes(s, [(int(f[3:]), MNV2_OUT_CHANNELS[f]) for f in fpn_in], fpn_ch, top_levels)
+    elif conv_body in RESNET_DEPTHS:
+        s.update(resnet_param_shapes(RESNET_DEPTHS[conv_body], "backbone.bottom_up.", last_stage=max(int(f[3:]) for f in fpn_in)))
+        _fpn_shapes(s, [(int(f[3:]), 2 ** (int(f[3:]) + 6)) for f in fpn_in], fpn_ch, top_levels)
     else:
         _vovnet_shapes(s, STAGE_SPECS[conv_body], stage_with_dcn, with_modulated_dcn, deformable_groups)
         _fpn_shapes(s, list(zip((3, 4, 5), STAGE_SPECS[conv_body]["stage_out_ch"][1:])), fpn_ch, 2)
@@ -221,6 +254,8 @@ def synthetic_tensor(name: str, shape: Iterable[int], seed: int = 0) -> torch.Te
         fan_in = shape[1] * shape[2] * shape[3]
         project = ".conv." in name and shape[2] == 1 and int(name.split(".")[-2]) in (3, 6)      # the linear 1x1 that ends a block
         return randn(math.sqrt((1.0 if project else 2.0) / fan_in))                            # a ReLU6 follows every other conv
+    if name.endswith("stem.conv1.norm.running_var"):
+        return rand(0.5, 1.5) * 400.0                 # the ResNet stem reads pixels too
     if name.endswith("stem_1/norm.running_var"):
         return rand(0.5, 1.5) * 400.0                 # pixel-scale inputs (std ~20) are normalised by the first BN
     if name.endswith("norm.weight") or name.endswith("norm.running_var"):     # '/norm.' and the dw bodies' '/pw_norm.'
@@ -280,6 +315,18 @@ def make_synthetic_state_dict(conv_body: str = "V-39-eSE", seed: int = 0, shapes
     shapes = shapes if shapes is not None else model_param_shapes(conv_body, **dcn)
     sd = OrderedDict((k, synthetic_tensor(k, v, seed).float().contiguous()) for k, v in shapes.items())
     if conv_body == MOBILENETV2:
+        return sd
+    if conv_body in RESNET_DEPTHS:
+        # relu(conv3(..) + shortcut(x) or x): conv3 and the shortcut are Kaiming-normal (gain 2) with no ReLU of their own behind them,
+        # so each branch doubles the second moment, and the sum adds the branches up; unscaled, the activations double in every one
+        # of the 16-50 blocks.  The FrozenBN affine that ends a branch is scaled by 1/sqrt(2) for the gain and by 1/sqrt(branches): the
+        # two branches of a stage's first block by 1/2, the identity blocks of a stage (which share one unit of growth, the 1/sqrt(blocks)
+        # rule of the VoVNet bodies below) by 1/sqrt(2 * blocks in the stage).
+        per_stage = RESNET_BLOCKS[RESNET_DEPTHS[conv_body]]
+        for k in sd:
+            m = re.search(r"\.res(\d)\.(\d+)\.(conv3|shortcut)\.norm\.(weight|bias)$", k)
+            if m:
+                sd[k] = (sd[k] * (4 if m.group(2) == "0" else 2 * per_stage[int(m.group(1)) - 2]) ** -0.5).contiguous()
         return sd
     blocks = STAGE_SPECS[conv_body]["block_per_stage"]
     for k in sd:

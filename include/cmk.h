@@ -219,6 +219,14 @@ int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, const float* w
 int cmk_stem_conv_nchw3(const float* x, const float* w /* [27][Cout] */, const float* scale, const float* shift,
                         float* y, int N, int H, int W, int Cout, void* stream);
 
+/* d2 BasicStem: y = max_pool2d(relu(conv7x7_s2_p3(x) * scale[c] + shift[c]), kernel 3, stride 2, padding 1)
+ * x (N,3,H,W) NCHW fp32; w [147][Cout], k = (kh*7 + kw)*3 + ci; y (N,Hp,Wp,Cout) NHWC channel-slice view.
+ * Hc = (H-1)/2 + 1, Wc likewise (conv); Hp = (Hc-1)/2 + 1, Wp likewise (pool). Pool padding never wins (-inf).
+ * One launch (csrc/stem7_pool.hip): the conv map stays in LDS.  Cout must be 64.  Conv taps outside the image are zeros; a NaN
+ * behaves as in torch (relu keeps it, the max returns it for every window that holds it). */
+int cmk_stem7x7_bn_relu_maxpool_nchw3(const float* x, const float* w, const float* scale, const float* shift,
+                                      float* y, int y_cs, int y_co, int N, int H, int W, int Cout, void* stream);
+
 /* ---- max pool k3 s2 ceil_mode, no padding (vovnet.py:349-350); k2 s2 (maskiou_head.py:93,108) ----------------- */
 /* gate: optional (N*C) non-negative channel gate applied after the max (the eSE scale of the producer block, folded in). */
 int cmk_maxpool3x3s2_ceil_nhwc(const float* x, int x_cs, int x_co, float* y, int y_cs, int y_co,
