@@ -1,4 +1,5 @@
-// Shared by the conv kernels of libcmk_hip.so: launch arguments (one struct passed by value) and vector types.
+// Shared by the conv kernels of libcmk_hip.so and their front door (conv.hip): launch arguments (one struct passed by value), vector types
+// and the prototypes through which conv.hip reaches each kernel file.
 #pragma once
 #include "cmk_common.hpp"
 
@@ -60,6 +61,19 @@ struct DeviceOnce {
     }
 };
 
+struct Variant { int wm, sc, wn; };
+
+inline int out_size(int h, int stride) { return stride == 1 ? h : (h - 1) / 2 + 1; }     // k3 p1 s2: floor((H+2-3)/2)+1
+
+// conv_igemm.hip: the direct implicit-GEMM kernel, variant v (= WM, SC, WN) of a 1x1 or a 3x3 stride 1 | 2 conv; sets a.cout_pad
+int launch_igemm(ConvArgs& a, int ksize, int stride, int cout32, Variant v, hipStream_t st);
+// conv_igemm.hip: its gather form (cmk.h tune_wm 7), wn = 4 | 2 | 1 cout tiles per wave
+int launch_igemm_gather(ConvArgs& a, int wn, int grid_y, hipStream_t st);
+// conv_igemm.hip: whether the direct kernel has variant (wm, sc, wn) for this conv, and the cost model's choice among those it has
+bool variant_ok(int taps, int stride, int cout32, int wm, int sc, int wn);
+Variant choose_variant(const cmk_conv_desc* descs, int n, int taps, int stride, int cout32);
+// conv_wino4r.hip: fused Winograd F(2x2,3x3)
+int launch_wino4r(ConvArgs& a, hipStream_t st);
 // conv_wino6.hip: fused Winograd F(4x4,3x3); pair: the paired form, 64 couts per workgroup from one shared W image (one 8-wave workgroup per CU)
 int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st);
 // conv_wino6s.hip: the same, 64 couts per workgroup from one frequency image shared through LDS (one 8-wave workgroup per CU)

@@ -40,7 +40,7 @@ __device__ f32x4 pw_buffer_load(i32x4 rsrc, int voffset, int soffset, int aux) _
 // UPRES: the FPN top-down add — the residual is the nearest-neighbour 2x upsampling of a map of half the size (a.res, a.Hr x a.Wr); needs an
 // even output width (then the pixel pairs the epilogue handles share one residual pixel).
 // SPLITK: blockIdx.y owns an (even) range of the K chunks and leaves raw partial sums in a.ws[z][pixel][cout_pad]; the caller runs
-// conv_igemm's reduce kernel (scale/shift/residual/ReLU there).  For the skinny GEMMs: MaskIoU fc1 (400 x 12544 x 1024), the 14 -> 7 conv.
+// the reduce kernel of conv.hip (scale/shift/residual/ReLU there).  For the skinny GEMMs: MaskIoU fc1 (400 x 12544 x 1024), the 14 -> 7 conv.
 // SPLIT (opt-in, cmk.h tune_wm 10; MT 4, no GA / UPRES / SPLITK): the same GEMM with fp32-ACCURATE products built from bf16 pieces on
 // v_mfma_f32_32x32x16_bf16 (2.0 PFLOP/s against the fp32 instruction's 0.157): every fp32 operand is split into three bf16 values
 // (x = hi + mid + lo exactly to 2^-24: hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), round to nearest even) and the six products of
@@ -626,7 +626,7 @@ static int launch_pw_mt(ConvArgs& a, hipStream_t st) {
     return check_launch("conv_pw");
 }
 
-// mt = 4 | 2.  The caller (conv_igemm.hip: run) has filled the problem, views, epilogue options and cout_pad; a.ga_stride = 1 | 2 asks for
+// mt = 4 | 2.  The caller (conv.hip: run) has filled the problem, views, epilogue options and cout_pad; a.ga_stride = 1 | 2 asks for
 // the gather form of a 3x3 conv (a.w then is conv_igemm's 9-tap packing), 0 for a 1x1 conv.
 int launch_pw(ConvArgs& a, int mt, hipStream_t st) {
     const ConvProblem& p = a.p[0];

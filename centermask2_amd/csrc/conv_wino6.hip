@@ -26,7 +26,7 @@
 //     addresses set up once, two periods per trip so that the W buffer is a compile-time offset); the fused-affine variant adds 48.
 //   * weights never touch LDS: U is packed so that every operand load of a wave is one contiguous KiB ([chunk][cout tile][wave][9][lane][4])
 //     and is fetched two steps (24 MFMAs) ahead into registers, as in the 2x2 kernel.
-//   * epilogue: each wave reduces its frequencies along b in registers (6 -> 4 and 3 -> 4 partial values per entry), the four waves swap
+//   * epilogue (w6_epilogue in wino6_common.hpp, shared with conv_wino6s.hip): each wave reduces its frequencies along b in registers (6 -> 4 and 3 -> 4 partial values per entry), the four waves swap
 //     those through LDS in two rounds, and wave w finishes the 8 tiles of accumulator registers 4w..4w+3: column pass, scale/shift/ReLU,
 //     NHWC stores, GroupNorm statistics — on pairs of accumulator registers with packed fp32, interior tiles stored through a scalar-walked
 //     base + one lane offset per tile (~460 VALU instructions per wave; the scalar form took ~1080 and 12.4 us beside a partner's MFMAs).
@@ -363,185 +363,12 @@ __device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
         period(c + 1, std::integral_constant<int, 1>{});
     }
 
-    // ---- epilogue ------------------------------------------------------------------------------------------------------------------
-    // A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1].  Row pass in registers: per accumulator entry the wave's 6 + 3
-    // frequencies become P[rowA][0..3] and the partial P[rowB][0..3] of its half (the two halves add up).  Wave d finishes the tiles of
-    // accumulator registers 4d..4d+3: in round q the other waves send it the 8 values of registers 4d+2q, 4d+2q+1.
-    // scale/shift are requested here: the two exchange rounds cover their latency (loaded inside the store loop they would serialise it)
-    const int co = co0 + li;
-    const bool cvalid = co < a.Cout;
-    float sc = P.scale[min(co, a.Cout - 1)];
-    float sh = P.shift[min(co, a.Cout - 1)];
-    __syncthreads();
-    // The stores below sit in per-tile predicated blocks; the compiler's wait-count pass cannot prove across their joins that the two loads
-    // above have landed and would put `s_waitcnt vmcnt(0)` in front of every store — which also waits for the previous STORE to retire
-    // (measured: 340 ns per store, 26 us of a 76 us workgroup).  Wait once here and hand the values over through an asm the pass
-    // cannot see through: from now on they are plain register values.
-    asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %0\n\tv_mov_b32 %1, %1" : "+v"(sc), "+v"(sh) : : "memory");
-    // split-K: raw partial sums (no scale / shift / ReLU) go to this split's slab of a.ws, laid out [pixel][cout_pad]; the reduce kernel of
-    // conv_igemm.hip sums the slabs in a fixed order and applies the epilogue
-    // raw is a property of the WORKGROUP: with a tail (GEO 1) only its pieces are raw; their slabs hold the tail's images alone, so a piece
-    // stores image n at slab image n - n_ws, and the main part's workgroups store finished values to y as ever
-    const bool raw = nsplit > 1;
-    const long slab_pix = GEO == 1 ? (long)(P.N - n_ws) * H * W : P.total_pix;
-    float* const ybuf = raw ? a.ws + (long)ks * slab_pix * a.cout_pad : P.y;
-    const int n_st = n - n_ws;
-    const int ycs = raw ? a.cout_pad : a.y_cs, yco = raw ? 0 : a.y_co;
-    if (raw) { sc = 1.f; sh = 0.f; }
-    // Everything below works on PAIRS of accumulator registers (r, r+1 = two tiles of the lane) with packed-fp32 instructions, and the
-    // stores of interior tiles take a wave-uniform (row, column) base from the scalar unit plus one lane offset per tile: a VALU instruction
-    // issued here waits for a gap in the MFMA stream of the other workgroup on the SIMD and takes the slot from it (trace: this epilogue
-    // ran 12.4 us next to a partner, 5.6 us alone), so the epilogue is priced in VALU instructions — 3x fewer than the scalar form.
-    f32x2* ex2 = reinterpret_cast<f32x2*>(smem + half * W6_EX_FLOATS);        // exchange: [src wave][dst wave][value 0..7][lane] pairs = 64 KiB (PAIR: per half)
-    const float lo = (co < a.relu_upto && !raw) ? 0.f : __builtin_nanf("");      // max(v, NaN) = v: lanes without the ReLU
-    const f32x2 sc2 = {sc, sc}, sh2 = {sh, sh};
-    auto fma2 = [](f32x2 x, float k, f32x2 y) { return __builtin_elementwise_fma(x, f32x2{k, k}, y); };
-    const bool want_stats = a.gn_ws != nullptr;
-    f32x2 gs2 = {0.f, 0.f}, gss2 = {0.f, 0.f};
-    float gs = 0.f, gss = 0.f;
-    float* yimg = ybuf + (long)n_st * H * W * ycs + yco + co;
-    // scalar side of the store addresses: image base (the pair's first image for GEO 1) and the byte strides of one pixel / one row
-    unsigned long long ybase_s;
-    {
-        const unsigned long long yb = (unsigned long long)(ybuf + (long)n_st * H * W * ycs);
-        ybase_s = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(yb >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)yb);
-    }
-    const unsigned long long px_b = (unsigned long long)ycs * 4u, rowskip_b = (unsigned long long)(W - 3) * ycs * 4u;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        f32x2 own[8];
-#pragma unroll
-        for (int dd = 0; dd < 4; ++dd) {
-            const int r0 = 4 * dd + 2 * q;
-            f32x2 v[8];
-            {
-                const f32x2 m0 = {acc[0][r0], acc[0][r0 + 1]}, m1 = {acc[1][r0], acc[1][r0 + 1]}, m2 = {acc[2][r0], acc[2][r0 + 1]},
-                            m3 = {acc[3][r0], acc[3][r0 + 1]}, m4 = {acc[4][r0], acc[4][r0 + 1]}, m5 = {acc[5][r0], acc[5][r0 + 1]};
-                const f32x2 s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-                v[0] = m0 + s1 + s2;
-                v[1] = fma2(d2, 2.0f, d1);
-                v[2] = fma2(s2, 4.0f, s1);
-                v[3] = fma2(d2, 8.0f, d1) + m5;
-                const f32x2 n0 = {acc[6][r0], acc[6][r0 + 1]}, n1 = {acc[7][r0], acc[7][r0 + 1]}, n2 = {acc[8][r0], acc[8][r0 + 1]};
-                if (halfB == 0) {      // b = 0, 1, 2
-                    const f32x2 t1 = n1 + n2, e1 = n1 - n2;
-                    v[4] = n0 + t1; v[5] = e1; v[6] = t1; v[7] = e1;
-                } else {               // b = 3, 4, 5
-                    const f32x2 t2s = n0 + n1, e2 = n0 - n1;
-                    v[4] = t2s; v[5] = e2 + e2; v[6] = t2s * 4.0f; v[7] = fma2(e2, 8.0f, n2);
-                }
-            }
-            if (dd == wave) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) own[k] = v[k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) ex2[(((wave * 4 + dd) * 8 + k) << 6) + lane] = v[k];
-            }
-        }
-        __syncthreads();
-        // P[a][j]: rows 0..3 from waves 0..3 (values 0..3), row 4 = halves of waves 0, 1, row 5 = halves of waves 2, 3 (values 4..7)
-        f32x2 Pm[6][4];
-        {
-            f32x2 part[4][4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                f32x2 v[8];
-                if (s == wave) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = own[k];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = ex2[(((s * 4 + wave) * 8 + k) << 6) + lane];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { Pm[s][j] = v[j]; part[s][j] = v[4 + j]; }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { Pm[4][j] = part[0][j] + part[1][j]; Pm[5][j] = part[2][j] + part[3][j]; }
-        }
-        f32x2 yv[4][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x2 s1 = Pm[1][j] + Pm[2][j], d1 = Pm[1][j] - Pm[2][j], s2 = Pm[3][j] + Pm[4][j], d2 = Pm[3][j] - Pm[4][j];
-            f32x2 y[4];
-            y[0] = Pm[0][j] + s1 + s2;
-            y[1] = fma2(d2, 2.0f, d1);
-            y[2] = fma2(s2, 4.0f, s1);
-            y[3] = fma2(d2, 8.0f, d1) + Pm[5][j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                f32x2 t = __builtin_elementwise_fma(y[i], sc2, sh2);
-                t.x = fmaxf(t.x, lo);
-                t.y = fmaxf(t.y, lo);
-                yv[i][j] = t;
-            }
-        }
-        // the pair's entries are accumulator registers 4*wave + 2q, +1 of lane half hh: tiles m, m + 1
-        bool full[2];
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int m = 2 * q + rr + 8 * wave + 4 * hh;
-            int mimg, mt, mtc;
-            G::tile_of(m, mimg, mt, mtc);
-            const int oh = oh0 + 4 * mt, ow = ow0 + 4 * mtc;
-            const bool tile_ok = cvalid && m < G::TILES && n + mimg < P.N;
-            full[rr] = tile_ok && oh + 4 <= H && ow + 4 <= W;
-            if (full[rr]) {                             // interior tile: 16 stores, no per-store predicate, no vector address arithmetic
-                const unsigned voff = (unsigned)((((mimg * H + oh) * W + ow) * ycs + yco + co) * 4);
-                unsigned long long sp = ybase_s;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float val = rr ? yv[i][j].y : yv[i][j].x;
-                        // ("+s": the pointer is walked between the stores, not computed 16 times up front)
-                        // nt: the output is a stream (84 MB per launch at stage 2) that must not push the weights and the halo lines this launch re-reads
-                        // out of L2; measured -2.2 % on the map shapes, +0.4 % end to end (profiles/r03_ablations.txt), sc0 / sc1 nothing
-                        asm volatile("global_store_dword %1, %2, %0 nt" : "+s"(sp) : "v"(voff), "v"(val) : "memory");
-                        sp += j == 3 ? rowskip_b : px_b;
-                    }
-            } else if (tile_ok) {
-                float* yp0 = yimg + (((long)mimg * H + oh) * W + ow) * ycs;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (oh + i < H && ow + j < W) {
-                            const float val = rr ? yv[i][j].y : yv[i][j].x;
-                            yp0[((long)i * W + j) * ycs] = val;
-                            gs += val;
-                            gss = fmaf(val, val, gss);
-                        }
-            }
-        }
-        if (want_stats) {                               // whole tiles: packed, masked by tile
-            const f32x2 mask = {full[0] ? 1.f : 0.f, full[1] ? 1.f : 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f32x2 t = yv[i][j] * mask;
-                    gs2 += t;
-                    gss2 = __builtin_elementwise_fma(t, yv[i][j], gss2);
-                }
-        }
-        if (q == 0) __syncthreads();                        // the exchange buffer is reused by round 1
-    }
-    gs += gs2.x + gs2.y;
-    gss += gss2.x + gss2.y;
-    // fused GroupNorm statistics of the NEXT layer's normalisation (fcos.py:182-186): one {sum, sumsq} record per
-    // (spatial tile, wave, group)
-    if (a.gn_ws) {
-        for (int o = 1; o < a.gn_cpg; o <<= 1) { gs += __shfl_xor(gs, o); gss += __shfl_xor(gss, o); }
-        gs += __shfl_xor(gs, 32);
-        gss += __shfl_xor(gss, 32);
-        if (cvalid && hh == 0 && (li & (a.gn_cpg - 1)) == 0) {
-            double* o = a.gn_ws + (((long)bx * 4 + wave) * a.gn_groups + co / a.gn_cpg) * 2;
-            o[0] = (double)gs;
-            o[1] = (double)gss;
-        }
-    }
+    // ---- epilogue (w6_epilogue, wino6_common.hpp) -----------------------------------------------------------------------------------
+    // split-K: raw partial sums (no scale / shift / ReLU) go to slab ks of a.ws, whose first image is n_ws; the reduce kernel (conv.hip)
+    // sums the slabs in a fixed order and applies the epilogue
+    const W6Out<bool> out{nsplit > 1, ks, n_ws};
+    // exchange area: 64 KiB from the start of LDS (PAIR: per half)
+    w6_epilogue<GEO>(a, P, acc, smem, half * W6_EX_FLOATS, wave, lane, li, hh, std::true_type{}, co0, H, W, n, oh0, ow0, bx, out);
 }
 
 template <bool AFF, int GEO>
@@ -568,19 +395,7 @@ static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
         return e == hipSuccess ? CMK_OK : fail(CMK_ELAUNCH, "conv_wino6: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     });
     if (rc) return rc;
-    int blocks = 0;
-    for (int i = 0; i < a.nprob; ++i) {
-        ConvProblem& p = a.p[i];
-        p.tile_begin = blocks;
-        if (GEO == 0) {
-            p.tiles_h = cdiv(p.Ho, W6G<0>::OH);
-            p.tiles_w = cdiv(p.Wo, W6G<0>::OW);
-            blocks += p.N * p.tiles_h * p.tiles_w;
-        } else {
-            p.tiles_h = p.tiles_w = 1;
-            blocks += cdiv(p.N, 2);
-        }
-    }
+    const int blocks = w6_assign_tiles<GEO>(a);
     a.grid_y = cdiv(a.Cout, 32);          // 32-cout tiles (the packed weights' layout); PAIR: the grid walks pairs of them
     a.total_tiles = blocks;
     if (a.ksplit < 1) a.ksplit = 1;
@@ -605,9 +420,8 @@ static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
 // geo 0: 12x40-pixel tiles of one image; geo 1: pairs of whole maps of at most 16 rows x 14 columns (one problem, no fused GN statistics);
 // pair: the paired form (64 couts per workgroup)
 int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st) {
-    for (int i = 0; i < a.nprob; ++i)       // the epilogue's stores take a 32-bit byte offset inside the output image (GEO 1: inside a pair of images)
-        if ((long)(geo == 0 ? 1 : 2) * a.p[i].H * a.p[i].W * std::max(a.y_cs, a.cout_pad) * 4 >= (1L << 32))
-            return fail(CMK_EINVAL, "conv_wino6: an output image of 4 GiB or more%s", "");
+    // (a split-K or tail workgroup stores with pixel stride cout_pad)
+    if (int rc = w6_refuse_size(a, geo, std::max(a.y_cs, a.cout_pad), "conv_wino6")) return rc;
     // split-K of the map geometry keeps its even-split rule; the RoI-pair geometry gives every piece whole chunk pairs (w6_piece_bounds), so
     // there any number of ways up to the pair count goes
     if (a.ksplit > 1 && (a.nprob != 1 || a.gn_ws || !a.ws || (geo == 0 ? ((a.Cin >> 3) % (2 * a.ksplit)) != 0 : a.ksplit > (a.Cin >> 4)) ||
@@ -619,8 +433,7 @@ int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st) {
             return fail(CMK_EINVAL, "conv_wino6: tail split-K takes one problem, no GroupNorm statistics, no split-K beside it, a workspace and at most Cin / 16 ways%s", "");
     }
     if (geo == 0) return pair ? launch_wino6_geo<0, true>(a, st) : launch_wino6_geo<0, false>(a, st);
-    if (a.nprob != 1 || a.p[0].H > 16 || a.p[0].W > 14 || a.gn_ws)
-        return fail(CMK_EINVAL, "conv_wino6: the RoI-pair geometry (with split-K or a split-K tail as without) takes one problem of maps up to 16x14 and produces no GroupNorm statistics%s", "");
+    if (int rc = w6_refuse_roi_pairs(a, "conv_wino6: the RoI-pair geometry (with split-K or a split-K tail as without)")) return rc;
     return pair ? launch_wino6_geo<1, true>(a, st) : launch_wino6_geo<1, false>(a, st);
 }
 

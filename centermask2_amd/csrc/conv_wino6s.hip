@@ -370,169 +370,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     if (act) loop(std::true_type{});
     else loop(std::false_type{});
 
-    // ---- epilogue (conv_wino6.hip's, per cout tile: wave group ct works in its own 64 KiB of the exchange area) ----------------------
-    // A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1].  Row pass in registers: per accumulator entry the wave's 6 + 3
-    // frequencies become P[rowA][0..3] and the partial P[rowB][0..3] of its half.  Wave d of a group finishes the tiles of accumulator
-    // registers 4d..4d+3: in round q the other waves of the group send it the 8 values of registers 4d+2q, 4d+2q+1.
-    const int halfB = g & 1;
-    const int co = co0 + li;
-    const bool cvalid = act && co < a.Cout;
-    float sc = P.scale[min(co, a.Cout - 1)];
-    float sh = P.shift[min(co, a.Cout - 1)];
-    __syncthreads();
-    asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %0\n\tv_mov_b32 %1, %1" : "+v"(sc), "+v"(sh) : : "memory");
-    f32x2* ex2 = reinterpret_cast<f32x2*>(smem) + ct * (64 * 1024 / 8);        // exchange: [src wave][dst wave][value 0..7][lane] pairs = 64 KiB
-    const float lo = co < a.relu_upto ? 0.f : __builtin_nanf("");      // max(v, NaN) = v: lanes without the ReLU
-    const f32x2 sc2 = {sc, sc}, sh2 = {sh, sh};
-    auto fma2 = [](f32x2 x, float k, f32x2 y) { return __builtin_elementwise_fma(x, f32x2{k, k}, y); };
-    const bool want_stats = a.gn_ws != nullptr;
-    f32x2 gs2 = {0.f, 0.f}, gss2 = {0.f, 0.f};
-    float gs = 0.f, gss = 0.f;
-    float* yimg = P.y + (long)n * H * W * a.y_cs + a.y_co + co;
-    unsigned long long ybase_s;
-    {
-        const unsigned long long yb = (unsigned long long)(P.y + (long)n * H * W * a.y_cs);
-        ybase_s = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(yb >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)yb);
-    }
-    const unsigned long long px_b = (unsigned long long)a.y_cs * 4u, rowskip_b = (unsigned long long)(W - 3) * a.y_cs * 4u;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        f32x2 own[8];
-        if (act) {
-#pragma unroll
-            for (int dd = 0; dd < 4; ++dd) {
-                const int r0 = 4 * dd + 2 * q;
-                f32x2 v[8];
-                {
-                    const f32x2 m0 = {acc[0][r0], acc[0][r0 + 1]}, m1 = {acc[1][r0], acc[1][r0 + 1]}, m2 = {acc[2][r0], acc[2][r0 + 1]},
-                                m3 = {acc[3][r0], acc[3][r0 + 1]}, m4 = {acc[4][r0], acc[4][r0 + 1]}, m5 = {acc[5][r0], acc[5][r0 + 1]};
-                    const f32x2 s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-                    v[0] = m0 + s1 + s2;
-                    v[1] = fma2(d2, 2.0f, d1);
-                    v[2] = fma2(s2, 4.0f, s1);
-                    v[3] = fma2(d2, 8.0f, d1) + m5;
-                    const f32x2 n0 = {acc[6][r0], acc[6][r0 + 1]}, n1 = {acc[7][r0], acc[7][r0 + 1]}, n2 = {acc[8][r0], acc[8][r0 + 1]};
-                    if (halfB == 0) {      // b = 0, 1, 2
-                        const f32x2 t1 = n1 + n2, e1 = n1 - n2;
-                        v[4] = n0 + t1; v[5] = e1; v[6] = t1; v[7] = e1;
-                    } else {               // b = 3, 4, 5
-                        const f32x2 t2s = n0 + n1, e2 = n0 - n1;
-                        v[4] = t2s; v[5] = e2 + e2; v[6] = t2s * 4.0f; v[7] = fma2(e2, 8.0f, n2);
-                    }
-                }
-                if (dd == g) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) own[k] = v[k];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) ex2[(((g * 4 + dd) * 8 + k) << 6) + lane] = v[k];
-                }
-            }
-        }
-        __syncthreads();
-        if (act) {
-            // P[a][j]: rows 0..3 from waves 0..3 (values 0..3), row 4 = halves of waves 0, 1, row 5 = halves of waves 2, 3 (values 4..7)
-            f32x2 Pm[6][4];
-            {
-                f32x2 part[4][4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    f32x2 v[8];
-                    if (s == g) {
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) v[k] = own[k];
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) v[k] = ex2[(((s * 4 + g) * 8 + k) << 6) + lane];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { Pm[s][j] = v[j]; part[s][j] = v[4 + j]; }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { Pm[4][j] = part[0][j] + part[1][j]; Pm[5][j] = part[2][j] + part[3][j]; }
-            }
-            f32x2 yv[4][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x2 s1 = Pm[1][j] + Pm[2][j], d1 = Pm[1][j] - Pm[2][j], s2 = Pm[3][j] + Pm[4][j], d2 = Pm[3][j] - Pm[4][j];
-                f32x2 y[4];
-                y[0] = Pm[0][j] + s1 + s2;
-                y[1] = fma2(d2, 2.0f, d1);
-                y[2] = fma2(s2, 4.0f, s1);
-                y[3] = fma2(d2, 8.0f, d1) + Pm[5][j];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    f32x2 t = __builtin_elementwise_fma(y[i], sc2, sh2);
-                    t.x = fmaxf(t.x, lo);
-                    t.y = fmaxf(t.y, lo);
-                    yv[i][j] = t;
-                }
-            }
-            // the pair's entries are accumulator registers 4*g + 2q, +1 of lane half hh: tiles m, m + 1
-            bool full[2];
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-                const int m = 2 * q + rr + 8 * g + 4 * hh;
-                int mimg, mt, mtc;
-                G::tile_of(m, mimg, mt, mtc);
-                const int oh = oh0 + 4 * mt, ow = ow0 + 4 * mtc;
-                const bool tile_ok = cvalid && m < G::TILES && n + mimg < P.N;
-                full[rr] = tile_ok && oh + 4 <= H && ow + 4 <= W;
-                if (full[rr]) {                             // interior tile: 16 stores, no per-store predicate, no vector address arithmetic
-                    const unsigned voff = (unsigned)((((mimg * H + oh) * W + ow) * a.y_cs + a.y_co + co) * 4);
-                    unsigned long long sp = ybase_s;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float val = rr ? yv[i][j].y : yv[i][j].x;
-                            // nt: the output is a stream (84 MB per launch at stage 2) that must not push the weights and the halo lines this launch re-reads
-                        // out of L2; measured -2.2 % on the map shapes, +0.4 % end to end (profiles/r03_ablations.txt), sc0 / sc1 nothing
-                        asm volatile("global_store_dword %1, %2, %0 nt" : "+s"(sp) : "v"(voff), "v"(val) : "memory");
-                            sp += j == 3 ? rowskip_b : px_b;
-                        }
-                } else if (tile_ok) {
-                    float* yp0 = yimg + (((long)mimg * H + oh) * W + ow) * a.y_cs;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (oh + i < H && ow + j < W) {
-                                const float val = rr ? yv[i][j].y : yv[i][j].x;
-                                yp0[((long)i * W + j) * a.y_cs] = val;
-                                gs += val;
-                                gss = fmaf(val, val, gss);
-                            }
-                }
-            }
-            if (want_stats) {                               // whole tiles: packed, masked by tile
-                const f32x2 mask = {full[0] ? 1.f : 0.f, full[1] ? 1.f : 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const f32x2 t = yv[i][j] * mask;
-                        gs2 += t;
-                        gss2 = __builtin_elementwise_fma(t, yv[i][j], gss2);
-                    }
-            }
-        }
-        if (q == 0) __syncthreads();                        // the exchange buffer is reused by round 1
-    }
-    gs += gs2.x + gs2.y;
-    gss += gss2.x + gss2.y;
-    // fused GroupNorm statistics of the NEXT layer's normalisation (fcos.py:182-186): one {sum, sumsq} record per
-    // (spatial tile, wave g of the group, group of channels) — the record layout of conv_wino6.hip
-    if (a.gn_ws && act) {
-        for (int o = 1; o < a.gn_cpg; o <<= 1) { gs += __shfl_xor(gs, o); gss += __shfl_xor(gss, o); }
-        gs += __shfl_xor(gs, 32);
-        gss += __shfl_xor(gss, 32);
-        if (cvalid && hh == 0 && (li & (a.gn_cpg - 1)) == 0) {
-            double* o = a.gn_ws + (((long)bx * 4 + g) * a.gn_groups + co / a.gn_cpg) * 2;
-            o[0] = (double)gs;
-            o[1] = (double)gss;
-        }
-    }
+    // ---- epilogue (w6_epilogue, wino6_common.hpp), per cout tile: wave group ct works in its own 64 KiB of the exchange area -------------
+    w6_epilogue<GEO>(a, P, acc, smem, ct * (64 * 1024 / 4), g, lane, li, hh, act, co0, H, W, n, oh0, ow0, bx,
+                     W6Out<std::false_type>{{}, 0, 0});
 }
 
 template <int GEO>
@@ -545,19 +385,7 @@ static int launch_wino6s_geo(ConvArgs& a, hipStream_t st) {
         return e == hipSuccess ? CMK_OK : fail(CMK_ELAUNCH, "conv_wino6s: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     });
     if (rc) return rc;
-    int blocks = 0;
-    for (int i = 0; i < a.nprob; ++i) {
-        ConvProblem& p = a.p[i];
-        p.tile_begin = blocks;
-        if (GEO == 0) {
-            p.tiles_h = cdiv(p.Ho, W6G<0>::OH);
-            p.tiles_w = cdiv(p.Wo, W6G<0>::OW);
-            blocks += p.N * p.tiles_h * p.tiles_w;
-        } else {
-            p.tiles_h = p.tiles_w = 1;
-            blocks += cdiv(p.N, 2);
-        }
-    }
+    const int blocks = w6_assign_tiles<GEO>(a);
     a.grid_y = cdiv(cdiv(a.Cout, 32), 2);
     a.total_tiles = blocks;
     if (a.ksplit > 1) return fail(CMK_EINVAL, "conv_wino6s: split-K is a feature of the 32-cout form (tune_sc 16)%s", "");
@@ -571,12 +399,9 @@ static int launch_wino6s_geo(ConvArgs& a, hipStream_t st) {
 
 // geo 0: 12x40-pixel tiles of one image; geo 1: pairs of whole maps of at most 16 rows x 14 columns (one problem, no fused GN statistics)
 int launch_wino6s(ConvArgs& a, int geo, hipStream_t st) {
-    for (int i = 0; i < a.nprob; ++i)       // the epilogue's stores take a 32-bit byte offset inside the output image (GEO 1: inside a pair of images)
-        if ((long)(geo == 0 ? 1 : 2) * a.p[i].H * a.p[i].W * a.y_cs * 4 >= (1L << 32))
-            return fail(CMK_EINVAL, "conv_wino6s: an output image of 4 GiB or more%s", "");
+    if (int rc = w6_refuse_size(a, geo, a.y_cs, "conv_wino6s")) return rc;
     if (geo == 0) return launch_wino6s_geo<0>(a, st);
-    if (a.nprob != 1 || a.p[0].H > 16 || a.p[0].W > 14 || a.gn_ws)
-        return fail(CMK_EINVAL, "conv_wino6s: the RoI-pair geometry takes one problem of maps up to 16x14 and produces no GroupNorm statistics%s", "");
+    if (int rc = w6_refuse_roi_pairs(a, "conv_wino6s: the RoI-pair geometry")) return rc;
     return launch_wino6s_geo<1>(a, st);
 }
 

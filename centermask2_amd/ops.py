@@ -1049,7 +1049,7 @@ def kernel_source_hash() -> str:
     import os
     h = hashlib.sha1()
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    for f in ("conv_args.hpp", "wino6_common.hpp", "conv_igemm.hip", "conv_wino6.hip", "conv_wino6s.hip", "conv_pw.hip", "conv_sp3.hip"):
+    for f in ("conv_args.hpp", "wino6_common.hpp", "conv.hip", "conv_igemm.hip", "conv_wino4r.hip", "conv_wino6.hip", "conv_wino6s.hip", "conv_pw.hip", "conv_sp3.hip"):
         h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:12]
 

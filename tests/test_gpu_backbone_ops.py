@@ -394,7 +394,7 @@ def test_conv_pointwise_upsampled_residual(dev, cmk_lib, case, mt):
 @pytest.mark.parametrize("case", [(1, 1, 37, 12544, 1024, 1, 1, (8, 32, 2, 8)), (1, 1, 400, 1024, 1024, 1, 1, (8, 32, 4, 2)), (6, 14, 14, 256, 256, 3, 2, (9, 32, 2, 4)),
                                   (2, 13, 20, 256, 256, 3, 2, (9, 32, 2, 8)), (2, 9, 11, 64, 320, 3, 1, (9, 32, 4, 2))])
 def test_conv_pointwise_split_k(dev, case):
-    """Split-K on the pointwise kernel (both the 1x1 and the gather form): raw partial sums + conv_igemm's reduce kernel."""
+    """Split-K on the pointwise kernel (both the 1x1 and the gather form): raw partial sums + the reduce kernel of conv.hip."""
     n, h, w, cin, cout, k, stride, tv = case
     x = _rand((n, cin, h, w), 111)
     wt = _rand((cout, cin, k, k), 112, (2.0 / (cin * k * k)) ** 0.5)
@@ -436,7 +436,7 @@ def test_conv_winograd6_variant(dev, case):
 @pytest.mark.parametrize("case", [(2, 25, 40, 768, 224, 4), (1, 50, 80, 512, 192, 2), (2, 13, 41, 64, 33, 2), (1, 12, 40, 128, 256, 8)])
 def test_conv_winograd6_split_k(dev, case):
     """tune_wm 6 with split-K: 2 / 4 / 8 workgroups share the chunk loop of one (spatial tile, cout tile), raw partial sums go to the
-    workspace, conv_igemm's reduce kernel sums them in a fixed order and applies the epilogue — for launches of about one round of
+    workspace, the reduce kernel of conv.hip sums them in a fixed order and applies the epilogue — for launches of about one round of
     workgroups with hundreds of input channels (the first conv of a stage-4 / stage-5 OSA block).  fp32 rounding differences only;
     chunk counts that do not split evenly and the shared-V form are refused."""
     n, h, w, cin, cout, sk = case
