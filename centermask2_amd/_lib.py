@@ -47,6 +47,7 @@ SIGNATURES = {
     "cmk_conv2d_nhwc": (c_int, [POINTER(ConvDesc), c_void_p]),
     "cmk_conv2d_nhwc_multi": (c_int, [POINTER(ConvDesc), c_int, c_void_p]),
     "cmk_conv_resolve": (c_int, [POINTER(ConvDesc), c_int, c_int, POINTER(c_int)]),
+    "cmk_conv_plan": (c_int, [POINTER(ConvDesc), c_int, c_char_p, c_int, POINTER(c_double), POINTER(c_int)]),
     "cmk_conv_pool_rows": (c_int, [POINTER(ConvDesc)]),
     "cmk_ese_gate_pooled": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "cmk_conv_packed_floats": (c_int64, [c_int, c_int, c_int]),

@@ -1,6 +1,7 @@
 // The conv front door of libcmk_hip.so: every extern "C" conv entry point, the validation of descriptors, the choice of a kernel for
-// a launch (resolve), its launch (dispatch, run) and the split-K reduce kernel that finishes the launches of every kernel file that
-// leaves raw partial sums (conv_igemm.hip, conv_wino6.hip, conv_pw.hip).  The kernels live in files of their own (conv_args.hpp).
+// a launch (resolve), its launch or the plan of it (dispatch, run; conv_args.hpp LaunchPlan) and the split-K reduce kernel that finishes
+// the launches of every kernel file that leaves raw partial sums (conv_igemm.hip, conv_wino6.hip, conv_pw.hip).  The kernels live in files
+// of their own (conv_args.hpp).
 #include <algorithm>
 
 #include "conv_args.hpp"
@@ -203,12 +204,15 @@ static void wino6_tail_of(const cmk_conv_desc* d, int& tiles, int& ways) {
     if (pt > 0) { tiles = pt; ways = std::min(d->splitk_tail, pw); }
 }
 
+// The kernels that produce fused GroupNorm statistics: the Winograd forms and the direct fp16-split 3x3
+static bool writes_gn_records(int tune_wm) { return tune_wm == 5 || tune_wm == 6 || tune_wm == 11; }
+
 // The launch of the explicit variant d->tune_wm/sc/wn (d: the first descriptor, resolved).  Returns with a.ksplit > 1 when the kernel left
-// split-K partial sums for run() to reduce.
-static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* descs, int n, hipStream_t st) {
+// split-K partial sums for run() to reduce.  plan: conv_args.hpp LaunchPlan.
+static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* descs, int n, hipStream_t st, LaunchPlan* plan) {
     const int cout32 = (d->Cout + 31) / 32;
-    if (d->gn_ws) {                 // fused GroupNorm statistics: the Winograd forms and the direct fp16-split 3x3 produce them
-        if (d->tune_wm != 5 && d->tune_wm != 6 && d->tune_wm != 11)
+    if (d->gn_ws) {
+        if (!writes_gn_records(d->tune_wm))
             return fail(CMK_EINVAL, "conv: fused GroupNorm statistics are only produced by the Winograd form%s", "");
         int rc = setup_gn(a, d);
         if (rc) return rc;
@@ -218,7 +222,7 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
             return fail(CMK_EINVAL, "conv: Winograd variant not available for this conv%s", "");
         if (d->splitk > 1) return fail(CMK_EINVAL, "conv: split-K is a direct-kernel feature%s", "");
         a.w = d->w_wino;
-        return launch_wino4r(a, st);
+        return launch_wino4r(a, st, plan);
     }
     if (d->tune_wm == 6) {          // Winograd F(4x4,3x3): same conditions, its own packed weights
         if (d->ksize != 3 || d->stride != 1 || d->res_mode != 0 || d->in_relu || !d->w_wino6 || (d->Cin & 7))
@@ -238,11 +242,11 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         }
         if (a.ksplit > 1) {           // F(4x4) with split-K (conv_wino6.hip forms): partial sums + the reduce kernel above
             if (d->tune_sc == 64 || (d->tune_wn != 1 && d->tune_wn != 2) || n != 1) return fail(CMK_EINVAL, "conv: Winograd split-K needs tune_sc 16 or 32, tune_wn 1 or 2, one problem%s", "");
-            return launch_wino6(a, d->tune_wn == 2 ? 1 : 0, pair, st);       // (tune_wn 2: run as the tail that takes every tile)
+            return launch_wino6(a, d->tune_wn == 2 ? 1 : 0, pair, st, plan);       // (tune_wn 2: run as the tail that takes every tile)
         }
         if (d->tune_wn != 1 && d->tune_wn != 2) return fail(CMK_EINVAL, "conv: tune_wm 6 takes tune_wn 1 (12x40 map tiles) or 2 (pairs of RoI maps up to 16x14)%s", "");
-        if (d->tune_sc == 64) return launch_wino6s(a, d->tune_wn == 2 ? 1 : 0, st);      // 64 couts per workgroup, shared frequency image
-        return launch_wino6(a, d->tune_wn == 2 ? 1 : 0, pair, st);
+        if (d->tune_sc == 64) return launch_wino6s(a, d->tune_wn == 2 ? 1 : 0, st, plan);      // 64 couts per workgroup, shared frequency image
+        return launch_wino6(a, d->tune_wn == 2 ? 1 : 0, pair, st, plan);
     }
     a.ksplit = d->splitk > 1 ? d->splitk : 1;
     a.ws = d->splitk_ws;
@@ -252,7 +256,7 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         if (d->ksize != 1 || cout32 <= 7) return fail(CMK_EINVAL, "conv: pointwise variant needs a 1x1 conv with Cout > 224%s", "");
         a.cout_pad = cdiv(cout32, 4) * 128;
         if (a.ksplit > 1 && !pointwise_mt(d, n)) return fail(CMK_EINVAL, "conv: pointwise variant: split-K not available for this conv%s", "");
-        return launch_pw(a, d->tune_wn, st);
+        return launch_pw(a, d->tune_wn, st, plan);
     }
     if (d->tune_wm == 10) {                            // opt-in: the pointwise GEMM from bf16-split products (fp32-accurate, cmk.h w_split)
         if (!(d->ksize == 1 ? pointwise_mt(d, n) : gather_mt(d, n)))
@@ -261,7 +265,7 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         a.w = reinterpret_cast<const float*>(d->w_split);
         a.ksplit = 1;
         a.ga_stride = d->ksize == 3 ? d->stride : 0;
-        return launch_pw_split(a, 1, st);
+        return launch_pw_split(a, 1, st, plan);
     }
     if (d->tune_wm == 12) {                            // opt-in: the same on two fp16 pieces per operand / three products (cmk.h w_splith)
         if (!(d->ksize == 1 ? pointwise_mt(d, n) : gather_mt(d, n)) || !(d->w_splith_scale > 0.f))
@@ -271,7 +275,7 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         a.p[0].acc_scale = d->w_splith_scale;
         a.ksplit = 1;
         a.ga_stride = d->ksize == 3 ? d->stride : 0;
-        return launch_pw_split(a, 2, st);
+        return launch_pw_split(a, 2, st, plan);
     }
     if (d->tune_wm == 11) {                            // opt-in: direct 3x3 conv on bf16-split products (conv_sp3.hip); tune_sc = pieces, tune_wn = geometry
         if (d->ksize != 3 || d->stride != 1 || !d->w_splith || d->splitk > 1 || d->res_mode != 0 || d->in_relu || d->pool_ws)
@@ -283,14 +287,14 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         }
         a.cout_pad = cdiv(cout32, 4) * 128;
         a.ksplit = 1;
-        return launch_sp3(a, d->tune_wn, d->tune_sc, st);
+        return launch_sp3(a, d->tune_wn, d->tune_sc, st, plan);
     }
     if (d->tune_wm == 9) {                             // gather form of a 3x3 conv on the pointwise GEMM kernel; tune_wn = accumulator rows per wave
         const int mt = gather_mt(d, n);
         if (!mt) return fail(CMK_EINVAL, "conv: pointwise gather variant not available for this conv%s", "");
         a.cout_pad = cdiv(cout32, 4) * 128;
         a.ga_stride = d->stride;
-        return launch_pw(a, mt, st);
+        return launch_pw(a, mt, st, plan);
     }
     if (d->tune_wm == 7) {                             // gather form: 3x3 (stride 1|2) as a flattened-pixel GEMM over 9x the K chunks
         if (d->ksize != 3 || n != 1 || d->res_mode == 2 || d->in_scale || (d->tune_wn != 1 && d->tune_wn != 2 && d->tune_wn != 4))
@@ -299,14 +303,16 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         if (cout_pad32 % d->tune_wn) return fail(CMK_EINVAL, "conv: gather variant: Cout tiles %% WN != 0%s", "");
         a.cout_pad = cout_pad32 * 32;
         a.ga_stride = d->stride;
-        return launch_igemm_gather(a, d->tune_wn, cout_pad32 / d->tune_wn, st);
+        return launch_igemm_gather(a, d->tune_wn, cout_pad32 / d->tune_wn, st, plan);
     }
     const Variant v{d->tune_wm, d->tune_sc, d->tune_wn};
     if (!variant_ok(d->ksize * d->ksize, d->stride, cout32, v.wm, v.sc, v.wn)) return fail(CMK_EINVAL, "conv: variant not available for this shape%s", "");
-    return launch_igemm(a, d->ksize, d->stride, cout32, v, st);
+    return launch_igemm(a, d->ksize, d->stride, cout32, v, st, plan);
 }
 
-static int run(const cmk_conv_desc* descs, int n, void* stream) {
+// plan: fill it instead of launching (cmk_conv_plan).  There gn_groups > 0 without a gn_ws asks for the launch as with statistics where the
+// resolved kernel writes them: the workspace is sized by the answer.
+static int run(const cmk_conv_desc* descs, int n, void* stream, LaunchPlan* plan = nullptr) {
     const cmk_conv_desc* d = &descs[0];
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -318,12 +324,15 @@ static int run(const cmk_conv_desc* descs, int n, void* stream) {
     a.res_cs = d->res_cs; a.res_co = d->res_co; a.res_mode = d->res_mode; a.Hr = d->Hr; a.Wr = d->Wr;
     if (a.res_mode == 2 && (a.Hr * 2 < a.p[0].Ho || a.Wr * 2 < a.p[0].Wo)) return fail(CMK_EINVAL, "conv: upsampled residual too small%s", "");
     a.relu_upto = d->relu_upto; a.in_relu = d->in_relu;
-    const Variant v = resolve(descs, n, d->gn_ws != nullptr);
+    const bool ask_gn = plan && !d->gn_ws && d->gn_groups > 0;
+    const Variant v = resolve(descs, n, d->gn_ws != nullptr || ask_gn);
     cmk_conv_desc dv = *d;          // zero tune fields launch exactly as the explicit variant they resolve to
     dv.tune_wm = v.wm; dv.tune_sc = v.sc; dv.tune_wn = v.wn;
+    static double no_ws;            // stands for the workspace in a plan; nothing is launched, so nothing writes through it
+    if (ask_gn && writes_gn_records(v.wm)) dv.gn_ws = &no_ws;
     hipStream_t st = (hipStream_t)stream;
-    int rc = dispatch(a, &dv, descs, n, st);
-    if (rc) return rc;
+    int rc = dispatch(a, &dv, descs, n, st, plan);
+    if (rc || plan) return rc;
     if (a.ksplit <= 1 && a.tail_ksplit > 1 && a.tail_tiles > 0) {
         // tail split-K (conv_wino6, RoI pairs): the images of the tail's tiles are one contiguous range of pixels at the end of y; the
         // slabs hold those images only.  Same fixed-order sum and epilogue as below, over that range.
@@ -356,15 +365,10 @@ extern "C" int64_t cmk_conv_packed_floats(int Cout, int Cin, int ksize) {
 
 extern "C" int cmk_conv_gn_tiles(int H, int W) { return ((H + 7) / 8) * ((W + 15) / 16); }
 
-// {sum, sumsq} records per image that a conv with fused GroupNorm statistics writes: tune_wm 5 -> 2 per 8x16 tile, 6 -> 4 per 12x40 tile,
-// 110 + g (tune_wm 11, geometry g: conv_sp3.hip) -> 2 per 8x32 (g 0) | 1 per 4x32 (1) | 2 per 16x16 (2) | 1 per 8x16 (3) tile
+// {sum, sumsq} records per image that a Winograd conv with fused GroupNorm statistics writes (tune_wm 6: the F(4x4) map kernels, otherwise
+// the F(2x2) kernel), from the kernels' own constants; cmk_conv_plan answers for any launch
 extern "C" int cmk_conv_gn_records(int H, int W, int tune_wm) {
-    if (tune_wm >= 110 && tune_wm <= 113) {
-        const int g = tune_wm - 110;
-        const int th = g == 0 ? 8 : g == 1 ? 4 : g == 2 ? 16 : 8, tw = g < 2 ? 32 : 16;
-        return ((g & 1) ? 1 : 2) * ((H + th - 1) / th) * ((W + tw - 1) / tw);
-    }
-    return tune_wm == 6 ? 4 * ((H + 11) / 12) * ((W + 39) / 40) : 2 * ((H + 7) / 8) * ((W + 15) / 16);
+    return tune_wm == 6 ? cmk::wino6_gn_records(H, W) : cmk::wino4r_gn_records(H, W);
 }
 
 extern "C" int64_t cmk_splith_packed_halves(int Cout, int Cin) {     // per tap: two fp16 pieces per weight (cmk.h w_splith)
@@ -406,6 +410,19 @@ extern "C" int cmk_conv2d_nhwc_multi(const cmk_conv_desc* descs, int n, void* st
     int rc = cmk::validate_multi(descs, n);
     if (rc) return rc;
     return cmk::run(descs, n, stream);
+}
+
+extern "C" int cmk_conv_plan(const cmk_conv_desc* descs, int n, char* kernel, int kernel_cap, double* executed_flops, int* gn_records) {
+    int rc = n == 1 ? cmk::validate(descs) : cmk::validate_multi(descs, n);
+    if (rc) return rc;
+    cmk::LaunchPlan plan;
+    memset(&plan, 0, sizeof(plan));
+    rc = cmk::run(descs, n, nullptr, &plan);
+    if (rc) return rc;
+    if (kernel && kernel_cap > 0) snprintf(kernel, kernel_cap, "%s", plan.kernel);
+    if (executed_flops) *executed_flops = (double)plan.executed_flops;
+    for (int i = 0; gn_records && i < n; ++i) gn_records[i] = plan.gn_records[i];
+    return CMK_OK;
 }
 
 extern "C" int cmk_conv_resolve(const cmk_conv_desc* descs, int n, int with_gn_stats, int variant[3]) {

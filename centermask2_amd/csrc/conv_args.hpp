@@ -63,26 +63,41 @@ struct DeviceOnce {
 
 struct Variant { int wm, sc, wn; };
 
+// What a launch would run, said by the code that picks it (cmk_conv_plan).  Every launch_* below takes a LaunchPlan*: null launches; otherwise
+// all checks and the geometry set-up run as for a launch, and the leaf launcher — the template function that names the kernel — fills the plan
+// next to its hipLaunchKernelGGL and returns before it touches a device.
+struct LaunchPlan {
+    char kernel[96];            // the instantiation as a profiler prints it, minus "void cmk::" and the argument list
+    int64_t executed_flops;     // FLOPs the matrix pipe executes, tile padding included (blocks that only pad the grid to 8 tiles are not); the
+                                // split-product forms in fp32-equivalent FLOPs
+    int gn_records[MAXP];       // per problem: {sum, sumsq} records per image written through gn_ws; 0 = none
+};
+
+inline const char* tf(bool b) { return b ? "true" : "false"; }      // a bool template argument as a demangled name spells it
+constexpr int64_t MFMA_FLOPS = 2 * 32 * 32 * 2;      // one v_mfma_f32_32x32x2_f32
+
 inline int out_size(int h, int stride) { return stride == 1 ? h : (h - 1) / 2 + 1; }     // k3 p1 s2: floor((H+2-3)/2)+1
 
 // conv_igemm.hip: the direct implicit-GEMM kernel, variant v (= WM, SC, WN) of a 1x1 or a 3x3 stride 1 | 2 conv; sets a.cout_pad
-int launch_igemm(ConvArgs& a, int ksize, int stride, int cout32, Variant v, hipStream_t st);
+int launch_igemm(ConvArgs& a, int ksize, int stride, int cout32, Variant v, hipStream_t st, LaunchPlan* plan);
 // conv_igemm.hip: its gather form (cmk.h tune_wm 7), wn = 4 | 2 | 1 cout tiles per wave
-int launch_igemm_gather(ConvArgs& a, int wn, int grid_y, hipStream_t st);
+int launch_igemm_gather(ConvArgs& a, int wn, int grid_y, hipStream_t st, LaunchPlan* plan);
 // conv_igemm.hip: whether the direct kernel has variant (wm, sc, wn) for this conv, and the cost model's choice among those it has
 bool variant_ok(int taps, int stride, int cout32, int wm, int sc, int wn);
 Variant choose_variant(const cmk_conv_desc* descs, int n, int taps, int stride, int cout32);
-// conv_wino4r.hip: fused Winograd F(2x2,3x3)
-int launch_wino4r(ConvArgs& a, hipStream_t st);
+// conv_wino4r.hip: fused Winograd F(2x2,3x3); its {sum, sumsq} records per H x W image (cmk.h gn_ws)
+int launch_wino4r(ConvArgs& a, hipStream_t st, LaunchPlan* plan);
+int wino4r_gn_records(int H, int W);
 // conv_wino6.hip: fused Winograd F(4x4,3x3); pair: the paired form, 64 couts per workgroup from one shared W image (one 8-wave workgroup per CU)
-int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st);
+int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st, LaunchPlan* plan);
+int wino6_gn_records(int H, int W);      // records per H x W image of the three F(4x4) kernels (map tiles; the RoI-pair geometry writes none)
 // conv_wino6s.hip: the same, 64 couts per workgroup from one frequency image shared through LDS (one 8-wave workgroup per CU)
-int launch_wino6s(ConvArgs& a, int geo, hipStream_t st);
+int launch_wino6s(ConvArgs& a, int geo, hipStream_t st, LaunchPlan* plan);
 // conv_pw.hip: 1x1 conv as a GEMM with the weights fetched straight into registers; mt = 4 | 2 accumulator rows per wave
-int launch_pw(ConvArgs& a, int mt, hipStream_t st);
+int launch_pw(ConvArgs& a, int mt, hipStream_t st, LaunchPlan* plan);
 // conv_pw.hip, opt-in: the same GEMM from split products (fp32-accurate; mode 1: three bf16 pieces, a.w = cmk.h w_split; 2: two fp16 pieces, w_splith)
-int launch_pw_split(ConvArgs& a, int mode, hipStream_t st);
+int launch_pw_split(ConvArgs& a, int mode, hipStream_t st, LaunchPlan* plan);
 // conv_sp3.hip, opt-in: 3x3 stride-1 conv as a direct implicit GEMM on fp16-split products (halo tile in LDS, 2 pieces per operand, geo 0..3)
-int launch_sp3(ConvArgs& a, int geo, int pieces, hipStream_t st);
+int launch_sp3(ConvArgs& a, int geo, int pieces, hipStream_t st, LaunchPlan* plan);
 
 }  // namespace cmk

@@ -367,11 +367,11 @@ __global__ __launch_bounds__(256, (occ_of(WM, WN, STRIDE))) void conv_igemm_kern
 // host side: variant menu + cost model
 // ---------------------------------------------------------------------------------------------------------------
 template <int TAPS, int STRIDE, int WM, int WN, int SC, bool GA = false>
-static int launch(ConvArgs& a, int grid_y, hipStream_t st) {
+static int launch(ConvArgs& a, int grid_y, hipStream_t st, LaunchPlan* plan) {
     using G = Geo<TAPS, STRIDE, WM, WN, SC>;
     static DeviceOnce once;      // one per template instantiation
     auto kern = conv_igemm_kernel<TAPS, STRIDE, WM, WN, SC, GA>;
-    int rc0 = once.run([kern]() {
+    int rc0 = plan ? CMK_OK : once.run([kern]() {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
         return e == hipSuccess ? CMK_OK : fail(CMK_ELAUNCH, "conv: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     });
@@ -395,6 +395,11 @@ static int launch(ConvArgs& a, int grid_y, hipStream_t st) {
     const int vchunks = (GA ? 9 : 1) * (a.Cin >> 4);
     if (a.ksplit > 1 && (a.nprob != 1 || a.res_mode == 2 || !a.ws || vchunks % (2 * a.ksplit)))
         return fail(CMK_EINVAL, "conv: split-K needs one problem, a workspace, no upsampled residual and K chunks %% (2*splitk) == 0%s", "");
+    if (plan) {      // every block: BM pixels x BN couts over K = taps x Cin (the gather form walks the 9 taps as K chunks)
+        snprintf(plan->kernel, sizeof(plan->kernel), "conv_igemm_kernel<%d, %d, %d, %d, %d, %s>", TAPS, STRIDE, WM, WN, SC, tf(GA));
+        plan->executed_flops = 2 * (int64_t)blocks * G::BM * grid_y * G::BN * (GA ? 9 : TAPS) * a.Cin;
+        return CMK_OK;
+    }
     hipLaunchKernelGGL(kern, dim3(((blocks + 7) / 8) * 8 * grid_y, a.ksplit), dim3(256), G::LDS_BYTES, st, a);
     return check_launch("conv_igemm");     // split-K: run() reduces the partial sums
 }
@@ -454,46 +459,46 @@ Variant choose_variant(const cmk_conv_desc* descs, int n, int taps, int stride, 
 }
 
 template <int TAPS, int STRIDE, int WN>
-static int dispatch_variant(ConvArgs& a, int grid_y, Variant v, hipStream_t st) {
+static int dispatch_variant(ConvArgs& a, int grid_y, Variant v, hipStream_t st, LaunchPlan* plan) {
     if constexpr (TAPS == 1) {
-        if constexpr (WN <= 4) { if (v.wm == 2) return launch<1, 1, 2, WN, 32>(a, grid_y, st); }
-        return launch<1, 1, 1, WN, 32>(a, grid_y, st);
+        if constexpr (WN <= 4) { if (v.wm == 2) return launch<1, 1, 2, WN, 32>(a, grid_y, st, plan); }
+        return launch<1, 1, 1, WN, 32>(a, grid_y, st, plan);
     } else if constexpr (STRIDE == 2) {
-        return launch<9, 2, 1, WN, 16>(a, grid_y, st);
+        return launch<9, 2, 1, WN, 16>(a, grid_y, st, plan);
     } else {
         if constexpr (WN <= 4) {
-            if (v.wm == 2) return v.sc == 16 ? launch<9, 1, 2, WN, 16>(a, grid_y, st) : launch<9, 1, 2, WN, 32>(a, grid_y, st);
+            if (v.wm == 2) return v.sc == 16 ? launch<9, 1, 2, WN, 16>(a, grid_y, st, plan) : launch<9, 1, 2, WN, 32>(a, grid_y, st, plan);
         }
-        return v.sc == 16 ? launch<9, 1, 1, WN, 16>(a, grid_y, st) : launch<9, 1, 1, WN, 32>(a, grid_y, st);
+        return v.sc == 16 ? launch<9, 1, 1, WN, 16>(a, grid_y, st, plan) : launch<9, 1, 1, WN, 32>(a, grid_y, st, plan);
     }
 }
 
 template <int TAPS, int STRIDE>
-static int dispatch_wn(ConvArgs& a, int cout32, Variant v, hipStream_t st) {
+static int dispatch_wn(ConvArgs& a, int cout32, Variant v, hipStream_t st, LaunchPlan* plan) {
     const int cout_pad32 = cout32 <= 7 ? cout32 : cdiv(cout32, 4) * 4;
     a.cout_pad = cout_pad32 * 32;
     const int grid_y = cout_pad32 / v.wn;
     switch (v.wn) {
-        case 1: return dispatch_variant<TAPS, STRIDE, 1>(a, grid_y, v, st);
-        case 2: return dispatch_variant<TAPS, STRIDE, 2>(a, grid_y, v, st);
-        case 3: return dispatch_variant<TAPS, STRIDE, 3>(a, grid_y, v, st);
-        case 4: return dispatch_variant<TAPS, STRIDE, 4>(a, grid_y, v, st);
-        case 5: return dispatch_variant<TAPS, STRIDE, 5>(a, grid_y, v, st);
-        case 6: return dispatch_variant<TAPS, STRIDE, 6>(a, grid_y, v, st);
-        case 7: return dispatch_variant<TAPS, STRIDE, 7>(a, grid_y, v, st);
+        case 1: return dispatch_variant<TAPS, STRIDE, 1>(a, grid_y, v, st, plan);
+        case 2: return dispatch_variant<TAPS, STRIDE, 2>(a, grid_y, v, st, plan);
+        case 3: return dispatch_variant<TAPS, STRIDE, 3>(a, grid_y, v, st, plan);
+        case 4: return dispatch_variant<TAPS, STRIDE, 4>(a, grid_y, v, st, plan);
+        case 5: return dispatch_variant<TAPS, STRIDE, 5>(a, grid_y, v, st, plan);
+        case 6: return dispatch_variant<TAPS, STRIDE, 6>(a, grid_y, v, st, plan);
+        case 7: return dispatch_variant<TAPS, STRIDE, 7>(a, grid_y, v, st, plan);
     }
     return fail(CMK_EINVAL, "conv: bad WN%s", "");
 }
 
-int launch_igemm(ConvArgs& a, int ksize, int stride, int cout32, Variant v, hipStream_t st) {
-    if (ksize == 1) return dispatch_wn<1, 1>(a, cout32, v, st);
-    if (stride == 1) return dispatch_wn<9, 1>(a, cout32, v, st);
-    return dispatch_wn<9, 2>(a, cout32, v, st);
+int launch_igemm(ConvArgs& a, int ksize, int stride, int cout32, Variant v, hipStream_t st, LaunchPlan* plan) {
+    if (ksize == 1) return dispatch_wn<1, 1>(a, cout32, v, st, plan);
+    if (stride == 1) return dispatch_wn<9, 1>(a, cout32, v, st, plan);
+    return dispatch_wn<9, 2>(a, cout32, v, st, plan);
 }
 
-int launch_igemm_gather(ConvArgs& a, int wn, int grid_y, hipStream_t st) {
-    return wn == 4 ? launch<1, 1, 1, 4, 32, true>(a, grid_y, st) : wn == 2 ? launch<1, 1, 1, 2, 32, true>(a, grid_y, st)
-                                                                        : launch<1, 1, 1, 1, 32, true>(a, grid_y, st);
+int launch_igemm_gather(ConvArgs& a, int wn, int grid_y, hipStream_t st, LaunchPlan* plan) {
+    return wn == 4 ? launch<1, 1, 1, 4, 32, true>(a, grid_y, st, plan) : wn == 2 ? launch<1, 1, 1, 2, 32, true>(a, grid_y, st, plan)
+                                                                        : launch<1, 1, 1, 1, 32, true>(a, grid_y, st, plan);
 }
 
 }  // namespace cmk

@@ -613,7 +613,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
 }
 
 template <int MT, bool POOL, bool GA, bool UPRES = false, bool SPLITK = false, int SPLIT = 0>
-static int launch_pw_mt(ConvArgs& a, hipStream_t st) {
+static int launch_pw_mt(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     constexpr int BM = 64 * MT;
     constexpr int LDS_BYTES = SPLIT == 2 && !GA ? 2 * (BM / 32) * 4 * 64 * 16 : SPLIT ? 2 * (BM / 32) * (SPLIT == 2 ? 2 : 3) * 64 * 16 : 2 * BM * PST * 4;       // 40 KB (MT 4) / 20 KB (MT 2) / 48 | 32 KB (split): under the 64 KB a kernel gets without an attribute
     ConvProblem& p = a.p[0];
@@ -622,13 +622,18 @@ static int launch_pw_mt(ConvArgs& a, hipStream_t st) {
     const long tiles = (p.total_pix + BM - 1) / BM;
     a.total_tiles = (int)tiles;
     a.grid_y = a.cout_pad / 128;
+    if (plan) {      // a workgroup: BM pixels x 128 couts over K = Cin (gather form: 9 taps x Cin); the split forms in fp32-equivalent FLOPs
+        snprintf(plan->kernel, sizeof(plan->kernel), "conv_pw_kernel<%d, %s, %s, %s, %s, %d>", MT, tf(POOL), tf(GA), tf(UPRES), tf(SPLITK), SPLIT);
+        plan->executed_flops = 2 * tiles * BM * a.grid_y * 128 * (GA ? 9 : 1) * a.Cin;
+        return CMK_OK;
+    }
     hipLaunchKernelGGL((conv_pw_kernel<MT, POOL, GA, UPRES, SPLITK, SPLIT>), dim3((unsigned)(((tiles + 7) / 8) * 8 * a.grid_y), SPLITK ? a.ksplit : 1), dim3(256), LDS_BYTES, st, a);
     return check_launch("conv_pw");
 }
 
 // mt = 4 | 2.  The caller (conv.hip: run) has filled the problem, views, epilogue options and cout_pad; a.ga_stride = 1 | 2 asks for
 // the gather form of a 3x3 conv (a.w then is conv_igemm's 9-tap packing), 0 for a 1x1 conv.
-int launch_pw(ConvArgs& a, int mt, hipStream_t st) {
+int launch_pw(ConvArgs& a, int mt, hipStream_t st, LaunchPlan* plan) {
     const ConvProblem& p = a.p[0];
     if (a.nprob != 1 || p.in_scale || a.in_relu || a.gn_ws)
         return fail(CMK_EINVAL, "conv_pw: one problem, no input affine / input ReLU / GroupNorm statistics%s", "");
@@ -636,9 +641,9 @@ int launch_pw(ConvArgs& a, int mt, hipStream_t st) {
         const int nch = (a.ga_stride ? 9 : 1) * (a.Cin >> 4);
         if (!a.ws || a.res_mode == 2 || a.pool_ws || nch % (2 * a.ksplit))
             return fail(CMK_EINVAL, "conv_pw: split-K needs a workspace, K chunks %% (2*splitk) == 0, no upsampled residual / pooled sums%s", "");
-        if (a.ga_stride) return mt == 4 ? launch_pw_mt<4, false, true, false, true>(a, st) : mt == 2 ? launch_pw_mt<2, false, true, false, true>(a, st)
+        if (a.ga_stride) return mt == 4 ? launch_pw_mt<4, false, true, false, true>(a, st, plan) : mt == 2 ? launch_pw_mt<2, false, true, false, true>(a, st, plan)
                                                                                                       : fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
-        return mt == 4 ? launch_pw_mt<4, false, false, false, true>(a, st) : mt == 2 ? launch_pw_mt<2, false, false, false, true>(a, st)
+        return mt == 4 ? launch_pw_mt<4, false, false, false, true>(a, st, plan) : mt == 2 ? launch_pw_mt<2, false, false, false, true>(a, st, plan)
                                                                                      : fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
     }
     if (a.res_mode == 2) {          // FPN top-down add
@@ -651,25 +656,25 @@ int launch_pw(ConvArgs& a, int mt, hipStream_t st) {
     if ((long)(64 * 4 + 8) * a.y_cs >= (1L << 30) || (long)(64 * 4 + 8) * a.res_cs >= (1L << 30)) return fail(CMK_EINVAL, "conv_pw: output row too wide%s", "");
     if (a.ga_stride) {
         if (a.pool_ws || p.H >= 32768 || p.W >= 32768) return fail(CMK_EINVAL, "conv_pw: gather form: no pooled sums, maps below 32768 x 32768%s", "");
-        if (mt == 4) return launch_pw_mt<4, false, true>(a, st);
-        if (mt == 2) return launch_pw_mt<2, false, true>(a, st);
+        if (mt == 4) return launch_pw_mt<4, false, true>(a, st, plan);
+        if (mt == 2) return launch_pw_mt<2, false, true>(a, st, plan);
         return fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
     }
     if (a.pool_ws && (long)p.Ho * p.Wo < 32 * mt) return fail(CMK_EINVAL, "conv_pw: pooled sums need H*W >= the block of %s%ld rows", "", 32 * mt);
     if (a.res_mode == 2) {
-        if (mt == 4) return launch_pw_mt<4, false, false, true>(a, st);
-        if (mt == 2) return launch_pw_mt<2, false, false, true>(a, st);
+        if (mt == 4) return launch_pw_mt<4, false, false, true>(a, st, plan);
+        if (mt == 2) return launch_pw_mt<2, false, false, true>(a, st, plan);
         return fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
     }
-    if (mt == 4) return a.pool_ws ? launch_pw_mt<4, true, false>(a, st) : launch_pw_mt<4, false, false>(a, st);
-    if (mt == 2) return a.pool_ws ? launch_pw_mt<2, true, false>(a, st) : launch_pw_mt<2, false, false>(a, st);
+    if (mt == 4) return a.pool_ws ? launch_pw_mt<4, true, false>(a, st, plan) : launch_pw_mt<4, false, false>(a, st, plan);
+    if (mt == 2) return a.pool_ws ? launch_pw_mt<2, true, false>(a, st, plan) : launch_pw_mt<2, false, false>(a, st, plan);
     return fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
 }
 
 // The split forms (cmk.h tune_wm 10: three bf16 pieces, six products; 12: two fp16 pieces, three products): a.w is the split packing; plain 1x1
 // conv, optionally with the pooled sums / the upsampled residual, or a 3x3 conv in the gather form.
 template <int SPLIT>
-static int launch_pw_split_mode(ConvArgs& a, hipStream_t st) {
+static int launch_pw_split_mode(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     const ConvProblem& p = a.p[0];
     if (a.nprob != 1 || p.in_scale || a.in_relu || a.gn_ws || a.ksplit > 1 || a.res_mode == 1)
         return fail(CMK_EINVAL, "conv_pw (split): one problem, no input affine / input ReLU / GroupNorm statistics / split-K / same-size residual%s", "");
@@ -679,20 +684,20 @@ static int launch_pw_split_mode(ConvArgs& a, hipStream_t st) {
     if ((long)(64 * 4 + 8) * a.y_cs >= (1L << 30) || (long)(64 * 4 + 8) * a.res_cs >= (1L << 30)) return fail(CMK_EINVAL, "conv_pw (split): output row too wide%s", "");
     if (a.ga_stride) {              // 3x3 conv (stride 1 | 2) as the gather GEMM over 9 taps
         if (a.pool_ws || a.res_mode || p.H >= 32768 || p.W >= 32768) return fail(CMK_EINVAL, "conv_pw (split): gather form: no pooled sums / residual, maps below 32768 x 32768%s", "");
-        return launch_pw_mt<4, false, true, false, false, SPLIT>(a, st);
+        return launch_pw_mt<4, false, true, false, false, SPLIT>(a, st, plan);
     }
     if (a.res_mode == 2) {          // FPN top-down add in the epilogue
         if (a.pool_ws || (p.Wo & 1) || (long)p.N * a.Hr * a.Wr * a.res_cs * 4 >= (1L << 31))
             return fail(CMK_EINVAL, "conv_pw (split): the upsampled residual needs an even output width, no pooled sums, a residual below 2 GiB%s", "");
-        return launch_pw_mt<4, false, false, true, false, SPLIT>(a, st);
+        return launch_pw_mt<4, false, false, true, false, SPLIT>(a, st, plan);
     }
     if (a.pool_ws && (long)p.Ho * p.Wo < 128) return fail(CMK_EINVAL, "conv_pw (split): pooled sums need H*W >= 128%s", "");
-    return a.pool_ws ? launch_pw_mt<4, true, false, false, false, SPLIT>(a, st) : launch_pw_mt<4, false, false, false, false, SPLIT>(a, st);
+    return a.pool_ws ? launch_pw_mt<4, true, false, false, false, SPLIT>(a, st, plan) : launch_pw_mt<4, false, false, false, false, SPLIT>(a, st, plan);
 }
 
-int launch_pw_split(ConvArgs& a, int mode, hipStream_t st) {
+int launch_pw_split(ConvArgs& a, int mode, hipStream_t st, LaunchPlan* plan) {
     if (mode == 2 && !(a.p[0].acc_scale > 0.f)) return fail(CMK_EINVAL, "conv_pw (split): w_splith_scale missing%s", "");
-    return mode == 2 ? launch_pw_split_mode<2>(a, st) : launch_pw_split_mode<1>(a, st);
+    return mode == 2 ? launch_pw_split_mode<2>(a, st, plan) : launch_pw_split_mode<1>(a, st, plan);
 }
 
 }  // namespace cmk

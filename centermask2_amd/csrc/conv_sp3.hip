@@ -62,6 +62,7 @@ struct SP3L {
     static constexpr int ITEMS = HR * HC * 4;                       // float4 loads per chunk
     static constexpr int IT = (ITEMS + 255) / 256;
     static constexpr int LDS_BYTES = 2 * STAGE;
+    static constexpr int WROWS = 4 / G::WCOLS;                      // wave rows; fused GroupNorm statistics: one record per (tile, wave row, group)
 };
 
 template <int GEO, int NB, int P, bool AFF>
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     typedef SP3L<GEO, P> L;
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    constexpr int WROWS = 4 / G::WCOLS;
+    constexpr int WROWS = L::WROWS;
     constexpr int IT = L::IT;
     static_assert((IT - 1) * 256 < L::ITEMS && IT <= 8, "only a thread's last staging item may fall outside the halo; the requests are spread over 8 slots");
     extern __shared__ __attribute__((aligned(16))) unsigned char sb[];
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     float* yimg = Pb.y + (long)n * H * W * a.y_cs + a.y_co;
     const bool interior = oy0 + L::TH <= H && ox0 + L::TW <= W && (cb0 + NB) * 32 <= a.Cout;
     // fused GroupNorm statistics of the NEXT layer's normalisation (fcos.py:182-186): one {sum, sumsq} record per (spatial tile, pixel row of
-    // waves), every group of it written by the wave that owns those couts (cmk_conv_gn_records: WROWS records per tile)
+    // waves), every group of it written by the wave that owns those couts (WROWS records per tile: gn_records of cmk_conv_plan)
     const bool want_stats = a.gn_ws != nullptr;
     const float acc_scale = Pb.acc_scale * (1.f / SX);          // 1 / (S_x * S_w)
     auto put_stats = [&](int co, bool cvalid, float gs, float gss) {
@@ -390,10 +391,10 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
 }
 
 template <int GEO, int NB, int P>
-static int launch_sp3_geo(ConvArgs& a, hipStream_t st) {
+static int launch_sp3_geo(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     typedef SP3L<GEO, P> L;
     static DeviceOnce once;
-    int rc = once.run([]() {
+    int rc = plan ? CMK_OK : once.run([]() {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sp3_kernel<GEO, NB, P, false>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_BYTES);
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sp3_kernel<GEO, NB, P, true>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_BYTES);
@@ -410,6 +411,12 @@ static int launch_sp3_geo(ConvArgs& a, hipStream_t st) {
     }
     a.total_tiles = blocks;
     a.grid_y = cdiv(a.Cout, 32 * NB * SP3G<GEO>::WCOLS);
+    if (plan) {      // a workgroup: TH x TW pixels x 32 * NB * WCOLS couts over K = 9 taps x Cin, in fp32-equivalent FLOPs
+        snprintf(plan->kernel, sizeof(plan->kernel), "conv_sp3_kernel<%d, %d, %d, %s>", GEO, NB, P, tf(a.p[0].in_scale));
+        plan->executed_flops = 2 * (int64_t)blocks * L::TH * L::TW * a.grid_y * (32 * NB * SP3G<GEO>::WCOLS) * 9 * a.Cin;
+        for (int i = 0; i < a.nprob; ++i) plan->gn_records[i] = a.gn_ws ? L::WROWS * a.p[i].tiles_h * a.p[i].tiles_w : 0;
+        return CMK_OK;
+    }
     const dim3 grid(((blocks + 7) / 8) * 8 * a.grid_y);
     if (a.p[0].in_scale)
         hipLaunchKernelGGL((conv_sp3_kernel<GEO, NB, P, true>), grid, dim3(256), L::LDS_BYTES, st, a);
@@ -419,7 +426,7 @@ static int launch_sp3_geo(ConvArgs& a, hipStream_t st) {
 }
 
 // geo 0..3 (above), pieces = 2.  p[i].w = the fp16 split packing (tap-major), p[i].acc_scale = 1 / S_w, a.cout_pad = the packing's padded Cout (a multiple of 128).
-int launch_sp3(ConvArgs& a, int geo, int pieces, hipStream_t st) {
+int launch_sp3(ConvArgs& a, int geo, int pieces, hipStream_t st, LaunchPlan* plan) {
     if ((a.Cin & 15) || a.cout_pad % 128 || a.cout_pad < a.Cout || a.ksplit > 1 || a.res_mode != 0 || a.in_relu ||
         9L * (a.Cin >> 4) * (a.cout_pad >> 5) * 2 * 1024 >= (1L << 31))
         return fail(CMK_EINVAL, "conv_sp3: needs Cin %% 16 == 0, no split-K / residual, split weights below 2 GiB%s", "");
@@ -435,10 +442,10 @@ int launch_sp3(ConvArgs& a, int geo, int pieces, hipStream_t st) {
         return fail(CMK_EINVAL, "conv_sp3: tune_sc must be 2 (two pieces per operand) or 21 (the same, one cout tile per wave)%s", "");
     const bool nb1 = pieces == 21 || (geo == 0 && a.Cout <= 64);
     switch (geo) {
-        case 0: return nb1 ? launch_sp3_geo<0, 1, 2>(a, st) : launch_sp3_geo<0, 2, 2>(a, st);
-        case 1: return nb1 ? launch_sp3_geo<1, 1, 2>(a, st) : launch_sp3_geo<1, 2, 2>(a, st);
-        case 2: return nb1 ? launch_sp3_geo<2, 1, 2>(a, st) : launch_sp3_geo<2, 2, 2>(a, st);
-        case 3: return nb1 ? launch_sp3_geo<3, 1, 2>(a, st) : launch_sp3_geo<3, 2, 2>(a, st);
+        case 0: return nb1 ? launch_sp3_geo<0, 1, 2>(a, st, plan) : launch_sp3_geo<0, 2, 2>(a, st, plan);
+        case 1: return nb1 ? launch_sp3_geo<1, 1, 2>(a, st, plan) : launch_sp3_geo<1, 2, 2>(a, st, plan);
+        case 2: return nb1 ? launch_sp3_geo<2, 1, 2>(a, st, plan) : launch_sp3_geo<2, 2, 2>(a, st, plan);
+        case 3: return nb1 ? launch_sp3_geo<3, 1, 2>(a, st, plan) : launch_sp3_geo<3, 2, 2>(a, st, plan);
     }
     return fail(CMK_EINVAL, "conv_sp3: geometry 0..3%s", "");
 }

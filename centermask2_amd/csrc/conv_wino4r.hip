@@ -23,6 +23,8 @@ namespace cmk {
 // cmk_conv_desc.w_wino); the LDS that a weight buffer would take holds a second V buffer, so the input transform of chunk c+1
 // overlaps the MFMAs of chunk c with two barriers per chunk, none of which waits for memory.
 // ---------------------------------------------------------------------------------------------------------------
+constexpr int R_TH = 8, R_TW = 16;                 // outputs of a workgroup's spatial tile
+constexpr int R_GN_RECS = 2;                       // fused GroupNorm statistics: one record per (tile, row parity fh, group)
 constexpr int S_HALO = 10 * 18;
 constexpr int S_SH = S_HALO * PST;                 // floats
 constexpr int S_SV = 16 * 32 * 16;
@@ -305,16 +307,18 @@ __global__ __launch_bounds__(256, 2) void conv_wino4r_kernel(const ConvArgs a) {
         gs += __shfl_xor(gs, 32);
         gss += __shfl_xor(gss, 32);
         if (cvalid && hh == 0 && (li & (a.gn_cpg - 1)) == 0) {
-            double* o = a.gn_ws + (((long)bx * 2 + fh) * a.gn_groups + co / a.gn_cpg) * 2;
+            double* o = a.gn_ws + (((long)bx * R_GN_RECS + fh) * a.gn_groups + co / a.gn_cpg) * 2;
             o[0] = (double)gs;
             o[1] = (double)gss;
         }
     }
 }
 
-int launch_wino4r(ConvArgs& a, hipStream_t st) {
+int wino4r_gn_records(int H, int W) { return R_GN_RECS * cdiv(H, R_TH) * cdiv(W, R_TW); }
+
+int launch_wino4r(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     static DeviceOnce once;
-    int rc0 = once.run([]() {
+    int rc0 = plan ? CMK_OK : once.run([]() {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4r_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, R_LDS_BYTES);
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4r_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, R_LDS_BYTES);
@@ -325,12 +329,18 @@ int launch_wino4r(ConvArgs& a, hipStream_t st) {
     for (int i = 0; i < a.nprob; ++i) {
         ConvProblem& p = a.p[i];
         p.tile_begin = blocks;
-        p.tiles_h = cdiv(p.Ho, 8);
-        p.tiles_w = cdiv(p.Wo, 16);
+        p.tiles_h = cdiv(p.Ho, R_TH);
+        p.tiles_w = cdiv(p.Wo, R_TW);
         blocks += p.N * p.tiles_h * p.tiles_w;
     }
     a.grid_y = cdiv(a.Cout, 64);
     a.total_tiles = blocks;
+    if (plan) {      // a workgroup: 16 frequency GEMMs of 32 tiles (2x2 outputs each) x 64 couts over Cin
+        snprintf(plan->kernel, sizeof(plan->kernel), "conv_wino4r_kernel<%s>", tf(a.p[0].in_scale));
+        plan->executed_flops = 2 * (int64_t)blocks * a.grid_y * 16 * (R_TH * R_TW / 4) * 64 * a.Cin;
+        for (int i = 0; i < a.nprob; ++i) plan->gn_records[i] = a.gn_ws ? wino4r_gn_records(a.p[i].Ho, a.p[i].Wo) : 0;
+        return CMK_OK;
+    }
     const dim3 grid(((blocks + 7) / 8) * 8 * a.grid_y);
     if (a.p[0].in_scale)          // all problems of a launch agree on this (validated)
         hipLaunchKernelGGL(conv_wino4r_kernel<true>, grid, dim3(256), R_LDS_BYTES, st, a);

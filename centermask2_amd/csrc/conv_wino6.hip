@@ -383,12 +383,12 @@ __global__ __launch_bounds__(512, 2) void conv_wino6p_kernel(const ConvArgs a) {
 }
 
 template <int GEO, bool PAIR>
-static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
+static int launch_wino6_geo(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     static DeviceOnce once;
     const auto k_plain = PAIR ? conv_wino6p_kernel<false, GEO> : conv_wino6_kernel<false, GEO>;
     const auto k_aff = PAIR ? conv_wino6p_kernel<true, GEO> : conv_wino6_kernel<true, GEO>;
     constexpr int lds = w6_lds_bytes<GEO, PAIR>();
-    int rc = once.run([&]() {
+    int rc = plan ? CMK_OK : once.run([&]() {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_aff), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -406,6 +406,8 @@ static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
     if (GEO == 0 || a.tail_ksplit <= 1 || a.tail_tiles <= 0) a.tail_tiles = a.tail_ksplit = 0;
     if (a.tail_tiles > blocks) a.tail_tiles = blocks;
     a.main_blocks = ((blocks - a.tail_tiles + 7) / 8) * 8 * gy;
+    // (the paired form runs two cout tiles per workgroup, the idle half of an odd last pair on the last tile's weights)
+    if (plan) return w6_plan<GEO>(plan, a, PAIR ? "conv_wino6p_kernel" : "conv_wino6_kernel", blocks, PAIR ? 2 * gy : a.grid_y);
     const dim3 grid(a.main_blocks + ((a.tail_tiles + 7) / 8) * 8 * gy * a.tail_ksplit, a.ksplit);
     if constexpr (PAIR) {
         if (a.p[0].in_scale) hipLaunchKernelGGL((conv_wino6p_kernel<true, GEO>), grid, dim3(512), lds, st, a);
@@ -419,7 +421,9 @@ static int launch_wino6_geo(ConvArgs& a, hipStream_t st) {
 
 // geo 0: 12x40-pixel tiles of one image; geo 1: pairs of whole maps of at most 16 rows x 14 columns (one problem, no fused GN statistics);
 // pair: the paired form (64 couts per workgroup)
-int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st) {
+int wino6_gn_records(int H, int W) { return W6_GN_RECS * cdiv(H, W6G<0>::OH) * cdiv(W, W6G<0>::OW); }
+
+int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st, LaunchPlan* plan) {
     // (a split-K or tail workgroup stores with pixel stride cout_pad)
     if (int rc = w6_refuse_size(a, geo, std::max(a.y_cs, a.cout_pad), "conv_wino6")) return rc;
     // split-K of the map geometry keeps its even-split rule; the RoI-pair geometry gives every piece whole chunk pairs (w6_piece_bounds), so
@@ -432,9 +436,9 @@ int launch_wino6(ConvArgs& a, int geo, bool pair, hipStream_t st) {
         if (a.ksplit > 1 || a.nprob != 1 || a.gn_ws || !a.ws || a.tail_ksplit > (a.Cin >> 4) || a.cout_pad < cdiv(a.Cout, 32) * 32)
             return fail(CMK_EINVAL, "conv_wino6: tail split-K takes one problem, no GroupNorm statistics, no split-K beside it, a workspace and at most Cin / 16 ways%s", "");
     }
-    if (geo == 0) return pair ? launch_wino6_geo<0, true>(a, st) : launch_wino6_geo<0, false>(a, st);
+    if (geo == 0) return pair ? launch_wino6_geo<0, true>(a, st, plan) : launch_wino6_geo<0, false>(a, st, plan);
     if (int rc = w6_refuse_roi_pairs(a, "conv_wino6: the RoI-pair geometry (with split-K or a split-K tail as without)")) return rc;
-    return pair ? launch_wino6_geo<1, true>(a, st) : launch_wino6_geo<1, false>(a, st);
+    return pair ? launch_wino6_geo<1, true>(a, st, plan) : launch_wino6_geo<1, false>(a, st, plan);
 }
 
 }  // namespace cmk

@@ -376,9 +376,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
 }
 
 template <int GEO>
-static int launch_wino6s_geo(ConvArgs& a, hipStream_t st) {
+static int launch_wino6s_geo(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     static DeviceOnce once;
-    int rc = once.run([]() {
+    int rc = plan ? CMK_OK : once.run([]() {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6s_kernel<false, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, W6S<GEO>::LDS_BYTES);
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino6s_kernel<true, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, W6S<GEO>::LDS_BYTES);
@@ -389,6 +389,8 @@ static int launch_wino6s_geo(ConvArgs& a, hipStream_t st) {
     a.grid_y = cdiv(cdiv(a.Cout, 32), 2);
     a.total_tiles = blocks;
     if (a.ksplit > 1) return fail(CMK_EINVAL, "conv_wino6s: split-K is a feature of the 32-cout form (tune_sc 16)%s", "");
+    // (a wave group without a cout tile, the second of an odd last pair, issues no MFMAs)
+    if (plan) return w6_plan<GEO>(plan, a, "conv_wino6s_kernel", blocks, cdiv(a.Cout, 32));
     const dim3 grid(((blocks + 7) / 8) * 8 * a.grid_y);
     if (a.p[0].in_scale)
         hipLaunchKernelGGL((conv_wino6s_kernel<true, GEO>), grid, dim3(512), W6S<GEO>::LDS_BYTES, st, a);
@@ -398,11 +400,11 @@ static int launch_wino6s_geo(ConvArgs& a, hipStream_t st) {
 }
 
 // geo 0: 12x40-pixel tiles of one image; geo 1: pairs of whole maps of at most 16 rows x 14 columns (one problem, no fused GN statistics)
-int launch_wino6s(ConvArgs& a, int geo, hipStream_t st) {
+int launch_wino6s(ConvArgs& a, int geo, hipStream_t st, LaunchPlan* plan) {
     if (int rc = w6_refuse_size(a, geo, a.y_cs, "conv_wino6s")) return rc;
-    if (geo == 0) return launch_wino6s_geo<0>(a, st);
+    if (geo == 0) return launch_wino6s_geo<0>(a, st, plan);
     if (int rc = w6_refuse_roi_pairs(a, "conv_wino6s: the RoI-pair geometry")) return rc;
-    return launch_wino6s_geo<1>(a, st);
+    return launch_wino6s_geo<1>(a, st, plan);
 }
 
 }  // namespace cmk

@@ -48,6 +48,9 @@ template <> struct W6G<1> {
     }
 };
 static_assert(W6G<0>::TP % 16 == 10 && W6G<1>::TP % 16 == 4, "conflict-free W image");
+constexpr int W6_GN_RECS = 4;      // fused GroupNorm statistics: one record per (spatial tile, wave g of the cout tile, group)
+// a wave-group's work on one spatial tile, one 32-cout tile and one channel: 36 frequency GEMMs of 32 tiles (4x4 outputs each) x 32 couts
+constexpr int64_t W6_FLOPS_PER_CHANNEL = 2 * 36 * 32 * 32;
 
 template <int GEO>
 __device__ __forceinline__ int w6_slot(int q, int r, int a, int col) {
@@ -297,7 +300,7 @@ __device__ __forceinline__ void w6_epilogue(const ConvArgs& a, const ConvProblem
         gs += __shfl_xor(gs, 32);
         gss += __shfl_xor(gss, 32);
         if (cvalid && hh == 0 && (li & (a.gn_cpg - 1)) == 0) {
-            double* o = a.gn_ws + (((long)bx * 4 + g) * a.gn_groups + co / a.gn_cpg) * 2;
+            double* o = a.gn_ws + (((long)bx * W6_GN_RECS + g) * a.gn_groups + co / a.gn_cpg) * 2;
             o[0] = (double)gs;
             o[1] = (double)gss;
         }
@@ -323,6 +326,16 @@ inline int w6_assign_tiles(ConvArgs& a) {
         }
     }
     return blocks;
+}
+
+// What the leaf launchers of the three kernels leave in a plan (conv_args.hpp) for `blocks` spatial tiles x `cout_tiles` executed 32-cout
+// tiles; records: the map geometry's, where the launch writes statistics (the RoI-pair geometry refuses them).
+template <int GEO>
+inline int w6_plan(LaunchPlan* plan, const ConvArgs& a, const char* kernel, int blocks, int cout_tiles) {
+    snprintf(plan->kernel, sizeof(plan->kernel), "%s<%s, %d>", kernel, tf(a.p[0].in_scale), GEO);
+    plan->executed_flops = (int64_t)blocks * cout_tiles * a.Cin * W6_FLOPS_PER_CHANNEL;
+    for (int i = 0; i < a.nprob; ++i) plan->gn_records[i] = a.gn_ws && GEO == 0 ? W6_GN_RECS * a.p[i].tiles_h * a.p[i].tiles_w : 0;
+    return CMK_OK;
 }
 
 // What kernel `name` refuses.  The epilogue's stores take a 32-bit byte offset inside the output image (geo 1: inside a pair of images)

@@ -494,11 +494,20 @@ def _problem_key(descs, n):
             tuple((descs[i].N, descs[i].H, descs[i].W) for i in range(n)))
 
 
-def _launch(descs, n, tv, ws, xs, ys, pcs, single=False, what="cmk_conv2d_nhwc_multi", **name_kw) -> None:
+def _plan(descs, n):
+    """(kernel name, executed FLOPs, {sum, sumsq} records per image of each problem) of the launch of these filled descriptors, from the
+    library's launchers (cmk_conv_plan); gn_groups without a gn_ws asks for the launch as with fused GroupNorm statistics."""
+    name, flops, recs = ctypes.create_string_buffer(96), ctypes.c_double(), (ctypes.c_int * n)()
+    check(_lib.load().cmk_conv_plan(descs, n, name, len(name), ctypes.byref(flops), recs), "cmk_conv_plan")
+    return name.value.decode(), flops.value, list(recs)
+
+
+def _launch(descs, n, ws, xs, ys, pcs, single=False, what="cmk_conv2d_nhwc_multi") -> None:
     """Launch the filled descriptors (cmk_conv2d_nhwc if single, else the _multi entry) with the split-K workspace ws alive across the
-    call.  When PROFILE is a list, the launch is timed and recorded under the kernel that the variant written, tv, runs."""
+    call.  When PROFILE is a list, the launch is timed and recorded under the kernel the library says it runs."""
     lib = _lib.load()
     if PROFILE is not None:
+        kernel, executed, _ = _plan(descs, n)
         pc = pcs[0]
         taps = pc.k * pc.k
         pix = lambda v: v.t.shape[0] * v.t.shape[1] * v.t.shape[2]
@@ -511,8 +520,7 @@ def _launch(descs, n, tv, ws, xs, ys, pcs, single=False, what="cmk_conv2d_nhwc_m
     if PROFILE is not None:
         e1.record()
         shape = tuple(xs[0].nhw) + (pc.cin, pc.cout, pc.k, pc.stride) if single else None
-        PROFILE.append((_kernel_name(taps, pc.stride, tv, **name_kw), flops, nbytes, e0, e1, shape,
-                        executed_flops(taps, pc.stride, tv, [tuple(y.t.shape[:3]) for y in ys], pc.cin_pad, pc.cout)))
+        PROFILE.append((kernel, flops, nbytes, e0, e1, shape, executed))
     del ws                  # referenced until the launch has been issued
 
 
@@ -522,16 +530,15 @@ def conv2d(x: View, pc: PackedConv, y: View, relu: bool = False, relu_upto: Opti
     sums of its output behind (cmk_conv_desc.pool_ws: the pointwise GEMM kernel, for the eSE gate); left empty otherwise."""
     descs = (ConvDesc * 1)()
     _fill_desc(descs[0], x, pc, y, relu, relu_upto, res, res_upsample, in_relu)
-    tv, ws = _apply_tuning(descs, 1, _problem_key(descs, 1))
-    pooled = pool is not None and FUSE_POOL
-    if pooled:
+    _, ws = _apply_tuning(descs, 1, _problem_key(descs, 1))
+    if pool is not None and FUSE_POOL:
         rows = _lib.load().cmk_conv_pool_rows(ctypes.byref(descs[0]))
         if rows > 0:
             d = descs[0]
             pws = torch.empty((2 * (-(-(d.N * d.H * d.W) // rows)), pc.cout), dtype=torch.float32, device=y.t.device)
             d.pool_ws = pws.data_ptr()
             pool.append((pws, rows))
-    _launch(descs, 1, tv, ws, [x], [y], [pc], single=True, what="cmk_conv2d_nhwc", pool=pooled, upres=bool(res_upsample), cout=pc.cout)
+    _launch(descs, 1, ws, [x], [y], [pc], single=True, what="cmk_conv2d_nhwc")
 
 
 def conv2d_multi(xs: Sequence[View], pcs: Sequence[PackedConv], ys: Sequence[View], relu: bool = False,
@@ -543,19 +550,26 @@ def conv2d_multi(xs: Sequence[View], pcs: Sequence[PackedConv], ys: Sequence[Vie
     for i in range(n):
         assert pcs[i].w.data_ptr() == pcs[0].w.data_ptr()
         _fill_desc(descs[i], xs[i], pcs[i], ys[i], relu, relu_upto, None, False, False, in_affine[i] if in_affine is not None else None)
-    tv, ws = _apply_tuning(descs, n, _problem_key(descs, n))
-    _launch(descs, n, tv, ws, xs, ys, pcs, aff=in_affine is not None)
+    _, ws = _apply_tuning(descs, n, _problem_key(descs, n))
+    _launch(descs, n, ws, xs, ys, pcs)
 
 
-def _gn_records(descs, ys, tv, groups):
-    """Point the descriptors at a new workspace for the fused GroupNorm statistics that variant tv writes (records numbered over the problems
-    in order).  Returns affine(lo, hi, gamma, beta, eps) -> [(scale, shift)] of problems lo..hi-1, to be called after the launch."""
+def _gn_records(descs, ys, groups):
+    """Point the descriptors at a new workspace for the fused GroupNorm statistics that their kernel writes (records numbered over the problems
+    in order), sized by the library's plan of the launch.  Returns affine(lo, hi, gamma, beta, eps) -> [(scale, shift)] of problems
+    lo..hi-1, to be called after the launch; None, with the descriptors left without statistics, when that kernel writes none."""
     lib = _lib.load()
     nimg, cout, dev = ys[0].t.shape[0], ys[0].c, ys[0].t.device
-    recs = [lib.cmk_conv_gn_records(y.t.shape[1], y.t.shape[2], 110 + tv[2] if tv[0] == 11 else tv[0]) for y in ys]
+    for i in range(len(ys)):
+        descs[i].gn_groups = groups             # without a gn_ws: the question
+    recs = _plan(descs, len(ys))[2]
+    if not any(recs):
+        for i in range(len(ys)):
+            descs[i].gn_groups = 0
+        return None
     gws = torch.empty((nimg * sum(recs), groups, 2), dtype=torch.float64, device=dev)
     for i in range(len(ys)):
-        descs[i].gn_ws, descs[i].gn_groups = gws.data_ptr(), groups
+        descs[i].gn_ws = gws.data_ptr()
 
     def affine(lo, hi, gamma, beta, eps):
         m = hi - lo
@@ -587,12 +601,11 @@ def conv_gn_multi(xs: Sequence[View], pcs: Sequence[PackedConv], gamma: torch.Te
         assert pcs[i].w.data_ptr() == pc.w.data_ptr()
         _fill_desc(descs[i], xs[i], pcs[i], ys[i], False, None, None, False, False, in_affine[i] if in_affine is not None else None)
     fusable = _gn_fusable(xs, pc.cout, groups)
-    tv, ws = _apply_tuning(descs, n, _problem_key(descs, n), with_gn_stats=fusable)
-    if not (fusable and tv[0] in (5, 6, 11)):
-        _launch(descs, n, tv, ws, xs, ys, pcs, aff=in_affine is not None)
+    _, ws = _apply_tuning(descs, n, _problem_key(descs, n), with_gn_stats=fusable)
+    affine = _gn_records(descs, ys, groups) if fusable else None
+    _launch(descs, n, ws, xs, ys, pcs)
+    if affine is None:
         return ys, groupnorm_affine_multi([y.t for y in ys], gamma, beta, groups, eps)
-    affine = _gn_records(descs, ys, tv, groups)
-    _launch(descs, n, tv, ws, xs, ys, pcs, aff=in_affine is not None)
     return ys, affine(0, n, gamma, beta, eps)
 
 
@@ -627,8 +640,8 @@ def conv_gn_multi_pair(xs_a: Sequence[View], pc_a: PackedConv, gn_a, xs_b: Seque
     if tv[3] > 1 or not (wino6 or sp3):
         return None
     _set_variant(descs, n, tv)
-    affine = _gn_records(descs, ys, tv, groups)
-    _launch(descs, n, tv, None, xs, ys, pcs, what="cmk_conv2d_nhwc_multi (tower pair)", aff=affs is not None)
+    affine = _gn_records(descs, ys, groups)
+    _launch(descs, n, None, xs, ys, pcs, what="cmk_conv2d_nhwc_multi (tower pair)")
     return (ys[:na], affine(0, na, gn_a[0], gn_a[1], eps)), (ys[na:], affine(na, n, gn_b[0], gn_b[1], eps))
 
 
@@ -1052,58 +1065,6 @@ def kernel_source_hash() -> str:
     for f in ("conv_args.hpp", "wino6_common.hpp", "conv.hip", "conv_igemm.hip", "conv_wino4r.hip", "conv_wino6.hip", "conv_wino6s.hip", "conv_pw.hip", "conv_sp3.hip"):
         h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:12]
-
-
-def executed_flops(taps: int, stride: int, tv, shapes, cin_pad: int, cout: int) -> float:
-    """FLOPs the matrix pipe EXECUTES for a conv launch, tile padding included (what a roofline fraction must be priced on; the
-    direct-convolution count is the algorithmic figure).  shapes: [(N, Ho, Wo)] per problem of the launch.
-    Winograd forms: 16 (F(2x2)) / 36 (F(4x4)) frequency GEMMs per tile of 2x2 / 4x4 outputs, 32 tiles x 32 couts per MFMA block."""
-    cd = lambda a, b: -(-a // b)
-    wm, sc, wn = (tuple(tv[:3]) if tv else (0, 0, 0))
-    if wm == 5:      # workgroup = 8x16 outputs x 64 couts: 256 MFMAs of 4096 FLOP per 16-channel chunk
-        return float(sum(n * cd(h, 8) * cd(w, 16) for n, h, w in shapes) * cd(cout, 64) * (cin_pad // 16) * 256 * 4096)
-    if wm == 6:      # workgroup = 12x40 outputs (wn 1) or two whole RoI maps (wn 2) x 32 couts: 144 MFMAs per 8-channel chunk
-        # (the shared-V form, sc 64, runs two such cout tiles per workgroup; a wave group without a tile issues no MFMAs: the same count;
-        # the paired form, sc 32, runs the idle half of an odd last pair on the last tile's weights: ceil(cout / 64) pairs)
-        wgs = sum(cd(n, 2) for n, h, w in shapes) if wn == 2 else sum(n * cd(h, 12) * cd(w, 40) for n, h, w in shapes)
-        return float(wgs * (2 * cd(cout, 64) if sc == 32 else cd(cout, 32)) * (cin_pad // 8) * 144 * 4096)
-    if wm == 11:     # direct 3x3 on split products (conv_sp3.hip), priced in fp32-equivalent FLOPs (x 3 products on the 16-bit pipe): tiles of geometry wn
-        th, tw, ct = ((8, 32, 128), (4, 32, 256), (16, 16, 128), (8, 16, 256))[wn]
-        if sc == 21 or (wn == 0 and cout <= 64):
-            ct //= 2
-        return float(sum(n * cd(h, th) * cd(w, tw) for n, h, w in shapes) * th * tw) * (cd(cout, ct) * ct) * cin_pad * 9 * 2.0
-    cout_pad = _lib.load().cmk_conv_cout_pad(cout)
-    if wm in (8, 9, 10, 12):  # workgroup = 64*wn pixels x 128 couts; 9 = the gather form (K = 9 taps x Cin); 10 / 12 = the split forms, priced in fp32-equivalent FLOPs
-        return float(sum(cd(n * h * w, 64 * wn) for n, h, w in shapes)) * (64 * wn) * (cd(cout, 128) * 128) * cin_pad * taps * 2.0
-    if wm not in (1, 2):                      # cost-model / gather / split-K variants: geometry of the smallest tile
-        wm, sc = 1, (32 if taps == 1 else 16)
-    if taps == 9 and tuple(tv[:1]) != (7,):
-        thh, tww = (32 // sc) * 4 * wm, sc
-        tiles = sum(n * cd(h, thh) * cd(w, tww) for n, h, w in shapes)
-    else:
-        tiles = sum(cd(n * h * w, 128 * wm) for n, h, w in shapes)
-    return float(tiles) * (128 * wm) * cout_pad * taps * cin_pad * 2.0
-
-
-def _kernel_name(taps, stride, tv, aff=False, pool=False, upres=False, cout=None) -> str:
-    """The template instantiation rocprofv3 will report (minus the `void cmk::` prefix and the argument list)."""
-    if tv[0] == 5:
-        return "conv_wino4r_kernel<{}>".format("true" if aff else "false")
-    if tv[0] == 6:
-        return "conv_wino6{}_kernel<{}, {}>".format({64: "s", 32: "p"}.get(tv[1], ""), "true" if aff else "false", 1 if tv[2] == 2 else 0)
-    wm, sc, wn = tv[:3]
-    sk = "true" if (len(tv) > 3 and tv[3] > 1) else "false"
-    if wm == 8:
-        return "conv_pw_kernel<{}, {}, false, {}, {}, 0>".format(wn, "true" if pool else "false", "true" if upres else "false", sk)
-    if wm in (10, 12):
-        return "conv_pw_kernel<4, {}, {}, {}, false, {}>".format("true" if pool else "false", "true" if taps == 9 else "false", "true" if upres else "false", 1 if wm == 10 else 2)
-    if wm == 11:
-        return "conv_sp3_kernel<{}, {}, 2, {}>".format(wn, 1 if (sc == 21 or (wn == 0 and cout is not None and cout <= 64)) else 2, "true" if aff else "false")
-    if wm == 9:
-        return "conv_pw_kernel<{}, false, true, false, {}, 0>".format(wn, sk)
-    if wm == 7:
-        return "conv_igemm_kernel<1, 1, 1, {}, 32, true>".format(wn)
-    return "conv_igemm_kernel<{}, {}, {}, {}, {}, false>".format(taps, stride, wm, wn, 32 if taps == 1 else sc)
 
 
 # ---------------------------------------------------------------------------------------------------------------

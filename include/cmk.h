@@ -87,7 +87,7 @@ typedef struct {
      * tiles numbered image-major per problem (for _multi: problems back to back) with cmk_conv_gn_tiles(H, W) tiles per image;
      * cmk_groupnorm_affine_tiles turns them into the per-(image, channel) scale/shift.  NULL = off.
      * With tune_wm == 6 the records are per (spatial tile of 12x40 outputs, wave 0..3, group): index ((tile*4 + wave)*gn_groups + group);
-     * cmk_conv_gn_records(H, W, tune_wm) gives the records per image of either form. */
+     * cmk_conv_gn_records(H, W, tune_wm) gives the records per image of either form, cmk_conv_plan those of any launch. */
     double* gn_ws; int gn_groups;
     /* tune_wm == 6 selects the fused Winograd F(4x4,3x3) kernel (conv_wino6.hip; 3x3 stride 1, no residual, Cin % 8 == 0; tune_wn 1 = 12x40-pixel
      * tiles of one image, tune_wn 2 = two whole maps of at most 16 rows x 14 columns per workgroup, for the 14x14 RoI features): 36 multiplies
@@ -132,8 +132,8 @@ typedef struct {
      * kernel (scaled by 2^-4, residual by 2^11: finite up to |x| = 1e6, 22 bits down to 2^-21); the caller packs the weights:
      * w' = w * S_w, S_w the power of two with max |w'| in [2^14, 2^15); w_splith = taps x cmk_splith_packed_halves(Cout, Cin) fp16 values,
      * [tap][Cin/16][cout_pad/32][piece h|m][lane 64][8] (lane = 32*hh + li: input channels 16*chunk + 8*hh + 0..7 of output channel 32*tile + li;
-     * cout_pad = Cout rounded up to 128, zero filled); w_splith_scale = 1 / S_w.  Takes in_scale/in_shift, gn_ws (cmk_conv_gn_records(H, W,
-     * 110 + geometry)), and in cmk_conv2d_nhwc_multi up to 10 problems that may differ in their weights.  No residual, split-K or pooled sums.
+     * cout_pad = Cout rounded up to 128, zero filled); w_splith_scale = 1 / S_w.  Takes in_scale/in_shift, gn_ws (records per image:
+     * cmk_conv_plan), and in cmk_conv2d_nhwc_multi up to 10 problems that may differ in their weights.  No residual, split-K or pooled sums.
      * No caller of this repository selects it by default (ops.ALLOW_SPLIT_F16); NULL = not available. */
     const void* w_splith;
     float w_splith_scale;
@@ -166,6 +166,16 @@ int cmk_conv2d_nhwc_multi(const cmk_conv_desc* descs, int n, void* stream);
  * statistics exactly as a launch with gn_ws set does (gn_ws may still be NULL: its size depends on the answer); when none applies, return
  * the choice among the others rather than fail. */
 int cmk_conv_resolve(const cmk_conv_desc* descs, int n, int with_gn_stats, int variant[3]);
+/* What cmk_conv2d_nhwc (n == 1) / cmk_conv2d_nhwc_multi would launch for these descriptors, as tuned (zero tune fields resolve as in a
+ * launch): validates and refuses exactly as the launch does, launches nothing and uses no stream.  The answer comes from the launcher that
+ * picks the template instantiation.  kernel (kernel_cap bytes, or NULL): the instantiation as a profiler names it, without the "void cmk::"
+ * prefix and the argument list, e.g. "conv_pw_kernel<4, true, false, false, false, 0>".  executed_flops (or NULL): what the matrix pipe
+ * executes, tile padding included; the split-product forms in fp32-equivalent FLOPs.  gn_records (n ints, or NULL): per problem the {sum,
+ * sumsq} records per image the launch writes through gn_ws, 0 where it writes none.
+ * gn_groups > 0 with gn_ws == NULL asks how large that workspace has to be (as cmk_conv_resolve's with_gn_stats): where the resolved kernel
+ * produces the statistics the launch is planned — and refused — as with a gn_ws; where it does not, as without (gn_records all 0).
+ * Touches no device, except that a tail with splitk_tail_tiles == 0 reads the current device's CU count (cmk_conv_tail_ws_floats). */
+int cmk_conv_plan(const cmk_conv_desc* descs, int n, char* kernel, int kernel_cap, double* executed_flops, int* gn_records /* n ints or NULL */);
 /* number of floats of the packed layout for (Cout, Cin, k): taps * ceil(Cin/16) * cout_pad * 16 */
 int64_t cmk_conv_packed_floats(int Cout, int Cin, int ksize);
 int cmk_conv_cout_pad(int Cout);
@@ -184,7 +194,8 @@ int64_t cmk_split_packed_halves(int Cout, int Cin);          /* 16-bit elements 
 int64_t cmk_splith_packed_halves(int Cout, int Cin);         /* 16-bit elements PER TAP of cmk_conv_desc.w_splith */
 /* spatial tiles per image of the fused-statistics conv (8 x 16 outputs each) */
 int cmk_conv_gn_tiles(int H, int W);
-/* {sum, sumsq} records per image written through cmk_conv_desc.gn_ws by the Winograd kernel tune_wm (5 or 6) on an H x W map */
+/* {sum, sumsq} records per image written through cmk_conv_desc.gn_ws by the Winograd kernel tune_wm (5 or 6) on an H x W map (any other
+ * kernel: cmk_conv_plan) */
 int cmk_conv_gn_records(int H, int W, int tune_wm);
 
 /* ---- deformable 3x3 conv of the VoVNet DCN stages (DFConv3x3.forward vovnet.py:185-201: d2 DeformConv / ModulatedDeformConv,

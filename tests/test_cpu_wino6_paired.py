@@ -34,10 +34,23 @@ def test_paired_form_is_on_the_menu():
         assert ops._variant_on_menu(tv), tv
     for tv in ((6, 32, 3), (6, 48, 1), (6, 64, 1, 2)):
         assert not ops._variant_on_menu(tv), tv
-    assert ops._kernel_name(9, 1, (6, 32, 1), aff=True) == "conv_wino6p_kernel<true, 0>"
-    assert ops._kernel_name(9, 1, (6, 32, 2)) == "conv_wino6p_kernel<false, 1>"
-    assert ops._kernel_name(9, 1, (6, 16, 1)) == "conv_wino6_kernel<false, 0>"
+    from centermask2_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_float * 64)()
+    ptr = (ctypes.addressof(buf) + 15) // 16 * 16
+
+    def plan(tv, aff=False, **shape):
+        d = _desc(_lib, ptr, tv, **shape)
+        if aff:
+            d.in_scale = d.in_shift = ptr
+        name, flops = ctypes.create_string_buffer(96), ctypes.c_double()
+        assert lib.cmk_conv_plan(ctypes.byref(d), 1, name, len(name), ctypes.byref(flops), None) == 0, lib.cmk_last_error()
+        return name.value.decode(), flops.value
+
+    assert plan((6, 32, 1), aff=True)[0] == "conv_wino6p_kernel<true, 0>"
+    assert plan((6, 32, 2), h=14, w=14)[0] == "conv_wino6p_kernel<false, 1>"
+    assert plan((6, 16, 1))[0] == "conv_wino6_kernel<false, 0>"
     # two cout tiles per workgroup: an odd last pair still executes two tiles' MFMAs
-    f16 = ops.executed_flops(9, 1, (6, 16, 1), [(8, 100, 160)], 256, 80)
-    f32 = ops.executed_flops(9, 1, (6, 32, 1), [(8, 100, 160)], 256, 80)
+    f16 = plan((6, 16, 1), n=8, h=100, w=160, cin=256, cout=80)[1]
+    f32 = plan((6, 32, 1), n=8, h=100, w=160, cin=256, cout=80)[1]
     assert f32 == f16 * 4 / 3

@@ -37,7 +37,7 @@ for name, h, w, cin, cout in SHAPES:
     best = [1e9, 1e9]
     for _ in range(rounds):
         for k in range(2): best[k] = min(best[k], timeit(ds[k][0]))
-    ex = ops.executed_flops(9, 1, (6, 16, 2 if roi else 1), [(n, h, w)], pc.cin_pad, cout)
+    ex = ops._plan(ds[0], 1)[1]          # the executed FLOPs of the 6/16 launch, from the library
     tot[0] += best[0]; tot[1] += best[1]
     print("%-9s %9.3f %8.1f %9.3f %8.1f %7.2f %6s" % (name, best[0], ex / best[0] / 1e9, best[1], ex / best[1] / 1e9, best[0] / best[1], eq), flush=True)
 print("sum w6 %.3f ms, w6s %.3f ms" % tuple(tot))
