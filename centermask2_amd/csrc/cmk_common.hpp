@@ -27,6 +27,12 @@ inline int check_launch(const char* what) {
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// grid of a grid-stride kernel with 256 threads per workgroup: one thread per work item, capped at 4096 workgroups
+inline int stream_grid(long work_items) {
+    long b = (work_items + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
+
 // wave64 reductions (DPP/bpermute via __shfl_xor)
 __device__ inline float wave_sum(float v) {
 #pragma unroll

@@ -5,6 +5,8 @@
 // the depth-wise conv, [out_min, out_max] = [0, 6] its own ReLU6.  The zero padding stands for zeros of the clamped input, so the
 // border taps are skipped, never replaced by `shift`.  Infinite bounds switch a clamp off.  Both clamps are written as selects: a NaN
 // fails every comparison and passes through, as in torch.nn.ReLU6 (fminf / fmaxf would return the bound instead).
+// PLAIN is the bare depth-wise 3x3 (vovnet.py:110-119 'dw_conv3x3': no bias, no activation; the point-wise 1x1 + FrozenBN + ReLU that
+// follows is an ordinary conv launch): y = dw3x3(x), both clamps and the affine compiled out, scale / shift never read.
 //
 // HBM-bound (1 FMA per 4 bytes at best): one thread = 4 channels x T adjacent output columns x R output rows, 16-byte loads and stores,
 // the ((R-1)*S+3) x ((T-1)*S+3) input quads each loaded once per thread, the 9 weight quads and the affine in registers.  Rows matter more
@@ -22,7 +24,7 @@ typedef float dwq __attribute__((ext_vector_type(4)));
 __device__ inline float clamp_hi(float v, float hi) { return v > hi ? hi : v; }                     // NaN stays NaN
 __device__ inline float clamp_lo_hi(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-template <int S, int T, int R>
+template <int S, int T, int R, bool PLAIN>
 __global__ __launch_bounds__(256) void dwconv3_bn_act_kernel(const float* __restrict__ x, int x_cs, int x_co, const float* __restrict__ w,
                                                             const float* __restrict__ scale, const float* __restrict__ shift, float in_max,
                                                             float out_min, float out_max, float* __restrict__ y, int y_cs, int y_co, int N,
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(256) void dwconv3_bn_act_kernel(const float* __rest
                 dwq v = {0.f, 0.f, 0.f, 0.f};
                 if (iw >= 0 && iw < W) {
                     v = *reinterpret_cast<const dwq*>(row + (long)iw * x_cs);
-                    v.x = clamp_hi(v.x, in_max); v.y = clamp_hi(v.y, in_max); v.z = clamp_hi(v.z, in_max); v.w = clamp_hi(v.w, in_max);
+                    if (!PLAIN) { v.x = clamp_hi(v.x, in_max); v.y = clamp_hi(v.y, in_max); v.z = clamp_hi(v.z, in_max); v.w = clamp_hi(v.w, in_max); }
                 }
 #pragma unroll
                 for (int q = 0; q < R; ++q) {
@@ -75,8 +77,11 @@ __global__ __launch_bounds__(256) void dwconv3_bn_act_kernel(const float* __rest
                 }
             }
         }
-        const dwq sc = *reinterpret_cast<const dwq*>(scale + c4 * 4);
-        const dwq sh = *reinterpret_cast<const dwq*>(shift + c4 * 4);
+        dwq sc = {0.f, 0.f, 0.f, 0.f}, sh = sc;
+        if (!PLAIN) {
+            sc = *reinterpret_cast<const dwq*>(scale + c4 * 4);
+            sh = *reinterpret_cast<const dwq*>(shift + c4 * 4);
+        }
 #pragma unroll
         for (int q = 0; q < R; ++q) {
             const int oh = oh0 + q;
@@ -85,11 +90,13 @@ __global__ __launch_bounds__(256) void dwconv3_bn_act_kernel(const float* __rest
             for (int j = 0; j < T; ++j) {
                 const int ow = wt * T + j;
                 if (ow < Wo) {
-                    dwq o;
-                    o.x = clamp_lo_hi(fmaf(acc[q][j].x, sc.x, sh.x), out_min, out_max);
-                    o.y = clamp_lo_hi(fmaf(acc[q][j].y, sc.y, sh.y), out_min, out_max);
-                    o.z = clamp_lo_hi(fmaf(acc[q][j].z, sc.z, sh.z), out_min, out_max);
-                    o.w = clamp_lo_hi(fmaf(acc[q][j].w, sc.w, sh.w), out_min, out_max);
+                    dwq o = acc[q][j];
+                    if (!PLAIN) {
+                        o.x = clamp_lo_hi(fmaf(o.x, sc.x, sh.x), out_min, out_max);
+                        o.y = clamp_lo_hi(fmaf(o.y, sc.y, sh.y), out_min, out_max);
+                        o.z = clamp_lo_hi(fmaf(o.z, sc.z, sh.z), out_min, out_max);
+                        o.w = clamp_lo_hi(fmaf(o.w, sc.w, sh.w), out_min, out_max);
+                    }
                     *reinterpret_cast<dwq*>(y + (((long)n * Ho + oh) * Wo + ow) * y_cs + y_co + c4 * 4) = o;
                 }
             }
@@ -109,11 +116,11 @@ static inline long dw_blocks(const DwArgs& a, int t, int r) {
     return ((long)a.N * ((a.Ho + r - 1) / r) * ((a.Wo + t - 1) / t) * a.C4 + 255) / 256;
 }
 
-template <int S, int T, int R>
+template <int S, int T, int R, bool PLAIN = false>
 static void launch_dw(const DwArgs& a) {
     const long blocks = dw_blocks(a, T, R);
-    const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
-    hipLaunchKernelGGL((dwconv3_bn_act_kernel<S, T, R>), dim3(grid), dim3(256), 0, (hipStream_t)a.stream, a.x, a.x_cs, a.x_co, a.w, a.scale, a.shift,
+    const unsigned grid = PLAIN ? (unsigned)stream_grid(blocks * 256) : (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
+    hipLaunchKernelGGL((dwconv3_bn_act_kernel<S, T, R, PLAIN>), dim3(grid), dim3(256), 0, (hipStream_t)a.stream, a.x, a.x_cs, a.x_co, a.w, a.scale, a.shift,
                        a.in_max, a.out_min, a.out_max, a.y, a.y_cs, a.y_co, a.N, a.H, a.W, a.Ho, a.Wo, a.C4);
 }
 
@@ -150,4 +157,18 @@ extern "C" int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, con
         else launch_dw<2, 1, 1>(a);
     }
     return check_launch("dwconv3_bn_act");
+}
+
+extern "C" int cmk_dwconv3x3_nhwc(const float* x, int x_cs, int x_co, const float* w, float* y, int y_cs, int y_co, int N, int H, int W,
+                                  int C, int stride, void* stream) {
+    if (!x || !w || !y) return fail(CMK_EINVAL, "dwconv: null pointer%s", "");
+    if ((C & 3) || (x_cs & 3) || (x_co & 3) || (y_cs & 3) || (y_co & 3) || C < 4) return fail(CMK_EINVAL, "dwconv: channels must be multiples of 4%s", "");
+    if (stride != 1 && stride != 2) return fail(CMK_EINVAL, "dwconv: stride must be 1 or 2%s", "");
+    if (N < 1 || H < 1 || W < 1) return fail(CMK_EINVAL, "dwconv: empty input%s", "");
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    if ((long)N * Ho * Wo * (C >> 2) >= (1L << 31)) return fail(CMK_EINVAL, "dwconv: %s%ld output quads, the kernel indexes them in 32 bits", "", (long)N * Ho * Wo * (C >> 2));
+    const DwArgs a = {x, w, nullptr, nullptr, y, x_cs, x_co, y_cs, y_co, N, H, W, Ho, Wo, C >> 2, INFINITY, -INFINITY, INFINITY, stream};
+    if (stride == 1) launch_dw<1, 4, 1, true>(a);
+    else launch_dw<2, 2, 1, true>(a);
+    return check_launch("dwconv3");
 }

@@ -848,14 +848,15 @@ def ese(x: View, fc_w: torch.Tensor, fc_b: torch.Tensor, y: View, identity: Opti
     n, h, w = x.nhw
     hw, c = h * w, x.c
     if gate is None:
-        chunks = _ese_chunks(hw, c)
-        ws = torch.empty((n, chunks, c), dtype=torch.float32, device=x.t.device)
-        gate = torch.empty((n, c), dtype=torch.float32, device=x.t.device)
-        check(lib.cmk_ese_gate(x.t.data_ptr(), x.cs, x.co, fc_w.data_ptr(), fc_b.data_ptr(), gate.data_ptr(), ws.data_ptr(), chunks,
-                               n, hw, c, _stream()), "cmk_ese_gate")
+        gate = ese_gate(x, fc_w, fc_b)
     idp, idcs, idco = (identity.t.data_ptr(), identity.cs, identity.co) if identity is not None else (None, 0, 0)
     check(lib.cmk_ese_scale(x.t.data_ptr(), x.cs, x.co, gate.data_ptr(), idp, idcs, idco, y.t.data_ptr(), y.cs, y.co,
                             n, hw, c, _stream()), "cmk_ese_scale")
+
+
+def _gn_chunks(hw: int) -> int:
+    """Pixel chunks per image for the GroupNorm statistics of one map: 128 pixels per workgroup, at most 128 chunks."""
+    return max(1, min(128, hw // 128))
 
 
 def groupnorm_affine(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int = 32, eps: float = 1e-5):
@@ -865,7 +866,7 @@ def groupnorm_affine(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, g
     _need_gpu(x, "groupnorm_affine")
     n, h, w, c = x.shape
     hw = h * w
-    chunks = max(1, min(128, hw // 128))
+    chunks = _gn_chunks(hw)
     ws = torch.empty((n, groups, chunks, 2), dtype=torch.float64, device=x.device)
     sc = torch.empty((n, c), dtype=torch.float32, device=x.device)
     sh = torch.empty((n, c), dtype=torch.float32, device=x.device)
@@ -901,7 +902,7 @@ def groupnorm_relu_(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gr
     _need_gpu(x, "groupnorm_relu_")
     n, h, w, c = x.shape
     hw = h * w
-    chunks = max(1, min(128, hw // 128))
+    chunks = _gn_chunks(hw)
     ws = torch.empty((n, groups, chunks, 2), dtype=torch.float64, device=x.device)
     fn = lib.cmk_groupnorm_relu_nhwc if relu else lib.cmk_groupnorm_nhwc
     check(fn(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws.data_ptr(), chunks, n, hw, c, groups, eps, _stream()), "cmk_groupnorm[_relu]_nhwc")

@@ -98,6 +98,24 @@ def test_depthwise_conv3x3(dev, case):
     assert y.c == c
 
 
+# the cases of test_depthwise_conv3x3 and an odd output width at stride 2
+@pytest.mark.parametrize("case", [(2, 37, 53, 64, 1), (1, 40, 64, 112, 2), (3, 9, 7, 80, 1), (1, 1, 1, 4, 2), (2, 30, 31, 96, 2), (1, 5, 9, 8, 2)])
+def test_depthwise_plain_equals_fused_with_unit_affine(dev, case):
+    """The plain depth-wise 3x3 is the fused kernel without its clamps and affine: with scale 1, shift 0 and infinite clamps both give the
+    same bits on finite inputs.  The order of the taps per output does not depend on the tile, and fmaf(v, 1, 0) is v."""
+    n, h, w, c, stride = case
+    g = torch.Generator().manual_seed(5)
+    buf = torch.randn((n, h, w, c + 16), generator=g).to(dev)
+    w9c = ops.pack_dw_weight(torch.randn((c, 1, 3, 3), generator=g)).to(dev)
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    plain, fused = (torch.full((n, ho, wo, c + 8), 7.0, device=dev) for _ in range(2))
+    ops.dwconv3x3(View(buf, 8, c), w9c, View(plain, 4, c), stride=stride)
+    ops.dwconv3x3_bn_act(View(buf, 8, c), w9c, torch.ones(c, device=dev), torch.zeros(c, device=dev), View(fused, 4, c), stride=stride)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(plain).all())
+    assert torch.equal(plain, fused)
+
+
 def test_stem_conv(dev):
     x = _rand((2, 3, 37, 50), 11, 40.0)
     wt = _rand((64, 3, 3, 3), 12, 0.2)
@@ -771,6 +789,53 @@ def test_groupnorm_affine_multi_level(dev):
         ref = F.group_norm(x, 32, gamma, beta, eps=1e-5)
         got = x * sc.cpu()[:, :, None, None] + sh.cpu()[:, :, None, None]
         _close(got, ref, 2e-5)
+
+
+def _gn_affine_raw(lib, xs, gamma, beta, groups, chunks, multi):
+    """(workspace, [(scale, shift) per level]) of cmk_groupnorm_affine (one level) or cmk_groupnorm_affine_multi on dense NHWC tensors."""
+    import ctypes
+    nl, (n, c) = len(xs), (xs[0].shape[0], xs[0].shape[3])
+    dev = xs[0].device
+    ws = torch.zeros((nl, n, groups, chunks, 2), dtype=torch.float64, device=dev)
+    out = [(torch.zeros((n, c), device=dev), torch.zeros((n, c), device=dev)) for _ in xs]
+    hws = [x.shape[1] * x.shape[2] for x in xs]
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if multi:
+        px, ps, pb = ((ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts]) for ts in (xs, [o[0] for o in out], [o[1] for o in out]))
+        rc = lib.cmk_groupnorm_affine_multi(px, (ctypes.c_int * nl)(*hws), nl, gamma.data_ptr(), beta.data_ptr(), ws.data_ptr(), chunks, n, c,
+                                            groups, 1e-5, ps, pb, stream)
+    else:
+        assert nl == 1
+        rc = lib.cmk_groupnorm_affine(xs[0].data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws.data_ptr(), chunks, n, hws[0], c, groups, 1e-5,
+                                      out[0][0].data_ptr(), out[0][1].data_ptr(), stream)
+    assert rc == 0, lib.cmk_last_error().decode()
+    torch.cuda.synchronize()
+    return ws, out
+
+
+def test_groupnorm_one_level_equals_multi(dev, cmk_lib):
+    """cmk_groupnorm_affine is cmk_groupnorm_affine_multi with one level: same workspace records, same (scale, shift), bit for bit; and each
+    level of a two-level call equals its own one-level call."""
+    def level(n, h, w, c, seed):
+        return (_rand((n, h, w, c), seed, 3.0) + 1.5).to(dev)
+
+    def params(c):
+        return (torch.rand(c, generator=torch.Generator().manual_seed(42)) + 0.5).to(dev), _rand((c,), 43, 0.1).to(dev)
+
+    # several pixels per thread row and HW no multiple of the chunks | one pixel per pass and an empty chunk | one pixel, one chunk
+    for n, h, w, c, groups, chunks in [(2, 5, 7, 64, 16, 3), (1, 3, 3, 1024, 32, 4), (3, 1, 1, 256, 32, 1)]:
+        x, (gamma, beta) = level(n, h, w, c, 7), params(c)
+        ws1, out1 = _gn_affine_raw(cmk_lib, [x], gamma, beta, groups, chunks, multi=False)
+        wsm, outm = _gn_affine_raw(cmk_lib, [x], gamma, beta, groups, chunks, multi=True)
+        assert bool(ws1.abs().sum() > 0) and torch.equal(ws1, wsm), (n, h, w, c)
+        assert torch.equal(out1[0][0], outm[0][0]) and torch.equal(out1[0][1], outm[0][1]), (n, h, w, c)
+    n, c, groups, chunks = 2, 64, 16, 3
+    xs, (gamma, beta) = [level(n, 5, 7, c, 8), level(n, 3, 4, c, 9)], params(c)
+    wsm, outm = _gn_affine_raw(cmk_lib, xs, gamma, beta, groups, chunks, multi=True)
+    for l, x in enumerate(xs):
+        ws1, out1 = _gn_affine_raw(cmk_lib, [x], gamma, beta, groups, chunks, multi=False)
+        assert torch.equal(ws1[0], wsm[l]), l
+        assert torch.equal(out1[0][0], outm[l][0]) and torch.equal(out1[0][1], outm[l][1]), l
 
 
 def test_maxpool_with_folded_ese_gate(dev):
