@@ -217,6 +217,8 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
         int rc = setup_gn(a, d);
         if (rc) return rc;
     }
+    if (d->splitk_tail > 1 && d->tune_wm != 6)      // (tune_wm 6 sorts out its own forms below)
+        return fail(CMK_EINVAL, "conv: tail split-K is a feature of the RoI-pair F(4x4) forms (tune_wm 6, tune_wn 2, tune_sc 16 or 32)%s", "");
     if (d->tune_wm == 5) {          // Winograd F(2x2,3x3): 3x3 stride 1, no residual / input ReLU
         if (d->ksize != 3 || d->stride != 1 || d->res_mode != 0 || d->in_relu || !d->w_wino)
             return fail(CMK_EINVAL, "conv: Winograd variant not available for this conv%s", "");

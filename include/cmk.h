@@ -145,7 +145,7 @@ typedef struct {
      * only); a reduce launch over those images sums them in a fixed order and applies scale / shift / ReLU.  The other images get the bits
      * of the launch without a tail; the tail's images differ from it by fp32 rounding.  splitk_tail_tiles > 0 is taken as given (capped at
      * the launch's tiles); 0 asks cmk_wino6_tail_plan with the current device's places (CUs x 2, paired form x 1) — the plan's tiles and at
-     * most its ways, and no tail at all where it finds no ragged round.  One problem, no gn_ws, no splitk beside it; tune_sc 64 refuses it.
+     * most its ways, and no tail at all where it finds no ragged round.  One problem, no gn_ws, no splitk beside it; tune_sc 64, tune_wn 1 and every other tune_wm refuse it.
      * splitk_tail 0 | 1 = off: nothing is on unless the caller names it.
      * (splitk > 1 with tune_wn 2 is the case "every tile is tail": splitk <= Cin / 16 ways, the full-size split-K workspace.) */
     int splitk_tail; int splitk_tail_tiles;

@@ -238,7 +238,7 @@ DIRECT_VARIANT_SHAPES = [(2, 37, 45, 64, 128), (1, 20, 70, 32, 96), (1, 9, 33, 4
 def test_conv_direct_tile_variants(dev, wm, sc):
     """Every (WM, sub-tile, WN) instantiation of the direct 3x3 stride-1 kernel that the library admits for a shape, driven through
     the real knob (the descriptor's tune_* fields).  The start-up tuner may pick any of them, so each must be right by itself."""
-    ran = 0
+    ran = set()
     for (n, h, w, cin, cout) in DIRECT_VARIANT_SHAPES:
         x = _rand((n, cin, h, w), 31)
         wt = _rand((cout, cin, 3, 3), 32, (2.0 / (cin * 9)) ** 0.5)
@@ -250,8 +250,10 @@ def test_conv_direct_tile_variants(dev, wm, sc):
             if rc != 0:
                 continue                  # not on the menu for this Cout (WN must divide the padded Cout; WM 2 needs WN <= 4)
             _close(y.nchw(), ref)
-            ran += 1
-    assert ran >= 6, ran
+            ran.add((cout, wn))
+    # the menu, exactly: a tiling that stopped being offered shows here.  WN divides the Cout tiles (Cout / 32 <= 7); WM 2 keeps WN <= 4
+    menu = {128: (1, 2, 4), 96: (1, 3), 160: (1, 5), 192: (1, 2, 3, 6), 224: (1, 7)}
+    assert ran == {(cout, wn) for cout, wns in menu.items() for wn in wns if wm == 1 or wn <= 4}, sorted(ran)
 
 
 def test_conv_stride2_and_1x1_variants(dev):
