@@ -211,6 +211,7 @@ static bool writes_gn_records(int tune_wm) { return tune_wm == 5 || tune_wm == 6
 // split-K partial sums for run() to reduce.  plan: conv_args.hpp LaunchPlan.
 static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* descs, int n, hipStream_t st, LaunchPlan* plan) {
     const int cout32 = (d->Cout + 31) / 32;
+    const int cout_pad128 = cdiv(cout32, 4) * 128;      // Cout padded to the 128 couts of a conv_pw / conv_sp3 workgroup column
     if (d->gn_ws) {
         if (!writes_gn_records(d->tune_wm))
             return fail(CMK_EINVAL, "conv: fused GroupNorm statistics are only produced by the Winograd form%s", "");
@@ -256,28 +257,23 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
     a.pool_ws = d->pool_ws;
     if (d->tune_wm == 8) {                             // pointwise GEMM kernel (conv_pw.hip); tune_wn = accumulator rows per wave
         if (d->ksize != 1 || cout32 <= 7) return fail(CMK_EINVAL, "conv: pointwise variant needs a 1x1 conv with Cout > 224%s", "");
-        a.cout_pad = cdiv(cout32, 4) * 128;
+        a.cout_pad = cout_pad128;
         if (a.ksplit > 1 && !pointwise_mt(d, n)) return fail(CMK_EINVAL, "conv: pointwise variant: split-K not available for this conv%s", "");
         return launch_pw(a, d->tune_wn, st, plan);
     }
-    if (d->tune_wm == 10) {                            // opt-in: the pointwise GEMM from bf16-split products (fp32-accurate, cmk.h w_split)
-        if (!(d->ksize == 1 ? pointwise_mt(d, n) : gather_mt(d, n)))
-            return fail(CMK_EINVAL, "conv: the bf16-split variant needs w_split and a conv the pointwise GEMM kernel takes (1x1, or 3x3 in its gather form)%s", "");
-        a.cout_pad = cdiv(cout32, 4) * 128;
-        a.w = reinterpret_cast<const float*>(d->w_split);
+    // opt-in: the pointwise GEMM from split products (fp32-accurate): 10 = three bf16 pieces per operand (cmk.h w_split), 12 = two fp16 pieces /
+    // three products (cmk.h w_splith, w_splith_scale)
+    if (d->tune_wm == 10 || d->tune_wm == 12) {
+        const bool f16 = d->tune_wm == 12;
+        if (!(d->ksize == 1 ? pointwise_mt(d, n) : gather_mt(d, n)) || (f16 && !(d->w_splith_scale > 0.f)))
+            return fail(CMK_EINVAL, f16 ? "conv: the fp16-split variant needs w_splith, w_splith_scale and a conv the pointwise GEMM kernel takes (1x1, or 3x3 in its gather form)%s"
+                                        : "conv: the bf16-split variant needs w_split and a conv the pointwise GEMM kernel takes (1x1, or 3x3 in its gather form)%s", "");
+        a.cout_pad = cout_pad128;
+        a.w = reinterpret_cast<const float*>(f16 ? d->w_splith : d->w_split);
+        if (f16) a.p[0].acc_scale = d->w_splith_scale;
         a.ksplit = 1;
         a.ga_stride = d->ksize == 3 ? d->stride : 0;
-        return launch_pw_split(a, 1, st, plan);
-    }
-    if (d->tune_wm == 12) {                            // opt-in: the same on two fp16 pieces per operand / three products (cmk.h w_splith)
-        if (!(d->ksize == 1 ? pointwise_mt(d, n) : gather_mt(d, n)) || !(d->w_splith_scale > 0.f))
-            return fail(CMK_EINVAL, "conv: the fp16-split variant needs w_splith, w_splith_scale and a conv the pointwise GEMM kernel takes (1x1, or 3x3 in its gather form)%s", "");
-        a.cout_pad = cdiv(cout32, 4) * 128;
-        a.w = reinterpret_cast<const float*>(d->w_splith);
-        a.p[0].acc_scale = d->w_splith_scale;
-        a.ksplit = 1;
-        a.ga_stride = d->ksize == 3 ? d->stride : 0;
-        return launch_pw_split(a, 2, st, plan);
+        return launch_pw_split(a, f16 ? 2 : 1, st, plan);
     }
     if (d->tune_wm == 11) {                            // opt-in: direct 3x3 conv on bf16-split products (conv_sp3.hip); tune_sc = pieces, tune_wn = geometry
         if (d->ksize != 3 || d->stride != 1 || !d->w_splith || d->splitk > 1 || d->res_mode != 0 || d->in_relu || d->pool_ws)
@@ -287,14 +283,14 @@ static int dispatch(ConvArgs& a, const cmk_conv_desc* d, const cmk_conv_desc* de
             a.p[i].w = reinterpret_cast<const float*>(descs[i].w_splith);
             a.p[i].acc_scale = descs[i].w_splith_scale;
         }
-        a.cout_pad = cdiv(cout32, 4) * 128;
+        a.cout_pad = cout_pad128;
         a.ksplit = 1;
         return launch_sp3(a, d->tune_wn, d->tune_sc, st, plan);
     }
     if (d->tune_wm == 9) {                             // gather form of a 3x3 conv on the pointwise GEMM kernel; tune_wn = accumulator rows per wave
         const int mt = gather_mt(d, n);
         if (!mt) return fail(CMK_EINVAL, "conv: pointwise gather variant not available for this conv%s", "");
-        a.cout_pad = cdiv(cout32, 4) * 128;
+        a.cout_pad = cout_pad128;
         a.ga_stride = d->stride;
         return launch_pw(a, mt, st, plan);
     }

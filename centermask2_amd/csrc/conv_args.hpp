@@ -7,6 +7,29 @@ namespace cmk {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// bounds-checked 16- | 8-byte loads: lanes whose byte offset lies outside [0, num_records) of the resource get 0
+__device__ f32x4 buffer_load_f32x4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
+__device__ f32x2 buffer_load_f32x2(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
+
+// buffer resource {base, num_records = bytes, raw dword format} over `bytes` bytes from a wave-uniform base
+__device__ __forceinline__ i32x4 buffer_rsrc(const void* base, int bytes) {
+    const unsigned long long b = (unsigned long long)base;
+    i32x4 rsrc;
+    rsrc.x = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffull));
+    rsrc.y = __builtin_amdgcn_readfirstlane((int)((b >> 32) & 0xffffull));
+    rsrc.z = __builtin_amdgcn_readfirstlane(bytes);
+    rsrc.w = 0x00020000;
+    return rsrc;
+}
+
+// a pointer every lane holds the same value of, moved to the scalar unit (the saddr of the epilogues' global_store walks)
+__device__ __forceinline__ unsigned long long wave_uniform_u64(const void* p) {
+    const unsigned long long b = (unsigned long long)p;
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)b);
+}
 
 constexpr int PST = 20;      // LDS row pitch in floats: 16 channels + 4 pad
 constexpr int MAXP = 10;     // problems per launch: the 5 FPN levels, twice where two convs with different weights share a launch (F(4x4) kernels)

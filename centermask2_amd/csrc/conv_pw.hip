@@ -24,13 +24,174 @@
 
 #include <type_traits>
 
-#include "conv_args.hpp"
+#include "conv_split.hpp"
 
 namespace cmk {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ f32x4 pw_buffer_load(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
+// ---- the K loops of the opt-in split forms (SPLIT below): conv_pw_kernel runs one of them in place of its fp32 pipeline --------------------------
+// What pw_split_loop asks of a split: pieces per operand, stage (split a staged float4 and write its pieces, 64 * 16 bytes apart, from the
+// thread's slot of piece 0), a cout tile's weight operands of one chunk from its pieces, and the product group (conv_split.hpp).
+struct PwSplitBf16 {        // three bf16 pieces, six products
+    static constexpr int P = 3;
+    struct B { bf16x8 h, m, l; };
+    static __device__ __forceinline__ void stage(f32x4 x, unsigned char* dst) {      // h and m leave before l is formed
+        const u32x2 h = split_bf16_piece(x), m = split_bf16_piece(x);
+        *reinterpret_cast<u32x2*>(dst) = h;
+        *reinterpret_cast<u32x2*>(dst + 64 * 16) = m;
+        *reinterpret_cast<u32x2*>(dst + 2 * 64 * 16) = split_bf16_piece(x);
+    }
+    static __device__ __forceinline__ B weights(const u32x4 (&w)[3]) {
+        return {__builtin_bit_cast(bf16x8, w[0]), __builtin_bit_cast(bf16x8, w[1]), __builtin_bit_cast(bf16x8, w[2])};
+    }
+    static __device__ __forceinline__ f32x16 products(const u32x4 (&av)[3], const B& b, f32x16 acc) {
+        return mfma6_bf16(__builtin_bit_cast(bf16x8, av[0]), __builtin_bit_cast(bf16x8, av[1]), __builtin_bit_cast(bf16x8, av[2]), b.h, b.m, b.l, acc);
+    }
+};
+struct PwSplitF16 {         // two fp16 pieces, three products
+    static constexpr int P = 2;
+    struct B { f16x8 h, m, hs; };
+    static __device__ __forceinline__ void stage(f32x4 x, unsigned char* dst) {
+        u32x2 h, m;
+        split_f16(x * SPLIT_SX, h, m);
+        *reinterpret_cast<u32x2*>(dst) = h;
+        *reinterpret_cast<u32x2*>(dst + 64 * 16) = m;
+    }
+    static __device__ __forceinline__ B weights(const u32x4 (&w)[2]) {
+        const f16x8 Bh = __builtin_bit_cast(f16x8, w[0]);
+        return {Bh, __builtin_bit_cast(f16x8, w[1]), split_f16_bhs(Bh)};
+    }
+    static __device__ __forceinline__ f32x16 products(const u32x4 (&av)[2], const B& b, f32x16 acc) {
+        return mfma3_f16(__builtin_bit_cast(f16x8, av[0]), __builtin_bit_cast(f16x8, av[1]), b.h, b.m, b.hs, acc);
+    }
+};
 
+// SPLIT 1 (1x1 and gather form) and the gather form of SPLIT 2: 16 channels per stage.  The activations are staged by the kernel's own load_A (GA:
+// it walks the 9 taps x Cin / 16 chunks in order, re-pointing the rows per tap; the split weights are packed tap-major to match) and split on
+// their way into the LDS; the weights come one chunk ahead from a.w: [chunk][cout_pad/32][piece][lane 64][8 x 16 bit].
+template <class S, int MT, class LoadA>
+__device__ __forceinline__ void pw_split_loop(const ConvArgs& a, unsigned char* sb, int tid, int lane, int wm, int co0, int nchunks,
+                                              const f32x4 (&a_st)[MT], LoadA&& load_A, f32x16 (&acc)[MT][2]) {
+    constexpr int P = S::P;
+    constexpr int STAGE = 2 * MT * P * 64 * 16;         // bytes per LDS stage: [32-row block][piece][lane][8 x 16 bit]
+    // this thread's 8-byte half slots: row r = tid / 4 + 64 it -> (block r / 32, li = r % 32); quad tid & 3 -> lane half (tid & 3) / 2, half slot (tid & 3) & 1
+    int st_off[MT];
+#pragma unroll
+    for (int it = 0; it < MT; ++it) {
+        const int r = (tid >> 2) + 64 * it;
+        st_off[it] = (((r >> 5) * P) * 64 + ((tid & 3) >> 1) * 32 + (r & 31)) * 16 + (tid & 1) * 8;
+    }
+    auto stage = [&](int buf) {
+        unsigned char* dst = sb + buf * STAGE;
+#pragma unroll
+        for (int it = 0; it < MT; ++it) S::stage(a_st[it], dst + st_off[it]);
+    };
+    const u32x4* wsp = reinterpret_cast<const u32x4*>(a.w) + ((long)(co0 >> 5) * P) * 64 + lane;      // wave-uniform base + lane
+    const long wstep = (long)(a.cout_pad >> 5) * P * 64;
+    u32x4 wb[2][P];
+    auto load_Bs = [&](int chunk) {
+#pragma unroll
+        for (int nn = 0; nn < 2; ++nn)
+#pragma unroll
+            for (int p_ = 0; p_ < P; ++p_) wb[nn][p_] = wsp[chunk * wstep + (nn * P + p_) * 64];
+    };
+    load_A(0);
+    load_Bs(0);
+    stage(0);
+    load_A(min(1, nchunks - 1));
+    for (int c = 0; c < nchunks; ++c) {
+        __syncthreads();            // stage c & 1 is complete; everybody has read all of the other stage
+        const u32x4* ap = reinterpret_cast<const u32x4*>(sb + (c & 1) * STAGE) + (wm * MT * P) * 64 + lane;
+        typename S::B wc[2];
+#pragma unroll
+        for (int nn = 0; nn < 2; ++nn) wc[nn] = S::weights(wb[nn]);
+        load_Bs(min(c + 1, nchunks - 1));
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            u32x4 av[P];
+#pragma unroll
+            for (int p_ = 0; p_ < P; ++p_) av[p_] = ap[(m * P + p_) * 64];
+            if (m == 1) {           // the next chunk's activations (in registers since the last chunk) are split between the MFMA groups
+                stage((c + 1) & 1);
+                load_A(min(c + 2, nchunks - 1));
+            }
+#pragma unroll
+            for (int nn = 0; nn < 2; ++nn) acc[m][nn] = S::products(av, wc[nn], acc[m][nn]);
+        }
+    }
+}
+
+// The 1x1 form of SPLIT 2, 32 channels per stage: a thread requests 16 bytes of a 128-byte line whose other seven sixteenths are requested by
+// its neighbours in the same instruction (the 16-channel form takes half of every line now and the other half one chunk later: measured, the
+// activation requests alone cost that form 44 % of its time, profiles/r03_conv_sp3.txt section 8), and a barrier spans 48 MFMAs of a wave.
+// A different pipeline from pw_split_loop's: two k16 halves per stage, each half's weights requested behind its own MFMAs.
+template <int MT>
+__device__ __forceinline__ void pw_split32_loop(const ConvArgs& a, unsigned char* sb, i32x4 rsrc, int tid, int lane, int wm, int co0, long pix0,
+                                                long total_pix, f32x16 (&acc)[MT][2]) {
+    constexpr int NIT = 2 * MT;                             // 8 requests per thread and stage: row tid / 8 + 32 it, channels 4 (tid & 7) .. + 3 of the 32
+    constexpr int STAGE = 2 * MT * 2 * 2 * 64 * 16;         // bytes per LDS stage: [row block][k16 half][piece][lane][8 fp16]
+    const int oct = tid & 7;
+    int x_voff[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const long px = pix0 + it * 32 + (tid >> 3);
+        x_voff[it] = px < total_pix ? (int)((px * a.x_cs + a.x_co + oct * 4) * 4) : (int)0x80000000;
+    }
+    // row r = tid / 8 + 32 it is row (tid >> 3) of row block it; channels 4 oct .. : k16 half oct >> 2, lane half (oct & 3) >> 1, 8-byte half slot oct & 1
+    const int st_off = (((oct >> 2) * 2) * 64 + ((oct & 3) >> 1) * 32 + (tid >> 3)) * 16 + (oct & 1) * 8;
+    f32x4 xs[NIT];
+    auto load_X = [&](int c32) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) xs[it] = buffer_load_f32x4(rsrc, x_voff[it], c32 * 128, 0);
+    };
+    auto stage = [&](int buf) {
+        unsigned char* dst = sb + buf * STAGE + st_off;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            u32x2 h, m_;
+            split_f16(xs[it] * SPLIT_SX, h, m_);
+            *reinterpret_cast<u32x2*>(dst + it * (4 * 64 * 16)) = h;
+            *reinterpret_cast<u32x2*>(dst + it * (4 * 64 * 16) + 64 * 16) = m_;
+        }
+    };
+    const u32x4* wsp = reinterpret_cast<const u32x4*>(a.w) + ((long)(co0 >> 5) * 2) * 64 + lane;      // wave-uniform base + lane
+    const long wstep = (long)(a.cout_pad >> 5) * 2 * 64;                                               // per 16 channels
+    u32x4 wb[2][2][2];                  // [k16 half][cout tile][piece]
+    auto load_Bs = [&](int s_, int k16) {
+#pragma unroll
+        for (int nn = 0; nn < 2; ++nn)
+#pragma unroll
+            for (int p_ = 0; p_ < 2; ++p_) wb[s_][nn][p_] = wsp[k16 * wstep + (nn * 2 + p_) * 64];
+    };
+    const int n32 = a.Cin >> 5;
+    load_X(0);
+    load_Bs(0, 0);
+    load_Bs(1, 1);
+    stage(0);
+    load_X(min(1, n32 - 1));
+    for (int c = 0; c < n32; ++c) {
+        __syncthreads();            // stage c & 1 is complete; everybody has read all of the other stage
+        const u32x4* ap = reinterpret_cast<const u32x4*>(sb + (c & 1) * STAGE) + (wm * MT * 4) * 64 + lane;
+#pragma unroll
+        for (int s_ = 0; s_ < 2; ++s_) {
+            f16x8 Bhs[2];
+#pragma unroll
+            for (int nn = 0; nn < 2; ++nn) Bhs[nn] = split_f16_bhs(__builtin_bit_cast(f16x8, wb[s_][nn][0]));
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const u32x4 ah = ap[(m * 4 + s_ * 2 + 0) * 64], am = ap[(m * 4 + s_ * 2 + 1) * 64];
+                if (s_ == 0 && m == 2) {        // the next stage's activations (in registers since the last stage) are split between the MFMA groups
+                    stage((c + 1) & 1);
+                    load_X(min(c + 2, n32 - 1));
+                }
+                const f16x8 Ah = __builtin_bit_cast(f16x8, ah), Am = __builtin_bit_cast(f16x8, am);
+#pragma unroll
+                for (int nn = 0; nn < 2; ++nn)
+                    acc[m][nn] = mfma3_f16(Ah, Am, __builtin_bit_cast(f16x8, wb[s_][nn][0]), __builtin_bit_cast(f16x8, wb[s_][nn][1]), Bhs[nn], acc[m][nn]);
+            }
+            load_Bs(s_, min(2 * (c + 1) + s_, 2 * n32 - 1));     // this half of the next stage's weights: in flight during the other half's MFMAs
+        }
+    }
+}
 // POOL: also leave the per-block sums of the stored values in a.pool_ws (the eSE average pool of the aggregation conv, cmk.h)
 // GA ("gather"): a 3x3 conv (stride a.ga_stride = 1 | 2, padding 1) as the same GEMM over flattened OUTPUT pixels whose K walks 9 taps x Cin/16
 // chunks: the staged row of a thread is gathered per tap straight from the image (an offset outside the resource where the tap falls
@@ -51,7 +212,7 @@ __device__ f32x4 pw_buffer_load(i32x4 rsrc, int voffset, int soffset, int aux) _
 // The accumulator layout is the fp32 kernel's, so the epilogue (scale/shift/ReLU, stores, POOL sums) is shared.
 // SPLIT 2 (opt-in, cmk.h tune_wm 12): the same GEMM on TWO FP16 pieces per operand — 22 bits of significand, three products m*h, h*m, h*h (what
 // is dropped is 2^-22 of a product), half the MFMAs of the bf16 form for the same fp32-class error; fp16's exponent range is met by exact
-// power-of-two scaling as in conv_sp3.hip (activations x 2^-4, their residual x 2^11 and the weight piece it meets x 2^-11 in registers; the
+// power-of-two scaling (conv_split.hpp: activations x 2^-4, their residual x 2^11 and the weight piece it meets x 2^-11 in registers; the
 // weights x S_w on the host, a.p[0].acc_scale = 1 / S_w; the accumulator x 2^4 / S_w folded into the epilogue's per-channel scale).
 // a.w: [K/16][cout_pad/32][piece 2][lane 64][8 fp16] (cmk.h w_splith).
 template <int MT, bool POOL, bool GA, bool UPRES, bool SPLITK, int SPLIT = 0>
@@ -82,14 +243,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
 
     // ---- activations: global -> registers -> LDS ------------------------------------------------------------------------------------
     // thread = (row tid>>2 (+64 per iteration), channel quad tid&3); a row past the last pixel gets an offset outside the resource
-    i32x4 rsrc;
-    {
-        const unsigned long long base = (unsigned long long)P.x;
-        rsrc.x = __builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
-        rsrc.y = __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffffull));
-        rsrc.z = __builtin_amdgcn_readfirstlane((int)((GA ? (long)P.N * P.H * P.W : total_pix) * a.x_cs * 4));      // < 2^31 (host)
-        rsrc.w = 0x00020000;
-    }
+    const i32x4 rsrc = buffer_rsrc(P.x, (int)((GA ? (long)P.N * P.H * P.W : total_pix) * a.x_cs * 4));      // < 2^31 (host)
     int a_voff[MT];
     int ga_base[GA ? MT : 1], ga_hw[GA ? MT : 1];       // GA: byte offset of the window's top-left sample (may be negative), (ih0 << 16) | (iw0 & 0xffff)
 #pragma unroll
@@ -130,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
             }
         }
 #pragma unroll
-        for (int it = 0; it < MT; ++it) a_st[it] = pw_buffer_load(rsrc, a_voff[it], soff, 0);
+        for (int it = 0; it < MT; ++it) a_st[it] = buffer_load_f32x4(rsrc, a_voff[it], soff, 0);
     };
     auto store_A = [&](int buf) {
         float* dst = smem + buf * ABUF + a_dst;
@@ -145,322 +299,87 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
         for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][nn][r] = 0.f;
-    if constexpr (SPLIT == 2 && !GA) {
-        // 1x1 conv on two fp16 pieces, 32 channels per stage: a thread requests 16 bytes of a 128-byte line whose other seven sixteenths are requested by
-        // its neighbours in the same instruction (the 16-channel form takes half of every line now and the other half one chunk later: measured, the
-        // activation requests alone cost that form 44 % of its time, profiles/r03_conv_sp3.txt section 8), and a barrier spans 48 MFMAs of a wave
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        constexpr float SX = 0.0625f, RS = 2048.f;              // activation scale 2^-4, residual scale 2^11
-        constexpr int NIT = BM / 32;                            // 8 requests per thread and stage: row tid / 8 + 32 it, channels 4 (tid & 7) .. + 3 of the 32
-        constexpr int STAGE = (BM / 32) * 2 * 2 * 64 * 16;      // bytes per LDS stage: [row block][k16 half][piece][lane][8 fp16]
-        unsigned char* sb = reinterpret_cast<unsigned char*>(smem);
-        auto pk = [](float x, float y) { return __builtin_bit_cast(unsigned, f16x2{(_Float16)x, (_Float16)y}); };       // round to nearest even
-        auto unpk = [](unsigned p_) { const f16x2 h_ = __builtin_bit_cast(f16x2, p_); return f32x2{(float)h_.x, (float)h_.y}; };
-        const int oct = tid & 7;
-        int x_voff[NIT];
+    if constexpr (!SPLIT) {
+        // ---- weights: L2 -> registers; lane (li, hh) takes channels 8*hh .. 8*hh+7 of output channel (tile base + li) ---------------------
+        const float* wbase[2];
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const long px = pix0 + it * 32 + (tid >> 3);
-            x_voff[it] = px < total_pix ? (int)((px * a.x_cs + a.x_co + oct * 4) * 4) : (int)0x80000000;
-        }
-        // row r = tid / 8 + 32 it is row (tid >> 3) of row block it; channels 4 oct .. : k16 half oct >> 2, lane half (oct & 3) >> 1, 8-byte half slot oct & 1
-        const int st_off = (((oct >> 2) * 2) * 64 + ((oct & 3) >> 1) * 32 + (tid >> 3)) * 16 + (oct & 1) * 8;
-        f32x4 xs[NIT];
-        auto load_X = [&](int c32) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) xs[it] = pw_buffer_load(rsrc, x_voff[it], c32 * 128, 0);
-        };
-        auto stage = [&](int buf) {
-            unsigned char* dst = sb + buf * STAGE + st_off;
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const f32x4 x = xs[it] * SX;
-                u32x2 h, m_;
-                h.x = pk(x.x, x.y); h.y = pk(x.z, x.w);
-                const f32x2 h01 = unpk(h.x), h23 = unpk(h.y);
-                const f32x4 r1 = f32x4{x.x - h01.x, x.y - h01.y, x.z - h23.x, x.w - h23.y} * RS;      // exact: h holds the leading bits of x
-                m_.x = pk(r1.x, r1.y); m_.y = pk(r1.z, r1.w);
-                *reinterpret_cast<u32x2*>(dst + it * (4 * 64 * 16)) = h;
-                *reinterpret_cast<u32x2*>(dst + it * (4 * 64 * 16) + 64 * 16) = m_;
-            }
-        };
-        const u32x4* wsp = reinterpret_cast<const u32x4*>(a.w) + ((long)(co0 >> 5) * 2) * 64 + lane;      // wave-uniform base + lane
-        const long wstep = (long)(a.cout_pad >> 5) * 2 * 64;                                               // per 16 channels
-        u32x4 wb[2][2][2];                  // [k16 half][cout tile][piece]
-        auto load_Bs = [&](int s_, int k16) {
-#pragma unroll
-            for (int nn = 0; nn < 2; ++nn)
-#pragma unroll
-                for (int p_ = 0; p_ < 2; ++p_) wb[s_][nn][p_] = wsp[k16 * wstep + (nn * 2 + p_) * 64];
-        };
-        const int n32 = a.Cin >> 5;
-        load_X(0);
-        load_Bs(0, 0);
-        load_Bs(1, 1);
-        stage(0);
-        load_X(min(1, n32 - 1));
-        for (int c = 0; c < n32; ++c) {
-            __syncthreads();            // stage c & 1 is complete; everybody has read all of the other stage
-            const u32x4* ap = reinterpret_cast<const u32x4*>(sb + (c & 1) * STAGE) + (wm * MT * 4) * 64 + lane;
-#pragma unroll
-            for (int s_ = 0; s_ < 2; ++s_) {
-                f16x8 Bhs[2];
-#pragma unroll
-                for (int nn = 0; nn < 2; ++nn) Bhs[nn] = __builtin_bit_cast(f16x8, wb[s_][nn][0]) * (_Float16)(1.f / RS);      // meets the activations' scaled residual
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const u32x4 ah = ap[(m * 4 + s_ * 2 + 0) * 64], am = ap[(m * 4 + s_ * 2 + 1) * 64];
-                    if (s_ == 0 && m == 2) {        // the next stage's activations (in registers since the last stage) are split between the MFMA groups
-                        stage((c + 1) & 1);
-                        load_X(min(c + 2, n32 - 1));
-                    }
-                    const f16x8 Ah = __builtin_bit_cast(f16x8, ah), Am = __builtin_bit_cast(f16x8, am);
-#pragma unroll
-                    for (int nn = 0; nn < 2; ++nn) {
-                        f32x16 cacc = acc[m][nn];
-                        cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Am, Bhs[nn], cacc, 0, 0, 0);
-                        cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, __builtin_bit_cast(f16x8, wb[s_][nn][1]), cacc, 0, 0, 0);
-                        cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, __builtin_bit_cast(f16x8, wb[s_][nn][0]), cacc, 0, 0, 0);
-                        acc[m][nn] = cacc;
-                    }
-                }
-                load_Bs(s_, min(2 * (c + 1) + s_, 2 * n32 - 1));     // this half of the next stage's weights: in flight during the other half's MFMAs
-            }
-        }
-        __syncthreads();                // the epilogue may reuse the LDS
-    } else if constexpr (SPLIT == 2) {
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        constexpr float SX = 0.0625f, RS = 2048.f;              // activation scale 2^-4, residual scale 2^11
-        constexpr int STAGE = (BM / 32) * 2 * 64 * 16;          // bytes per LDS stage: [row block][piece][lane][8 fp16]
-        unsigned char* sb = reinterpret_cast<unsigned char*>(smem);
-        auto pk = [](float x, float y) { return __builtin_bit_cast(unsigned, f16x2{(_Float16)x, (_Float16)y}); };       // round to nearest even
-        auto unpk = [](unsigned p_) { const f16x2 h_ = __builtin_bit_cast(f16x2, p_); return f32x2{(float)h_.x, (float)h_.y}; };
-        int st_off[MT];
-#pragma unroll
-        for (int it = 0; it < MT; ++it) {
-            const int r = (tid >> 2) + 64 * it;
-            st_off[it] = (((r >> 5) * 2) * 64 + ((tid & 3) >> 1) * 32 + (r & 31)) * 16 + (tid & 1) * 8;
-        }
-        auto stage = [&](int buf) {
-            unsigned char* dst = sb + buf * STAGE;
-#pragma unroll
-            for (int it = 0; it < MT; ++it) {
-                const f32x4 x = a_st[it] * SX;
-                u32x2 h, m_;
-                h.x = pk(x.x, x.y); h.y = pk(x.z, x.w);
-                const f32x2 h01 = unpk(h.x), h23 = unpk(h.y);
-                const f32x4 r1 = f32x4{x.x - h01.x, x.y - h01.y, x.z - h23.x, x.w - h23.y} * RS;      // exact: h holds the leading bits of x
-                m_.x = pk(r1.x, r1.y); m_.y = pk(r1.z, r1.w);
-                *reinterpret_cast<u32x2*>(dst + st_off[it]) = h;
-                *reinterpret_cast<u32x2*>(dst + st_off[it] + 64 * 16) = m_;
-            }
-        };
-        const u32x4* wsp = reinterpret_cast<const u32x4*>(a.w) + ((long)(co0 >> 5) * 2) * 64 + lane;      // wave-uniform base + lane
-        const long wstep = (long)(a.cout_pad >> 5) * 2 * 64;
-        u32x4 wb[2][2];
-        auto load_Bs = [&](int chunk) {
-#pragma unroll
-            for (int nn = 0; nn < 2; ++nn)
-#pragma unroll
-                for (int p_ = 0; p_ < 2; ++p_) wb[nn][p_] = wsp[chunk * wstep + (nn * 2 + p_) * 64];
-        };
-        load_A(0);
-        load_Bs(0);
-        stage(0);
-        load_A(min(1, nchunks - 1));
-        for (int c = 0; c < nchunks; ++c) {
-            __syncthreads();            // stage c & 1 is complete; everybody has read all of the other stage
-            const u32x4* ap = reinterpret_cast<const u32x4*>(sb + (c & 1) * STAGE) + (wm * MT * 2) * 64 + lane;
-            f16x8 Bh[2], Bm[2], Bhs[2];
+        for (int nn = 0; nn < 2; ++nn) wbase[nn] = a.w + (long)min(co0 + nn * 32, a.cout_pad - 32) * 16;     // wave-uniform
+        const long w_chunk = (long)a.cout_pad * 16;
+        const unsigned w_lane = li * 16 + hh * 8;
+        f32x4 bq[2][2][2];                  // [register set][cout tile][k-steps 0..3 | 4..7]
+        auto load_B = [&](int chunk, int set) {
 #pragma unroll
             for (int nn = 0; nn < 2; ++nn) {
-                Bh[nn] = __builtin_bit_cast(f16x8, wb[nn][0]);
-                Bm[nn] = __builtin_bit_cast(f16x8, wb[nn][1]);
-                Bhs[nn] = Bh[nn] * (_Float16)(1.f / RS);        // meets the activations' scaled residual
+                const float* src = wbase[nn] + chunk * w_chunk;
+                bq[set][nn][0] = *reinterpret_cast<const f32x4*>(src + w_lane);
+                bq[set][nn][1] = *reinterpret_cast<const f32x4*>(src + (w_lane + 4));
             }
-            load_Bs(min(c + 1, nchunks - 1));
+        };
+
+        // ---- MFMA side --------------------------------------------------------------------------------------------------------------------
+        int a_off[MT];
 #pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const u32x4 ah = ap[(m * 2 + 0) * 64], am = ap[(m * 2 + 1) * 64];
-                if (m == 1) {           // the next chunk's activations (in registers since the last chunk) are split between the MFMA groups
-                    stage((c + 1) & 1);
-                    load_A(min(c + 2, nchunks - 1));
-                }
-                const f16x8 Ah = __builtin_bit_cast(f16x8, ah), Am = __builtin_bit_cast(f16x8, am);
+        for (int m = 0; m < MT; ++m) a_off[m] = ((wm * MT + m) * 32 + li) * PST + hh * 8;
+        f32x4 avA[MT], avB[MT];             // operands of the first / second half (4 k-steps each) of a chunk
+        auto rd = [&](f32x4 (&v)[MT], int buf, int h) {
+            const float* A = smem + buf * ABUF + 4 * h;
 #pragma unroll
-                for (int nn = 0; nn < 2; ++nn) {
-                    f32x16 cacc = acc[m][nn];
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Am, Bhs[nn], cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bm[nn], cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[nn], cacc, 0, 0, 0);
-                    acc[m][nn] = cacc;
-                }
+            for (int m = 0; m < MT; ++m) v[m] = *reinterpret_cast<const f32x4*>(A + a_off[m]);
+        };
+        // 4 k-steps: channels 4h..4h+3 (lane half 0) and 8+4h..8+4h+3 (lane half 1) of the chunk — conv_igemm's order
+        auto mh = [&](const f32x4 (&v)[MT], int set, int h) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+#pragma unroll
+                    for (int nn = 0; nn < 2; ++nn)
+                        acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[m][s], bq[set][nn][h][s], acc[m][nn], 0, 0, 0);
+        };
+
+        // ---- pipeline ------------------------------------------------------------------------------------------------------------------
+        // chunk c, LDS buffer u = c & 1, weight set u:
+        //   read the second-half operands of chunk c; 32 MFMAs of the first half, among them: A(c+1) (in registers since chunk c-1) into
+        //   buffer u^1, request A(c+2)
+        //   barrier: buffer u^1 is complete, everybody has read all of buffer u
+        //   read the first-half operands of chunk c+1; 32 MFMAs of the second half; request B(c+2) into set u
+        // No MFMA waits for an LDS round trip (each read has 32 MFMAs to land), the activations have a whole chunk to arrive, the weights
+        // more.  Measured with the trace build: reading all of a chunk's operands behind its barrier cost a wave alone on its SIMD 700 of
+        // 4800 cycles per chunk.
+        // The fences pin the order of the prologue's requests: the compiler's wait counts at the loop head are the minimum over the prologue's
+        // and the loop's order, so a weight request scheduled late there makes every chunk wait for younger loads than it needs.
+        load_A(c_lo);
+        __builtin_amdgcn_sched_barrier(0);
+        load_B(c_lo, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        store_A(0);
+        load_A(c_lo + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        load_B(c_lo + 1, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        rd(avA, 0, 0);
+        for (int c = c_lo; c < nchunks; c += 2) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                rd(avB, u, 1);
+                mh(avA, u, 0);
+                store_A(u ^ 1);
+                load_A(min(c + u + 2, nchunks - 1));
+                __builtin_amdgcn_sched_barrier(0);      // (the compiler otherwise moves the second half's MFMAs in front of the barrier)
+                __syncthreads();
+                rd(avA, u ^ 1, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                mh(avB, u, 1);
+                load_B(min(c + u + 2, nchunks - 1), u);
             }
         }
-        __syncthreads();                // the epilogue may reuse the LDS
-    } else if constexpr (SPLIT == 1) {
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-        constexpr int STAGE = (BM / 32) * 3 * 64 * 16;          // bytes per LDS stage: [row block][piece][lane][8 bf16]
+    } else {        // the opt-in split-product forms: the same tile and epilogue around a K loop of their own (above)
         unsigned char* sb = reinterpret_cast<unsigned char*>(smem);
-        auto pk = [](float x, float y) { unsigned r; asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; };
-        auto f_lo = [](unsigned p_) { return __builtin_bit_cast(float, p_ << 16); };
-        auto f_hi = [](unsigned p_) { return __builtin_bit_cast(float, p_ & 0xffff0000u); };
-        // this thread's 8-byte half slots: row r = tid / 4 + 64 it -> (block r / 32, li = r % 32); quad tid & 3 -> lane half (tid & 3) / 2, half slot (tid & 3) & 1
-        int st_off[MT];
-#pragma unroll
-        for (int it = 0; it < MT; ++it) {
-            const int r = (tid >> 2) + 64 * it;
-            st_off[it] = (((r >> 5) * 3) * 64 + ((tid & 3) >> 1) * 32 + (r & 31)) * 16 + (tid & 1) * 8;
-        }
-        auto stage = [&](int buf) {
-            unsigned char* dst = sb + buf * STAGE;
-#pragma unroll
-            for (int it = 0; it < MT; ++it) {
-                const f32x4 x = a_st[it];
-                u32x2 h, m_, l;
-                h.x = pk(x.x, x.y); h.y = pk(x.z, x.w);
-                const f32x4 r1 = {x.x - f_lo(h.x), x.y - f_hi(h.x), x.z - f_lo(h.y), x.w - f_hi(h.y)};
-                m_.x = pk(r1.x, r1.y); m_.y = pk(r1.z, r1.w);
-                const f32x4 r2 = {r1.x - f_lo(m_.x), r1.y - f_hi(m_.x), r1.z - f_lo(m_.y), r1.w - f_hi(m_.y)};
-                *reinterpret_cast<u32x2*>(dst + st_off[it]) = h;
-                *reinterpret_cast<u32x2*>(dst + st_off[it] + 64 * 16) = m_;
-                l.x = pk(r2.x, r2.y); l.y = pk(r2.z, r2.w);
-                *reinterpret_cast<u32x2*>(dst + st_off[it] + 2 * 64 * 16) = l;
-            }
-        };
-        const u32x4* wsp = reinterpret_cast<const u32x4*>(a.w) + ((long)(co0 >> 5) * 3) * 64 + lane;      // wave-uniform base + lane
-        const long wstep = (long)(a.cout_pad >> 5) * 3 * 64;
-        u32x4 wb[2][3];
-        auto load_Bs = [&](int chunk) {
-#pragma unroll
-            for (int nn = 0; nn < 2; ++nn)
-#pragma unroll
-                for (int p_ = 0; p_ < 3; ++p_) wb[nn][p_] = wsp[chunk * wstep + (nn * 3 + p_) * 64];
-        };
-        // (GA: load_A walks the 9 taps x Cin / 16 chunks in order, re-pointing the rows per tap; the split weights are packed tap-major to match)
-        load_A(0);
-        load_Bs(0);
-        stage(0);
-        load_A(min(1, nchunks - 1));
-        for (int c = 0; c < nchunks; ++c) {
-            __syncthreads();            // stage c & 1 is complete; everybody has read all of the other stage
-            const u32x4* ap = reinterpret_cast<const u32x4*>(sb + (c & 1) * STAGE) + (wm * MT * 3) * 64 + lane;
-            u32x4 wc[2][3];
-#pragma unroll
-            for (int nn = 0; nn < 2; ++nn)
-#pragma unroll
-                for (int p_ = 0; p_ < 3; ++p_) wc[nn][p_] = wb[nn][p_];
-            load_Bs(min(c + 1, nchunks - 1));
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const u32x4 ah = ap[(m * 3 + 0) * 64], am = ap[(m * 3 + 1) * 64], al = ap[(m * 3 + 2) * 64];
-                if (m == 1) {           // the next chunk's activations (in registers since the last chunk) are split between the MFMA groups
-                    stage((c + 1) & 1);
-                    load_A(min(c + 2, nchunks - 1));
-                }
-                const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah), Am = __builtin_bit_cast(bf16x8, am), Al = __builtin_bit_cast(bf16x8, al);
-#pragma unroll
-                for (int nn = 0; nn < 2; ++nn) {
-                    const bf16x8 Bh = __builtin_bit_cast(bf16x8, wc[nn][0]), Bm = __builtin_bit_cast(bf16x8, wc[nn][1]), Bl = __builtin_bit_cast(bf16x8, wc[nn][2]);
-                    f32x16 cacc = acc[m][nn];
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, cacc, 0, 0, 0);
-                    acc[m][nn] = cacc;
-                }
-            }
-        }
+        if constexpr (SPLIT == 2 && !GA) pw_split32_loop<MT>(a, sb, rsrc, tid, lane, wm, co0, pix0, total_pix, acc);
+        else pw_split_loop<std::conditional_t<SPLIT == 1, PwSplitBf16, PwSplitF16>, MT>(a, sb, tid, lane, wm, co0, nchunks, a_st, load_A, acc);
         __syncthreads();                // the epilogue may reuse the LDS
-    } else {
-    // ---- weights: L2 -> registers; lane (li, hh) takes channels 8*hh .. 8*hh+7 of output channel (tile base + li) ---------------------
-    const float* wbase[2];
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn) wbase[nn] = a.w + (long)min(co0 + nn * 32, a.cout_pad - 32) * 16;     // wave-uniform
-    const long w_chunk = (long)a.cout_pad * 16;
-    const unsigned w_lane = li * 16 + hh * 8;
-    f32x4 bq[2][2][2];                  // [register set][cout tile][k-steps 0..3 | 4..7]
-    auto load_B = [&](int chunk, int set) {
-#pragma unroll
-        for (int nn = 0; nn < 2; ++nn) {
-            const float* src = wbase[nn] + chunk * w_chunk;
-            bq[set][nn][0] = *reinterpret_cast<const f32x4*>(src + w_lane);
-            bq[set][nn][1] = *reinterpret_cast<const f32x4*>(src + (w_lane + 4));
-        }
-    };
-
-    // ---- MFMA side --------------------------------------------------------------------------------------------------------------------
-    int a_off[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) a_off[m] = ((wm * MT + m) * 32 + li) * PST + hh * 8;
-    f32x4 avA[MT], avB[MT];             // operands of the first / second half (4 k-steps each) of a chunk
-    auto rd = [&](f32x4 (&v)[MT], int buf, int h) {
-        const float* A = smem + buf * ABUF + 4 * h;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) v[m] = *reinterpret_cast<const f32x4*>(A + a_off[m]);
-    };
-    // 4 k-steps: channels 4h..4h+3 (lane half 0) and 8+4h..8+4h+3 (lane half 1) of the chunk — conv_igemm's order
-    auto mh = [&](const f32x4 (&v)[MT], int set, int h) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int nn = 0; nn < 2; ++nn)
-                    acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[m][s], bq[set][nn][h][s], acc[m][nn], 0, 0, 0);
-    };
-
-    // ---- pipeline ------------------------------------------------------------------------------------------------------------------
-    // chunk c, LDS buffer u = c & 1, weight set u:
-    //   read the second-half operands of chunk c; 32 MFMAs of the first half, among them: A(c+1) (in registers since chunk c-1) into
-    //   buffer u^1, request A(c+2)
-    //   barrier: buffer u^1 is complete, everybody has read all of buffer u
-    //   read the first-half operands of chunk c+1; 32 MFMAs of the second half; request B(c+2) into set u
-    // No MFMA waits for an LDS round trip (each read has 32 MFMAs to land), the activations have a whole chunk to arrive, the weights
-    // more.  Measured with the trace build: reading all of a chunk's operands behind its barrier cost a wave alone on its SIMD 700 of
-    // 4800 cycles per chunk.
-    // The fences pin the order of the prologue's requests: the compiler's wait counts at the loop head are the minimum over the prologue's
-    // and the loop's order, so a weight request scheduled late there makes every chunk wait for younger loads than it needs.
-    load_A(c_lo);
-    __builtin_amdgcn_sched_barrier(0);
-    load_B(c_lo, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    store_A(0);
-    load_A(c_lo + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    load_B(c_lo + 1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-    rd(avA, 0, 0);
-    for (int c = c_lo; c < nchunks; c += 2) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            rd(avB, u, 1);
-            mh(avA, u, 0);
-            store_A(u ^ 1);
-            load_A(min(c + u + 2, nchunks - 1));
-            __builtin_amdgcn_sched_barrier(0);      // (the compiler otherwise moves the second half's MFMAs in front of the barrier)
-            __syncthreads();
-            rd(avA, u ^ 1, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            mh(avB, u, 1);
-            load_B(min(c + u + 2, nchunks - 1), u);
-        }
     }
-
-    }       // fp32-MFMA operand path
     // ---- epilogue: scale/shift (+same-size residual) (+ReLU), NHWC stores ------------------------------------------------------------------------
     // accumulator register r of lane half hh is pixel row (r & 3) + 8 * (r >> 2) + 4 * hh of the 32-pixel sub-tile; the lane is the cout
     const long wpix0 = pix0 + wm * (MT * 32);
@@ -506,7 +425,6 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
         constexpr bool INTERIOR = decltype(interior_tag)::value;
 #pragma unroll
         for (int nn = 0; nn < 2; ++nn) {
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
             f32x2 pool2 = {0.f, 0.f};             // sums of this lane's stored values: rows before / from `bnd` (INTERIOR without a boundary: .x and .y are two halves of one sum)
             float poolA = 0.f, poolB = 0.f;
             const int co = co0 + nn * 32 + li;
@@ -525,9 +443,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs a) {
                 // asm because the compiler renders the same C as 64-bit vector adds: 5 VALU per value, trace build: 37k-cycle epilogues).
                 const f32x2 sc2 = {sc, sc}, sh2 = {sh, sh};
                 const unsigned voff = (unsigned)(4 * hh * a.y_cs + a.y_co + co) * 4u;
-                const unsigned long long yb = (unsigned long long)ybase;
-                unsigned long long rowp = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(yb >> 32)) << 32) |
-                                          (unsigned)__builtin_amdgcn_readfirstlane((int)yb);
+                unsigned long long rowp = wave_uniform_u64(ybase);
                 const unsigned long long row1 = (unsigned long long)a.y_cs * 4u, row5 = row1 * 5u;
                 float rv[UPRES ? MT : 1][8];
                 if constexpr (UPRES) {
@@ -631,44 +547,43 @@ static int launch_pw_mt(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     return check_launch("conv_pw");
 }
 
+// the input view and output row bounds of both front doors; `who` is the door's name in its refusals
+static int pw_check_sizes(const ConvArgs& a, const char* who) {
+    const ConvProblem& p = a.p[0];
+    const long in_pix = a.ga_stride ? (long)p.N * p.H * p.W : p.total_pix;
+    if (in_pix * a.x_cs * 4 >= (1L << 31)) return fail(CMK_EINVAL, "%s: input view of 2 GiB or more", who);
+    if ((long)(64 * 4 + 8) * a.y_cs >= (1L << 30) || (long)(64 * 4 + 8) * a.res_cs >= (1L << 30)) return fail(CMK_EINVAL, "%s: output row too wide", who);
+    return CMK_OK;
+}
+
 // mt = 4 | 2.  The caller (conv.hip: run) has filled the problem, views, epilogue options and cout_pad; a.ga_stride = 1 | 2 asks for
 // the gather form of a 3x3 conv (a.w then is conv_igemm's 9-tap packing), 0 for a 1x1 conv.
 int launch_pw(ConvArgs& a, int mt, hipStream_t st, LaunchPlan* plan) {
     const ConvProblem& p = a.p[0];
     if (a.nprob != 1 || p.in_scale || a.in_relu || a.gn_ws)
         return fail(CMK_EINVAL, "conv_pw: one problem, no input affine / input ReLU / GroupNorm statistics%s", "");
-    if (a.ksplit > 1) {             // raw partial sums into a.ws; the caller reduces
-        const int nch = (a.ga_stride ? 9 : 1) * (a.Cin >> 4);
-        if (!a.ws || a.res_mode == 2 || a.pool_ws || nch % (2 * a.ksplit))
+    const bool splitk = a.ksplit > 1, ga = a.ga_stride != 0, upres = a.res_mode == 2;
+    if (splitk) {                   // raw partial sums into a.ws; the caller reduces
+        const int nch = (ga ? 9 : 1) * (a.Cin >> 4);
+        if (!a.ws || upres || a.pool_ws || nch % (2 * a.ksplit))
             return fail(CMK_EINVAL, "conv_pw: split-K needs a workspace, K chunks %% (2*splitk) == 0, no upsampled residual / pooled sums%s", "");
-        if (a.ga_stride) return mt == 4 ? launch_pw_mt<4, false, true, false, true>(a, st, plan) : mt == 2 ? launch_pw_mt<2, false, true, false, true>(a, st, plan)
-                                                                                                      : fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
-        return mt == 4 ? launch_pw_mt<4, false, false, false, true>(a, st, plan) : mt == 2 ? launch_pw_mt<2, false, false, false, true>(a, st, plan)
-                                                                                     : fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
-    }
-    if (a.res_mode == 2) {          // FPN top-down add
-        if (a.ga_stride || a.pool_ws || (p.Wo & 1) || (long)p.N * a.Hr * a.Wr * a.res_cs * 4 >= (1L << 31))
+    } else {
+        if (upres && (ga || a.pool_ws || (p.Wo & 1) || (long)p.N * a.Hr * a.Wr * a.res_cs * 4 >= (1L << 31)))      // FPN top-down add
             return fail(CMK_EINVAL, "conv_pw: the upsampled residual needs a 1x1 conv, an even output width, no pooled sums, a residual below 2 GiB%s", "");
+        if ((a.Cin & 31) || (a.cout_pad & 127)) return fail(CMK_EINVAL, "conv_pw: needs Cin %% 32 == 0 and Cout in 97..128 or > 224%s", "");
+        if (int rc = pw_check_sizes(a, "conv_pw")) return rc;
+        if (ga && (a.pool_ws || p.H >= 32768 || p.W >= 32768)) return fail(CMK_EINVAL, "conv_pw: gather form: no pooled sums, maps below 32768 x 32768%s", "");
+        if (a.pool_ws && (long)p.Ho * p.Wo < 32 * mt) return fail(CMK_EINVAL, "conv_pw: pooled sums need H*W >= the block of %s%ld rows", "", 32 * mt);
     }
-    if ((a.Cin & 31) || (a.cout_pad & 127)) return fail(CMK_EINVAL, "conv_pw: needs Cin %% 32 == 0 and Cout in 97..128 or > 224%s", "");
-    const long in_pix = a.ga_stride ? (long)p.N * p.H * p.W : p.total_pix;
-    if (in_pix * a.x_cs * 4 >= (1L << 31)) return fail(CMK_EINVAL, "conv_pw: input view of 2 GiB or more%s", "");
-    if ((long)(64 * 4 + 8) * a.y_cs >= (1L << 30) || (long)(64 * 4 + 8) * a.res_cs >= (1L << 30)) return fail(CMK_EINVAL, "conv_pw: output row too wide%s", "");
-    if (a.ga_stride) {
-        if (a.pool_ws || p.H >= 32768 || p.W >= 32768) return fail(CMK_EINVAL, "conv_pw: gather form: no pooled sums, maps below 32768 x 32768%s", "");
-        if (mt == 4) return launch_pw_mt<4, false, true>(a, st, plan);
-        if (mt == 2) return launch_pw_mt<2, false, true>(a, st, plan);
-        return fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
-    }
-    if (a.pool_ws && (long)p.Ho * p.Wo < 32 * mt) return fail(CMK_EINVAL, "conv_pw: pooled sums need H*W >= the block of %s%ld rows", "", 32 * mt);
-    if (a.res_mode == 2) {
-        if (mt == 4) return launch_pw_mt<4, false, false, true>(a, st, plan);
-        if (mt == 2) return launch_pw_mt<2, false, false, true>(a, st, plan);
-        return fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
-    }
-    if (mt == 4) return a.pool_ws ? launch_pw_mt<4, true, false>(a, st, plan) : launch_pw_mt<4, false, false>(a, st, plan);
-    if (mt == 2) return a.pool_ws ? launch_pw_mt<2, true, false>(a, st, plan) : launch_pw_mt<2, false, false>(a, st, plan);
-    return fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
+    if (mt != 4 && mt != 2) return fail(CMK_EINVAL, "conv_pw: tile height must be 4 or 2%s", "");
+    auto launch = [&](auto mt_tag) {
+        constexpr int MT = decltype(mt_tag)::value;
+        if (splitk) return ga ? launch_pw_mt<MT, false, true, false, true>(a, st, plan) : launch_pw_mt<MT, false, false, false, true>(a, st, plan);
+        if (ga) return launch_pw_mt<MT, false, true>(a, st, plan);
+        if (upres) return launch_pw_mt<MT, false, false, true>(a, st, plan);
+        return a.pool_ws ? launch_pw_mt<MT, true, false>(a, st, plan) : launch_pw_mt<MT, false, false>(a, st, plan);
+    };
+    return mt == 4 ? launch(std::integral_constant<int, 4>{}) : launch(std::integral_constant<int, 2>{});
 }
 
 // The split forms (cmk.h tune_wm 10: three bf16 pieces, six products; 12: two fp16 pieces, three products): a.w is the split packing; plain 1x1
@@ -679,9 +594,7 @@ static int launch_pw_split_mode(ConvArgs& a, hipStream_t st, LaunchPlan* plan) {
     if (a.nprob != 1 || p.in_scale || a.in_relu || a.gn_ws || a.ksplit > 1 || a.res_mode == 1)
         return fail(CMK_EINVAL, "conv_pw (split): one problem, no input affine / input ReLU / GroupNorm statistics / split-K / same-size residual%s", "");
     if ((a.Cin & 15) || (a.cout_pad & 127)) return fail(CMK_EINVAL, "conv_pw (split): needs Cin %% 16 == 0 and a cout padding of 128%s", "");
-    const long in_pix = a.ga_stride ? (long)p.N * p.H * p.W : p.total_pix;
-    if (in_pix * a.x_cs * 4 >= (1L << 31)) return fail(CMK_EINVAL, "conv_pw (split): input view of 2 GiB or more%s", "");
-    if ((long)(64 * 4 + 8) * a.y_cs >= (1L << 30) || (long)(64 * 4 + 8) * a.res_cs >= (1L << 30)) return fail(CMK_EINVAL, "conv_pw (split): output row too wide%s", "");
+    if (int rc = pw_check_sizes(a, "conv_pw (split)")) return rc;
     if (a.ga_stride) {              // 3x3 conv (stride 1 | 2) as the gather GEMM over 9 taps
         if (a.pool_ws || a.res_mode || p.H >= 32768 || p.W >= 32768) return fail(CMK_EINVAL, "conv_pw (split): gather form: no pooled sums / residual, maps below 32768 x 32768%s", "");
         return launch_pw_mt<4, false, true, false, false, SPLIT>(a, st, plan);

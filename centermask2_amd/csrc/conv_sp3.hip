@@ -7,13 +7,7 @@
 // representation error is a third of an fp32 GEMM's own accumulation error (profiles/r03_conv_sp3.txt section 3), i.e. the result carries the
 // error of an fp32 accumulation.  (Two BF16 pieces, 16 bits, were built first and measured 5x the fp32 path's end-to-end error: reg 1.4e-3 against
 // the 1e-3 bar; three bf16 pieces / six products are fp32-accurate but slower than Winograd on a 3x3 conv — same file.)
-// fp16's narrow exponent is handled by scaling, all powers of two (exact):
-//   activations  x' = x * 2^-4 (|x| up to 1e6 stays finite); the residual is stored as fp16((x' - h) * 2^11), so it keeps 11 bits down to
-//                |x| = 2^-21 (unscaled it would be subnormal below |x| = 0.06), and the weight piece it meets is multiplied by 2^-11 in
-//                registers (4 packed multiplies per tap and cout tile);
-//   weights      w' = w * S_w with S_w the power of two that puts max |w'| in [2^14, 2^15) (host, per conv): both pieces of every weight
-//                larger than 2^-17 of the largest are normal fp16;
-//   the accumulator is multiplied by 2^4 / S_w in the epilogue (folded into the per-channel scale).
+// fp16's narrow exponent is handled by scaling, all powers of two (exact): conv_split.hpp, which holds the split and the three products.
 // No transform, so no Winograd error amplification either.
 //
 // What the gather form of conv_pw.hip (tune_wm 10 / 12 on a 3x3 conv) pays nine times — the activation load, the split, the LDS write — is
@@ -38,12 +32,9 @@
 
 #include <type_traits>
 
-#include "conv_args.hpp"
+#include "conv_split.hpp"
 
 namespace cmk {
-
-typedef int sp3_i32x4 __attribute__((ext_vector_type(4)));
-__device__ f32x4 sp3_buffer_load(sp3_i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
 
 template <int GEO> struct SP3G;
 template <> struct SP3G<0> { static constexpr int WCOLS = 2, BR = 2, BC = 4; };
@@ -69,8 +60,6 @@ template <int GEO, int NB, int P, bool AFF>
 __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     typedef SP3G<GEO> G;
     typedef SP3L<GEO, P> L;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     constexpr int WROWS = L::WROWS;
     constexpr int IT = L::IT;
     static_assert((IT - 1) * 256 < L::ITEMS && IT <= 8, "only a thread's last staging item may fall outside the halo; the requests are spread over 8 slots");
@@ -102,14 +91,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     const int cb0 = (by * G::WCOLS + wc) * NB;          // this wave's first cout tile of 32
 
     // ---- staging set-up: item idx = it * 256 + tid -> halo pixel idx >> 2, channel quad idx & 3 (= tid & 3) -----------------------------------
-    sp3_i32x4 rsrc;
-    {
-        const unsigned long long base = (unsigned long long)Pb.x;
-        rsrc.x = __builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
-        rsrc.y = __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffffull));
-        rsrc.z = __builtin_amdgcn_readfirstlane((int)((long)Pb.N * H * W * a.x_cs * 4));      // < 2^31 (host)
-        rsrc.w = 0x00020000;
-    }
+    const i32x4 rsrc = buffer_rsrc(Pb.x, (int)((long)Pb.N * H * W * a.x_cs * 4));      // < 2^31 (host)
     const int q = tid & 3;
     int st_voff[IT], st_dst[IT];        // byte offset into x (outside the resource: zeros), byte offset into a stage (-1: no item)
 #pragma unroll
@@ -125,24 +107,18 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     }
     f32x4 st[IT];
     auto load_X1 = [&](int chunk, int it) {
-        st[it] = sp3_buffer_load(rsrc, st_voff[it], chunk * 64, 0);
+        st[it] = buffer_load_f32x4(rsrc, st_voff[it], chunk * 64, 0);
     };
     auto load_X = [&](int chunk) {
 #pragma unroll
         for (int it = 0; it < IT; ++it) load_X1(chunk, it);
     };
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    constexpr float SX = 0.0625f, RS = 2048.f;       // activation scale 2^-4, residual scale 2^11
-    auto pk = [](float x, float y) { return __builtin_bit_cast(unsigned, f16x2{(_Float16)x, (_Float16)y}); };       // round to nearest even
-    auto unpk = [](unsigned p_) { const f16x2 h_ = __builtin_bit_cast(f16x2, p_); return f32x2{(float)h_.x, (float)h_.y}; };
     auto stage = [&](int buf, int chunk) {
         unsigned char* dst = sb + buf * L::STAGE;
-        f32x4 isc = {SX, SX, SX, SX}, ish = {0.f, 0.f, 0.f, 0.f};
+        f32x4 isc = {SPLIT_SX, SPLIT_SX, SPLIT_SX, SPLIT_SX}, ish = {0.f, 0.f, 0.f, 0.f};
         if constexpr (AFF) {
-            isc = *reinterpret_cast<const f32x4*>(Pb.in_scale + (long)n * a.Cin + chunk * 16 + q * 4) * SX;
-            ish = *reinterpret_cast<const f32x4*>(Pb.in_shift + (long)n * a.Cin + chunk * 16 + q * 4) * SX;
+            isc = *reinterpret_cast<const f32x4*>(Pb.in_scale + (long)n * a.Cin + chunk * 16 + q * 4) * SPLIT_SX;
+            ish = *reinterpret_cast<const f32x4*>(Pb.in_shift + (long)n * a.Cin + chunk * 16 + q * 4) * SPLIT_SX;
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
@@ -154,13 +130,10 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
                 x.z = in ? fmaxf(fmaf(x.z, isc.z, ish.z), 0.f) : 0.f;
                 x.w = in ? fmaxf(fmaf(x.w, isc.w, ish.w), 0.f) : 0.f;
             } else {
-                x *= SX;
+                x *= SPLIT_SX;
             }
             u32x2 h, m_;
-            h.x = pk(x.x, x.y); h.y = pk(x.z, x.w);
-            const f32x2 h01 = unpk(h.x), h23 = unpk(h.y);
-            const f32x4 r1 = f32x4{x.x - h01.x, x.y - h01.y, x.z - h23.x, x.w - h23.y} * RS;      // exact: h holds the leading bits of x
-            m_.x = pk(r1.x, r1.y); m_.y = pk(r1.z, r1.w);
+            split_f16(x, h, m_);
             if (it < IT - 1 || st_dst[it] >= 0) {
                 *reinterpret_cast<u32x2*>(dst + st_dst[it]) = h;
                 *reinterpret_cast<u32x2*>(dst + st_dst[it] + 2 * L::PLANE) = m_;
@@ -171,14 +144,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     // ---- weights: wave-uniform base + lane ----------------------------------------------------------------------------------------------------
     // (problems of one launch may differ in weights: the two FCOS towers)  Buffer loads: the lane offset is the only vector operand, the
     // position of the (tap, chunk, cout tile, piece) KiB is a scalar offset — no 64-bit vector address arithmetic per request
-    sp3_i32x4 wrsrc;
-    {
-        const unsigned long long base = (unsigned long long)Pb.w;
-        wrsrc.x = __builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
-        wrsrc.y = __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffffull));
-        wrsrc.z = __builtin_amdgcn_readfirstlane(9 * nchunks * nblocks * P * 1024);       // < 2^31 (host)
-        wrsrc.w = 0x00020000;
-    }
+    const i32x4 wrsrc = buffer_rsrc(Pb.w, 9 * nchunks * nblocks * P * 1024);       // < 2^31 (host)
     const int wlane = lane * 16;
     int wblk[NB];
 #pragma unroll
@@ -192,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < NB * P; ++j)
             if (part < 0 || part == j)
-                wq[set][j / P][j % P] = __builtin_bit_cast(u32x4, sp3_buffer_load(wrsrc, wlane, (int)(k + wblk[j / P] + (j % P) * 64) * 16, 0));
+                wq[set][j / P][j % P] = __builtin_bit_cast(u32x4, buffer_load_f32x4(wrsrc, wlane, (int)(k + wblk[j / P] + (j % P) * 64) * 16, 0));
     };
 
     // ---- A operand addresses: patch b = wr * 4 + m -> (b / BC, b % BC); lane -> pixel (li >> 3, li & 7) of the patch, k half hh ----------------
@@ -257,16 +223,12 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
                 if (m == 0) {
 #pragma unroll
                     for (int nn = 0; nn < NB; ++nn)
-                        Bhs[nn] = __builtin_bit_cast(f16x8, wq[set][nn][0]) * (_Float16)(1.f / RS);
+                        Bhs[nn] = split_f16_bhs(__builtin_bit_cast(f16x8, wq[set][nn][0]));
                 }
 #pragma unroll
                 for (int nn = 0; nn < NB; ++nn) {
                     const f16x8 Bh = __builtin_bit_cast(f16x8, wq[set][nn][0]), Bm = __builtin_bit_cast(f16x8, wq[set][nn][1]);
-                    f32x16 cacc = acc[m][nn];
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Am, Bhs[nn], cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bm, cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, cacc, 0, 0, 0);
-                    acc[m][nn] = cacc;
+                    acc[m][nn] = mfma3_f16(Ah, Am, Bh, Bm, Bhs[nn], acc[m][nn]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -284,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     // fused GroupNorm statistics of the NEXT layer's normalisation (fcos.py:182-186): one {sum, sumsq} record per (spatial tile, pixel row of
     // waves), every group of it written by the wave that owns those couts (WROWS records per tile: gn_records of cmk_conv_plan)
     const bool want_stats = a.gn_ws != nullptr;
-    const float acc_scale = Pb.acc_scale * (1.f / SX);          // 1 / (S_x * S_w)
+    const float acc_scale = Pb.acc_scale * (1.f / SPLIT_SX);          // 1 / (S_x * S_w)
     auto put_stats = [&](int co, bool cvalid, float gs, float gss) {
         for (int o = 1; o < a.gn_cpg; o <<= 1) { gs += __shfl_xor(gs, o); gss += __shfl_xor(gss, o); }
         gs += __shfl_xor(gs, 32);
@@ -298,10 +260,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     if (interior) {
         // 1.5 VALU per stored value (one packed fma per two, one max each); the address is a wave-uniform pointer walked by the scalar unit plus a
         // fixed lane offset (global_store saddr form, written as asm: the compiler renders the same C as 64-bit vector adds per store — conv_pw.hip)
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const unsigned long long yb = (unsigned long long)yimg;
-        const unsigned long long ybs = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(yb >> 32)) << 32) |
-                                       (unsigned)__builtin_amdgcn_readfirstlane((int)yb);
+        const unsigned long long ybs = wave_uniform_u64(yimg);
         const unsigned long long px_b = (unsigned long long)a.y_cs * 4u, rowskip_b = (unsigned long long)(W - 3) * a.y_cs * 4u;
 #pragma unroll
         for (int nn = 0; nn < NB; ++nn) {
@@ -336,10 +295,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp3_kernel(const ConvArgs a) {
     }
     // border tiles: the same walk; a store is predicated on its row (wave-uniform) and its column / cout (per lane, four compares per patch)
     {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const unsigned long long yb = (unsigned long long)yimg;
-        const unsigned long long ybs = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(yb >> 32)) << 32) |
-                                       (unsigned)__builtin_amdgcn_readfirstlane((int)yb);
+        const unsigned long long ybs = wave_uniform_u64(yimg);
         const unsigned long long px_b = (unsigned long long)a.y_cs * 4u, rowskip_b = (unsigned long long)(W - 3) * a.y_cs * 4u;
 #pragma unroll
         for (int nn = 0; nn < NB; ++nn) {

@@ -144,15 +144,11 @@ __device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
     // buffer resource over the image this thread stages (GEO 1: wave-uniform, waves 0-1 the first image of the pair, waves 2-3 the second
     // — PAIR: waves 0-3, 4-7; an image index past the batch gets an empty resource: every load returns 0): {base, num_records = bytes of
     // the image, raw dword format}
-    i32x4 rsrc;
-    {
-        const int img_n = n + (GEO == 1 ? (PAIR ? (wid >> 2) : (wave >> 1)) : 0);
-        const unsigned long long base = (unsigned long long)(P.x + (long)min(img_n, P.N - 1) * H * W * a.x_cs);
-        rsrc.x = __builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
-        rsrc.y = __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffffull));
-        rsrc.z = __builtin_amdgcn_readfirstlane(img_n < P.N ? H * W * a.x_cs * 4 : 0);
-        rsrc.w = 0x00020000;
-    }
+    const int img_n = n + (GEO == 1 ? (PAIR ? (wid >> 2) : (wave >> 1)) : 0);
+    // (the size is set behind the base: as an argument of buffer_rsrc the test is evaluated in front of the base's readfirstlanes, and the scalar
+    // code of the RoI-pair kernels moves with it)
+    i32x4 rsrc = buffer_rsrc(P.x + (long)min(img_n, P.N - 1) * H * W * a.x_cs, 0);
+    rsrc.z = __builtin_amdgcn_readfirstlane(img_n < P.N ? H * W * a.x_cs * 4 : 0);
     const int row_bytes = W * a.x_cs * 4;
     const int ih0 = oh0 - 1 + 4 * p_t, iw = ow0 - 1 + p_col;
     // byte offset of input row 0 of the item; rows above/below the image are out of the resource's range by themselves, a column
@@ -176,8 +172,8 @@ __device__ __forceinline__ void conv_wino6_body(const ConvArgs& a) {
     auto load_D = [&](int chunk) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            if constexpr (PAIR) d[i] = w6_buffer_load2(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
-            else d[i] = w6_buffer_load(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
+            if constexpr (PAIR) d[i] = buffer_load_f32x2(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
+            else d[i] = buffer_load_f32x4(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
         }
         if (AFF) {
             in_sc = *reinterpret_cast<const DV*>(P.in_scale + chunk * 8 + aff_off);

@@ -98,15 +98,12 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     int p_img, p_q, p_pair, p_t, p_col;
     bool p_active;
     S::item_of(tid, p_img, p_q, p_pair, p_t, p_col, p_active);
-    i32x4 rsrc;      // GEO 1: wave-uniform image (waves 0-3 the first image of the pair, waves 4-7 the second); an image past the batch reads zeros
-    {
-        const int img_n = n + (GEO == 1 ? (wave >> 2) : 0);
-        const unsigned long long base = (unsigned long long)(P.x + (long)min(img_n, P.N - 1) * H * W * a.x_cs);
-        rsrc.x = __builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
-        rsrc.y = __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffffull));
-        rsrc.z = __builtin_amdgcn_readfirstlane(img_n < P.N ? H * W * a.x_cs * 4 : 0);
-        rsrc.w = 0x00020000;
-    }
+    // GEO 1: wave-uniform image (waves 0-3 the first image of the pair, waves 4-7 the second); an image past the batch reads zeros
+    const int img_n = n + (GEO == 1 ? (wave >> 2) : 0);
+    // (the size is set behind the base: as an argument of buffer_rsrc the test is evaluated in front of the base's readfirstlanes, and the scalar
+    // code of the RoI-pair kernels moves with it)
+    i32x4 rsrc = buffer_rsrc(P.x + (long)min(img_n, P.N - 1) * H * W * a.x_cs, 0);
+    rsrc.z = __builtin_amdgcn_readfirstlane(img_n < P.N ? H * W * a.x_cs * 4 : 0);
     const int row_bytes = W * a.x_cs * 4;
     const int ih0 = oh0 - 1 + 4 * p_t, iw = ow0 - 1 + p_col;
     // rows above/below the image are out of the resource's range by themselves; a column outside the image would alias the neighbouring
@@ -123,7 +120,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino6s_kernel(const ConvArgs a) {
     f32x2 in_sc = {1.f, 1.f}, in_sh = {0.f, 0.f};
     auto load_D = [&](int chunk) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) d[i] = w6_buffer_load2(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
+        for (int i = 0; i < 6; ++i) d[i] = buffer_load_f32x2(rsrc, voff0 + i * row_bytes, chunk * 32, 0);
         if (AFF) {
             in_sc = *reinterpret_cast<const f32x2*>(P.in_scale + chunk * 8 + aff_off);
             in_sh = *reinterpret_cast<const f32x2*>(P.in_shift + chunk * 8 + aff_off);

@@ -9,13 +9,6 @@
 
 namespace cmk {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// bounds-checked 16-byte load: lanes whose byte offset lies outside [0, num_records) of the resource get 0
-__device__ f32x4 w6_buffer_load(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-__device__ f32x2 w6_buffer_load2(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");      // 8 bytes
-
 // Two tilings of the 32 MFMA rows (a workgroup's 32 tiles of 4x4 outputs):
 //   GEO 0  maps: 3 x 10 tiles of ONE image (12 x 40 pixels: every map width of the model is a multiple of 40); rows 30, 31 carry no tile;
 //   GEO 1  RoI maps (at most 16 rows x 14 columns, e.g. the 14x14 RoI features of the mask / mask-IoU heads): 4 x 4 tiles of each of
@@ -160,11 +153,7 @@ __device__ __forceinline__ void w6_epilogue(const ConvArgs& a, const ConvProblem
     float gs = 0.f, gss = 0.f;
     float* yimg = ybuf + (long)n_st * H * W * ycs + yco + co;
     // scalar side of the store addresses: image base (the pair's first image for GEO 1) and the byte strides of one pixel / one row
-    unsigned long long ybase_s;
-    {
-        const unsigned long long yb = (unsigned long long)(ybuf + (long)n_st * H * W * ycs);
-        ybase_s = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(yb >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)yb);
-    }
+    const unsigned long long ybase_s = wave_uniform_u64(ybuf + (long)n_st * H * W * ycs);
     const unsigned long long px_b = (unsigned long long)ycs * 4u, rowskip_b = (unsigned long long)(W - 3) * ycs * 4u;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {

@@ -557,7 +557,7 @@ def conv2d_multi(xs: Sequence[View], pcs: Sequence[PackedConv], ys: Sequence[Vie
 def _gn_records(descs, ys, groups):
     """Point the descriptors at a new workspace for the fused GroupNorm statistics that their kernel writes (records numbered over the problems
     in order), sized by the library's plan of the launch.  Returns affine(lo, hi, gamma, beta, eps) -> [(scale, shift)] of problems
-    lo..hi-1, to be called after the launch; None, with the descriptors left without statistics, when that kernel writes none."""
+    lo..hi-1, to be called after the launch (affine.records: the workspace itself); None, with the descriptors left without statistics, when that kernel writes none."""
     lib = _lib.load()
     nimg, cout, dev = ys[0].t.shape[0], ys[0].c, ys[0].t.device
     for i in range(len(ys)):
@@ -579,6 +579,7 @@ def _gn_records(descs, ys, groups):
         check(lib.cmk_groupnorm_affine_tiles(gws.data_ptr() + nimg * sum(recs[:lo]) * groups * 2 * 8, hs, wss, rc, m, gamma.data_ptr(), beta.data_ptr(), nimg, cout,
                                              groups, eps, ps, pb, _stream()), "cmk_groupnorm_affine_tiles")
         return out
+    affine.records = gws
     return affine
 
 
@@ -1063,7 +1064,7 @@ def kernel_source_hash() -> str:
     import os
     h = hashlib.sha1()
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    for f in ("conv_args.hpp", "wino6_common.hpp", "conv.hip", "conv_igemm.hip", "conv_wino4r.hip", "conv_wino6.hip", "conv_wino6s.hip", "conv_pw.hip", "conv_sp3.hip"):
+    for f in ("conv_args.hpp", "conv_split.hpp", "wino6_common.hpp", "conv.hip", "conv_igemm.hip", "conv_wino4r.hip", "conv_wino6.hip", "conv_wino6s.hip", "conv_pw.hip", "conv_sp3.hip"):
         h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:12]
 
