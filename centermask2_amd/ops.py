@@ -704,6 +704,61 @@ def deform_conv3x3(x: View, offsets: torch.Tensor, packed: PackedDeformConv, y: 
           "cmk_deform_conv3x3_nhwc")
 
 
+GROUP_CONV_CG = (4, 8, 16, 32, 64)     # channels per group that cmk_group_conv3x3_nhwc builds
+
+
+def group_conv_supported(c: int, groups: int) -> bool:
+    """What cmk_group_conv3x3_nhwc takes: groups >= 2 dividing C, with C / groups in {4, 8, 16, 32, 64}."""
+    return groups >= 2 and c >= groups and c % groups == 0 and c // groups in GROUP_CONV_CG
+
+
+def pack_group_weight(weight: torch.Tensor, groups: int) -> torch.Tensor:
+    """(C, Cg, 3, 3) weight of a grouped 3x3 conv (C = groups * Cg) -> the 9*Cg*C floats cmk_group_conv3x3_nhwc reads (csrc/conv_group3.hip),
+    tap = kh*3 + kw, ci the input channel inside the group:
+      Cg in {4, 8}:        [tap][ci][C]:                        packed[(tap*Cg + ci)*C + cout] = weight[cout, ci, kh, kw]
+      Cg in {16, 32, 64}:  [group][chunk][tap][tile][q][n][j]:  weight[group*Cg + tile*16 + n, chunk*16 + 4*q + j, kh, kw]
+                           with chunk, tile < Cg/16, q < 4, n < 16, j < 4."""
+    if weight.dim() != 4 or groups < 2 or weight.shape[0] % groups or tuple(weight.shape[1:]) != (weight.shape[0] // groups, 3, 3):
+        raise _lib.CmkError("grouped conv: a (C, C/groups, 3, 3) weight is expected for groups = {}, got {}".format(groups, tuple(weight.shape)))
+    c, cg = weight.shape[0], weight.shape[1]
+    if cg not in GROUP_CONV_CG:
+        raise _lib.CmkError("grouped conv: Cg = {} channels per group is not built ({} are)".format(cg, list(GROUP_CONV_CG)))
+    w = weight.detach().float().cpu()
+    if cg < 16:
+        return w.permute(2, 3, 1, 0).reshape(-1).contiguous()
+    t = cg // 16
+    return w.reshape(groups, t, 16, t, 4, 4, 3, 3).permute(0, 3, 6, 7, 1, 4, 2, 5).reshape(-1).contiguous()
+
+
+class PackedGroupConv:
+    """Device-resident packed weight of a grouped 3x3 conv (ResNeXt conv2) plus the folded FrozenBN scale/shift."""
+
+    def __init__(self, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], device, groups: int, stride: int = 1):
+        self.w = pack_group_weight(weight, groups).to(device)
+        self.c, self.cg, self.groups, self.stride = weight.shape[0], weight.shape[1], groups, stride
+        self.cin = self.cout = self.c
+        if stride not in (1, 2):
+            raise _lib.CmkError("grouped conv: stride {} must be 1 or 2".format(stride))
+        self.scale = (torch.ones(self.c) if scale is None else scale.detach().float().cpu()).contiguous().to(device)
+        self.shift = (torch.zeros(self.c) if shift is None else shift.detach().float().cpu()).contiguous().to(device)
+
+
+def group_conv3x3(x: View, packed: PackedGroupConv, y: Optional[View] = None, relu: bool = False) -> View:
+    """Grouped 3x3 conv (pad 1, packed.stride, no bias) + folded FrozenBN (+ ReLU): y = [relu](gconv3x3(x) * scale + shift)."""
+    lib = _lib.load()
+    _need_gpu(x.t, "group_conv3x3")
+    n, h, w = x.nhw
+    s = packed.stride
+    ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
+    if y is None:
+        y = View(torch.empty((n, ho, wo, packed.c), dtype=torch.float32, device=x.t.device))
+    assert x.c == packed.c and y.c == packed.c and y.nhw == (n, ho, wo), (x.c, y.c, packed.c, y.nhw)
+    check(lib.cmk_group_conv3x3_nhwc(x.t.data_ptr(), x.cs, x.co, packed.w.data_ptr(), packed.scale.data_ptr(), packed.shift.data_ptr(),
+                                     y.t.data_ptr(), y.cs, y.co, n, h, w, packed.c, packed.groups, s, int(bool(relu)), _stream()),
+          "cmk_group_conv3x3_nhwc")
+    return y
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # backbone pieces
 # ---------------------------------------------------------------------------------------------------------------

@@ -67,15 +67,25 @@ def mobilenetv2_param_shapes(prefix: str = "") -> "OrderedDict[str, Tuple[int, .
 
 RESNET_DEPTHS = {"R-50": 50, "R-101": 101, "R-152": 152}      # conv_body names of the detectron2 bottleneck ResNets (MODEL.RESNETS.DEPTH)
 RESNET_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+# ResNeXt bodies: name -> (MODEL.RESNETS.DEPTH, NUM_GROUPS, WIDTH_PER_GROUP); conv2 of every bottleneck is a grouped 3x3
+RESNEXT_BODIES = {"X-50-32x4d": (50, 32, 4), "X-101-32x4d": (101, 32, 4), "X-101-64x4d": (101, 64, 4), "X-101-32x8d": (101, 32, 8)}
 
 
-def resnet_param_shapes(depth: int = 50, prefix: str = "", last_stage: int = 5, res2_out: int = 256, width: int = 64) -> "OrderedDict[str, Tuple[int, ...]]":
+def resnet_body(conv_body: str):
+    """(depth, groups, width per group) of a ResNet / ResNeXt conv_body name, or None for any other body."""
+    if conv_body in RESNET_DEPTHS:
+        return RESNET_DEPTHS[conv_body], 1, 64
+    return RESNEXT_BODIES.get(conv_body)
+
+
+def resnet_param_shapes(depth: int = 50, prefix: str = "", last_stage: int = 5, res2_out: int = 256, width: int = 64,
+                        groups: int = 1) -> "OrderedDict[str, Tuple[int, ...]]":
     """State-dict entries of detectron2's bottleneck ResNet up to res<last_stage>, in d2's key names and order (the shortcut of a stage's
-    first block is registered before its conv1)."""
+    first block is registered before its conv1).  width: NUM_GROUPS * WIDTH_PER_GROUP; groups > 1 (ResNeXt) makes conv2 a grouped 3x3."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
 
-    def conv_bn(key: str, cin: int, cout: int, k: int) -> None:
-        s[key + ".weight"] = (cout, cin, k, k)
+    def conv_bn(key: str, cin: int, cout: int, k: int, g: int = 1) -> None:
+        s[key + ".weight"] = (cout, cin // g, k, k)
         for n in ("weight", "bias", "running_mean", "running_var"):
             s["{}.norm.{}".format(key, n)] = (cout,)
 
@@ -87,7 +97,7 @@ def resnet_param_shapes(depth: int = 50, prefix: str = "", last_stage: int = 5, 
             if cin != cout:
                 conv_bn(p + "shortcut", cin, cout, 1)
             conv_bn(p + "conv1", cin, width, 1)
-            conv_bn(p + "conv2", width, width, 3)
+            conv_bn(p + "conv2", width, width, 3, groups)
             conv_bn(p + "conv3", width, cout, 1)
             cin = cout
         cout, width = cout * 2, width * 2
@@ -106,14 +116,16 @@ def model_param_shapes(conv_body: str = "V-39-eSE", num_classes: int = 80, fpn_c
     DFConv3x3 (vovnet.py:132-201: '/conv_offset' with bias, '/conv', '/norm'), except in the depth-wise bodies (vovnet.py:292-298).
     conv_body "MobileNetV2": the CenterMask-Lite body behind build_fcos_mobilenetv2_fpn_backbone, FPN laterals over `fpn_in`
     (MODEL.FPN.IN_FEATURES) and `top_levels` (MODEL.FCOS.TOP_LEVELS) top convs.  conv_body "R-50" / "R-101" / "R-152": detectron2's
-    bottleneck ResNet behind build_fcos_resnet_fpn_backbone at d2's default widths, with the same `fpn_in` / `top_levels`.  num_tower_convs / mask_num_conv / maskiou_num_conv:
+    bottleneck ResNet behind build_fcos_resnet_fpn_backbone at d2's default widths, with the same `fpn_in` / `top_levels`; the RESNEXT_BODIES names
+    ("X-101-32x8d", ...) are its grouped (ResNeXt) members.  num_tower_convs / mask_num_conv / maskiou_num_conv:
     MODEL.FCOS.NUM_{CLS,BOX}_CONVS, MODEL.ROI_MASK_HEAD.NUM_CONV, MODEL.ROI_MASKIOU_HEAD.NUM_CONV; fpn_ch and mask_dim the widths."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
     if conv_body == MOBILENETV2:
         s.update(mobilenetv2_param_shapes("backbone.bottom_up."))
         _fpn_shapes(s, [(int(f[3:]), MNV2_OUT_CHANNELS[f]) for f in fpn_in], fpn_ch, top_levels)
-    elif conv_body in RESNET_DEPTHS:
-        s.update(resnet_param_shapes(RESNET_DEPTHS[conv_body], "backbone.bottom_up.", last_stage=max(int(f[3:]) for f in fpn_in)))
+    elif resnet_body(conv_body) is not None:
+        depth, groups, wpg = resnet_body(conv_body)
+        s.update(resnet_param_shapes(depth, "backbone.bottom_up.", last_stage=max(int(f[3:]) for f in fpn_in), width=groups * wpg, groups=groups))
         _fpn_shapes(s, [(int(f[3:]), 2 ** (int(f[3:]) + 6)) for f in fpn_in], fpn_ch, top_levels)
     else:
         _vovnet_shapes(s, STAGE_SPECS[conv_body], stage_with_dcn, with_modulated_dcn, deformable_groups)
@@ -316,13 +328,13 @@ def make_synthetic_state_dict(conv_body: str = "V-39-eSE", seed: int = 0, shapes
     sd = OrderedDict((k, synthetic_tensor(k, v, seed).float().contiguous()) for k, v in shapes.items())
     if conv_body == MOBILENETV2:
         return sd
-    if conv_body in RESNET_DEPTHS:
+    if resnet_body(conv_body) is not None:
         # relu(conv3(..) + shortcut(x) or x): conv3 and the shortcut are Kaiming-normal (gain 2) with no ReLU of their own behind them,
         # so each branch doubles the second moment, and the sum adds the branches up; unscaled, the activations double in every one
         # of the 16-50 blocks.  The FrozenBN affine that ends a branch is scaled by 1/sqrt(2) for the gain and by 1/sqrt(branches): the
         # two branches of a stage's first block by 1/2, the identity blocks of a stage (which share one unit of growth, the 1/sqrt(blocks)
         # rule of the VoVNet bodies below) by 1/sqrt(2 * blocks in the stage).
-        per_stage = RESNET_BLOCKS[RESNET_DEPTHS[conv_body]]
+        per_stage = RESNET_BLOCKS[resnet_body(conv_body)[0]]
         for k in sd:
             m = re.search(r"\.res(\d)\.(\d+)\.(conv3|shortcut)\.norm\.(weight|bias)$", k)
             if m:

@@ -226,6 +226,15 @@ int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, const float* w
                               float in_max, float out_min, float out_max, float* y, int y_cs, int y_co,
                               int N, int H, int W, int C, int stride, void* stream);
 
+/* ---- grouped 3x3 conv of a ResNeXt bottleneck (d2 BottleneckBlock.conv2, MODEL.RESNETS.NUM_GROUPS > 1) with its FrozenBN folded:
+ *   y = [relu](gconv3x3(x) * scale[c] + shift[c]),  pad 1, stride 1|2, no bias, Cin = Cout = C, `groups` >= 2 groups of Cg = C/groups,
+ * Cg in {4, 8, 16, 32, 64}.  Exact fp32; a group reads only its own Cg input channels (a NaN / Inf stays inside its group); a NaN passes
+ * the ReLU.  Output map ((H-1)/stride + 1, (W-1)/stride + 1).  x, y: NHWC channel-slice views; w: 9*Cg*C floats in the packing written
+ * down in csrc/conv_group3.hip (ops.pack_group_weight); all pointers 16-byte aligned, offsets and strides multiples of 4 floats.
+ * One launch, no workspace.  Additive entry: the ABI version stays 5. */
+int cmk_group_conv3x3_nhwc(const float* x, int x_cs, int x_co, const float* w, const float* scale, const float* shift,
+                           float* y, int y_cs, int y_co, int N, int H, int W, int C, int groups, int stride, int relu, void* stream);
+
 /* ---- stem_1: 3x3 stride-2 conv on the NCHW 3-channel image (vovnet.py:409), BN-folded, ReLU, NHWC out -------- */
 int cmk_stem_conv_nchw3(const float* x, const float* w /* [27][Cout] */, const float* scale, const float* shift,
                         float* y, int N, int H, int W, int Cout, void* stream);
