@@ -1299,3 +1299,45 @@ def paste_masks(masks: torch.Tensor, boxes: torch.Tensor, height: int, width: in
         check(lib.cmk_paste_masks(masks.contiguous().data_ptr(), boxes.contiguous().float().data_ptr(), r, s, height, width, float(threshold),
                                   out.data_ptr(), _stream()), "cmk_paste_masks")
     return out.bool()
+
+
+def mask_rle(masks: torch.Tensor):
+    """(R,H,W) bool bitmasks on the GPU -> (counts, strings): per mask the COCO run lengths (int32 CPU tensor, the uncompressed form)
+    and the compressed string, byte for byte what wire.rle_counts / wire.rle_to_string give (coco_evaluation.py:362-427).
+    Two host synchronisations: the run totals after the count phase, which size every output exactly (7 bytes bound the characters of
+    one count), then one download of lengths, counts and bytes after the encode phase."""
+    lib = _lib.load()
+    if not torch.is_tensor(masks) or not masks.is_cuda:
+        raise _lib.CmkError("mask_rle: masks are on {}; the device encoder needs a GPU (no CPU fallback; wire.rle_encode is the host codec)".format(
+            masks.device if torch.is_tensor(masks) else type(masks).__name__))
+    if masks.dtype != torch.bool or masks.dim() != 3:
+        raise _lib.CmkError("mask_rle: expected (R,H,W) bool bitmasks, got {} {}".format(masks.dtype, tuple(masks.shape)))
+    _need_current_device(masks, "mask_rle")
+    masks = masks.contiguous()
+    r, h, w = masks.shape
+    if r == 0:
+        return [], []
+    dev = masks.device
+    ws_bytes = lib.cmk_rle_ws_bytes(r, h, w)
+    ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
+    n_runs = torch.empty((r,), dtype=torch.int32, device=dev)
+    check(lib.cmk_rle_count(masks.data_ptr(), r, h, w, ws.data_ptr(), ws_bytes, n_runs.data_ptr(), _stream()), "cmk_rle_count")
+    n_host = n_runs.cpu().numpy().astype("int64")                      # synchronisation 1
+    total = int(n_host.sum())
+    # one buffer, one download: [lens R int64 | counts total int32 | bytes 7*total]
+    out = torch.empty((8 * r + 11 * total,), dtype=torch.uint8, device=dev)
+    starts = torch.empty((total,), dtype=torch.int32, device=dev)
+    p = out.data_ptr()
+    check(lib.cmk_rle_encode(masks.data_ptr(), r, h, w, ws.data_ptr(), ws_bytes, n_runs.data_ptr(), starts.data_ptr(), p + 8 * r,
+                             p + 8 * r + 4 * total, p, _stream()), "cmk_rle_encode")
+    host = out.cpu()                                                   # synchronisation 2
+    lens = host[:8 * r].view(torch.int64).tolist()
+    all_counts = host[8 * r:8 * r + 4 * total].view(torch.int32)
+    data = host[8 * r + 4 * total:].numpy()
+    counts, strings, off = [], [], 0
+    for k in range(r):
+        n = int(n_host[k])
+        counts.append(all_counts[off:off + n].clone())
+        strings.append(data[7 * off:7 * off + lens[k]].tobytes().decode("ascii"))
+        off += n
+    return counts, strings

@@ -7,7 +7,8 @@
   that segm AP is ranked by `mask_score` (:557-563).
 pycocotools is absent here, so the RLE codec below restates its published algorithm (maskApi.c rleEncode / rleToString:
 column-major runs starting with a zero run, 5-bit groups with a continuation bit, delta coding from the third count on);
-it is checked by round trip only ("parity unpinned" for the exact bytes).
+it is checked by round trip only ("parity unpinned" for the exact bytes).  The same codec runs on the device for GPU bitmasks
+(csrc/rle.hip through ops.mask_rle), held to byte equality with the host functions here, which stay the reference and the CPU path.
 """
 import os
 from typing import Dict, List, Tuple
@@ -89,6 +90,16 @@ def rle_encode(mask) -> Dict:
     return {"size": [int(m.shape[0]), int(m.shape[1])], "counts": rle_to_string(rle_counts(m))}
 
 
+def rle_encode_batch(masks) -> List[Dict]:
+    """(n,H,W) bitmasks -> one RLE dict each.  Bool bitmasks on a GPU are encoded there (ops.mask_rle: the bitmaps are not downloaded);
+    anything else (CPU tensors, NumPy arrays) goes through rle_encode mask by mask.  Both give the same bytes."""
+    if torch.is_tensor(masks) and masks.is_cuda and masks.dtype == torch.bool and masks.dim() == 3:
+        from . import ops
+        size = [int(masks.shape[1]), int(masks.shape[2])]
+        return [{"size": list(size), "counts": s} for s in ops.mask_rle(masks)[1]]
+    return [rle_encode(m) for m in masks]
+
+
 def rle_decode(rle: Dict) -> np.ndarray:
     h, w = rle["size"]
     counts = rle_from_string(rle["counts"])
@@ -112,7 +123,7 @@ def instances_to_coco_json(instances, img_id: int) -> List[Dict]:
     boxes = boxes.tolist()
     scores = instances.scores.tolist()
     classes = instances.pred_classes.tolist()
-    rles = [rle_encode(m) for m in instances.pred_masks] if instances.has("pred_masks") else None
+    rles = rle_encode_batch(instances.pred_masks) if instances.has("pred_masks") else None
     mask_scores = instances.mask_scores.tolist() if instances.has("mask_scores") else None
     keypoints = None
     if instances.has("pred_keypoints"):        # coco_evaluation.py:418-425: COCO's keypoint coordinates are pixel indices

@@ -402,6 +402,23 @@ int cmk_resize_v_preprocess(const uint8_t* src, int h, int new_h, int new_w, con
 int cmk_paste_masks(const float* masks, const float* boxes, int R, int S, int H, int W, float threshold, uint8_t* out,
                     void* stream);
 
+/* ---- COCO RLE of those bitmasks, the "segmentation" of a result (evaluation/coco_evaluation.py:362-427), in two phases around one
+ * host read of the run totals.  masks (R,H,W) bytes 0/1 as cmk_paste_masks writes them.  Runs are taken over the column-major
+ * flattening (position x*H + y) and start with a zeros run, 0 long for a mask whose first pixel is set; the string writes every count
+ * as 5-bit groups, low group first, + 0x20 while more follow, + 48, counts from the fourth on as the signed difference to the count two
+ * back (pycocotools' rleToString as restated by wire.rle_to_string; at most 7 characters per count).
+ * ws: cmk_rle_ws_bytes(R, H, W) bytes, 8-byte aligned (0 for arguments the launches refuse): R+1 int64 run offsets, then one int32
+ * per (mask, 64-row chunk, column).  Refused: H or W < 1, H*W >= 2^31 - 1 (positions and run totals are int32), R > 65535, null pointers,
+ * a workspace too small.  R == 0 is CMK_OK with no launch. */
+int64_t cmk_rle_ws_bytes(int R, int H, int W);
+/* evaluation/coco_evaluation.py:362-427, count phase: n_runs[r] = runs of mask r; ws keeps the scanned offsets for the encode phase. */
+int cmk_rle_count(const uint8_t* masks, int R, int H, int W, void* ws, int64_t ws_bytes, int32_t* n_runs, void* stream);
+/* evaluation/coco_evaluation.py:362-427, encode phase, after cmk_rle_count on the same masks, ws and n_runs.  With T the sum of n_runs
+ * and off[r] the sum of n_runs[0..r): counts (T int32) gets the run lengths of mask r at off[r]; bytes (7*T) its string at 7*off[r],
+ * lens[r] characters long; starts (T int32) is scratch. */
+int cmk_rle_encode(const uint8_t* masks, int R, int H, int W, const void* ws, int64_t ws_bytes, const int32_t* n_runs, int32_t* starts,
+                   int32_t* counts, uint8_t* bytes, int64_t* lens, void* stream);
+
 /* ---- multi-GPU result exchange (the reference's analogue: comm.gather in evaluation/coco_evaluation.py:155-156) ----------
  * One fixed-stride float record per image, written straight into the all-gather send buffer:
  * [box 4K | score K | mask_score K | loc 2K | class K (as float) | mask K*hw*hw | count], K*(9 + hw*hw) + 1 floats. */
