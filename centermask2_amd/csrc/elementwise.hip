@@ -8,6 +8,14 @@ namespace cmk {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Selects, not fmaxf / fminf (which return the other operand for a NaN): a NaN behaves as in torch.
+__device__ __forceinline__ float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }   // max_pool2d: a NaN wins and stays
+__device__ __forceinline__ float hsigmoid3(float v) {                                            // relu6(v) / 6 with v = fc + 3: a NaN stays
+    v = v < 0.f ? 0.f : v;
+    v = v > 6.f ? 6.f : v;
+    return v / 6.0f;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // stem_1 (vovnet.py:409): conv3x3 s2 p1 on (N,3,H,W) NCHW -> (N,Ho,Wo,Cout) NHWC, y = relu(acc*scale + shift).
 // 4 threads per output pixel, 16 output channels each (Cout = 64); 27 taps broadcast from LDS.
@@ -76,6 +84,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------------------------
 // MaxPool2d(3, 2, ceil_mode=True), no padding (vovnet.py:349-350).  One lane = one output pixel x 4 channels.
 // ---------------------------------------------------------------------------------------------------------------
+// A window that holds a NaN comes out NaN (F.max_pool2d), an all -inf window -inf.
 // `gate` (optional, N*C, all >= 0): the eSE channel gate of the producer block applied after the max — max(x*g) == g*max(x)
 // for g >= 0, so stage 2's eSE scale pass (whose output nobody else reads) folds into the pool.
 __global__ __launch_bounds__(256) void maxpool3_kernel(const float* __restrict__ x, int x_cs, int x_co, float* __restrict__ y,
@@ -96,7 +105,7 @@ __global__ __launch_bounds__(256) void maxpool3_kernel(const float* __restrict__
                 int ih = oh * 2 + kh, iw = ow * 2 + kw;
                 if (ih < H && iw < W) {
                     f32x4 v = *reinterpret_cast<const f32x4*>(x + (((long)n * H + ih) * W + iw) * x_cs + x_co + c4 * 4);
-                    m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                    m.x = nanmax(m.x, v.x); m.y = nanmax(m.y, v.y); m.z = nanmax(m.z, v.z); m.w = nanmax(m.w, v.w);
                 }
             }
         if (gate) {
@@ -192,7 +201,7 @@ __global__ __launch_bounds__(256) void ese_fc_kernel(const float* __restrict__ w
         s = wave_sum(s);
         if (lane == 0) {
             float v = (float)(s + (double)fc_b[o] + 3.0);
-            gate[(long)n * C + o] = fminf(fmaxf(v, 0.f), 6.f) / 6.0f;
+            gate[(long)n * C + o] = hsigmoid3(v);      // a NaN mean gives a NaN gate: the image comes out NaN, as in torch
         }
     }
 }
@@ -245,7 +254,7 @@ __global__ __launch_bounds__(256) void ese_fc_pooled_kernel(const float* __restr
         s = wave_sum(s);
         if (lane == 0) {
             float v = (float)(s + (double)fc_b[o] + 3.0);
-            gate[(long)n * C + o] = fminf(fmaxf(v, 0.f), 6.f) / 6.0f;
+            gate[(long)n * C + o] = hsigmoid3(v);      // a NaN mean gives a NaN gate: the image comes out NaN, as in torch
         }
     }
 }
@@ -266,6 +275,22 @@ __global__ __launch_bounds__(256) void ese_scale_kernel(const float* __restrict_
             o.x += d.x; o.y += d.y; o.z += d.z; o.w += d.w;
         }
         *reinterpret_cast<f32x4*>(y + p * y_cs + y_co + c4 * 4) = o;
+    }
+}
+
+// nearest-neighbour 2x upsampling of `coarse` added to `y` in place (d2 FPN's top-down path, ctor at vovnet.py:547-554, when a norm sits between the
+// lateral conv and the sum, so that the sum cannot ride in the conv's epilogue)
+__global__ __launch_bounds__(256) void upsample2x_add_kernel(float* __restrict__ y, const float* __restrict__ c, int N, int H, int W, int Hc, int Wc, int C4) {
+    long total = (long)N * H * W * C4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        int c4 = (int)(i % C4);
+        long p = i / C4;
+        int w = (int)(p % W);
+        int h = (int)((p / W) % H);
+        int n = (int)(p / ((long)W * H));
+        const f32x4 a = *reinterpret_cast<const f32x4*>(y + i * 4);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(c + ((((long)n * Hc + (h >> 1)) * Wc + (w >> 1)) * C4 + c4) * 4);
+        *reinterpret_cast<f32x4*>(y + i * 4) = f32x4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w};
     }
 }
 
@@ -320,6 +345,7 @@ extern "C" int cmk_ese_gate(const float* x, int x_cs, int x_co, const float* fc_
                             int ws_chunks, int N, int HW, int C, void* stream) {
     if (!x || !fc_w || !fc_b || !gate || !ws) return fail(CMK_EINVAL, "ese_gate: null pointer%s", "");
     if ((C & 3) || (x_cs & 3) || (x_co & 3) || ws_chunks < 1) return fail(CMK_EINVAL, "ese_gate: bad shape%s", "");
+    if (N < 1 || HW < 1 || C < 4) return fail(CMK_EINVAL, "ese_gate: N, H*W >= 1 and C >= 4%s", "");
     int G = C >> 2;
     int ppl = G >= 256 ? 1 : 256 / G;
     size_t lds1 = (size_t)ppl * C * sizeof(float);
@@ -333,7 +359,7 @@ extern "C" int cmk_ese_gate(const float* x, int x_cs, int x_co, const float* fc_
 
 extern "C" int cmk_ese_gate_pooled(const float* pool_ws, int rows, const float* fc_w, const float* fc_b, float* gate, int N, int HW, int C, void* stream) {
     if (!pool_ws || !fc_w || !fc_b || !gate) return fail(CMK_EINVAL, "ese_gate_pooled: null pointer%s", "");
-    if ((C & 3) || rows < 1 || HW < rows || N < 1) return fail(CMK_EINVAL, "ese_gate_pooled: bad shape (C %% 4, H*W >= rows)%s", "");
+    if ((C & 3) || C < 4 || rows < 1 || HW < rows || N < 1) return fail(CMK_EINVAL, "ese_gate_pooled: bad shape (C %% 4, H*W >= rows)%s", "");
     const int G = C >> 2;
     const int parts = G >= 256 ? 1 : 256 / G;
     hipLaunchKernelGGL(ese_fc_pooled_kernel, dim3(cdiv(C, 16), N), dim3(256), (size_t)parts * C * sizeof(double), (hipStream_t)stream, pool_ws, rows,
@@ -346,26 +372,11 @@ extern "C" int cmk_ese_scale(const float* x, int x_cs, int x_co, const float* ga
     if (!x || !gate || !y) return fail(CMK_EINVAL, "ese_scale: null pointer%s", "");
     if ((C & 3) || (x_cs & 3) || (x_co & 3) || (y_cs & 3) || (y_co & 3) || (id_cs & 3) || (id_co & 3))
         return fail(CMK_EINVAL, "ese_scale: channels must be multiples of 4%s", "");
+    if (N < 1 || HW < 1) return fail(CMK_EINVAL, "ese_scale: N, H*W >= 1%s", "");
     long total = (long)N * HW * (C >> 2);
     hipLaunchKernelGGL(ese_scale_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, x_cs, x_co, gate, identity, id_cs,
                        id_co, y, y_cs, y_co, N, HW, C >> 2);
     return check_launch("ese_scale");
-}
-
-// nearest-neighbour 2x upsampling of `coarse` added to `y` in place (d2 FPN's top-down path, ctor at vovnet.py:547-554, when a norm sits between the
-// lateral conv and the sum, so that the sum cannot ride in the conv's epilogue)
-__global__ __launch_bounds__(256) void upsample2x_add_kernel(float* __restrict__ y, const float* __restrict__ c, int N, int H, int W, int Hc, int Wc, int C4) {
-    long total = (long)N * H * W * C4;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        int c4 = (int)(i % C4);
-        long p = i / C4;
-        int w = (int)(p % W);
-        int h = (int)((p / W) % H);
-        int n = (int)(p / ((long)W * H));
-        const f32x4 a = *reinterpret_cast<const f32x4*>(y + i * 4);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(c + ((((long)n * Hc + (h >> 1)) * Wc + (w >> 1)) * C4 + c4) * 4);
-        *reinterpret_cast<f32x4*>(y + i * 4) = f32x4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w};
-    }
 }
 
 extern "C" int cmk_upsample2x_add_nhwc(float* y, const float* coarse, int N, int H, int W, int Hc, int Wc, int C, void* stream) {

@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void gn_finalize_tiles_kernel(const GnTileLeve
 
 // what gn_stats_kernel's thread mapping and the 64-entry mean/rstd tables can take
 static bool gn_shape_ok(int C, int groups, int ws_chunks) {
-    return !((C & 3) || C > 1024 || groups < 1 || groups > 64 || C % groups || ((C / groups) & 3) || 256 % (C >> 2) || ws_chunks < 1);
+    return !((C & 3) || C < 4 || C > 1024 || groups < 1 || groups > 64 || C % groups || ((C / groups) & 3) || 256 % (C >> 2) || ws_chunks < 1);
 }
 
 }  // namespace cmk
@@ -242,6 +242,7 @@ static int groupnorm_inplace(float* x, const float* gamma, const float* beta, do
                              bool relu, void* stream) {
     if (!x || !gamma || !beta || !ws) return fail(CMK_EINVAL, "groupnorm: null pointer%s", "");
     if (!gn_shape_ok(C, groups, ws_chunks)) return fail(CMK_EINVAL, "groupnorm: unsupported C/groups%s", "");
+    if (N < 1 || HW < 1) return fail(CMK_EINVAL, "groupnorm: N, H*W >= 1%s", "");
     hipLaunchKernelGGL(gn_stats_kernel, dim3(ws_chunks, N), dim3(256), 0, (hipStream_t)stream, x, ws, HW, C, groups, ws_chunks);
     int rc = check_launch("gn_stats");
     if (rc) return rc;
@@ -267,6 +268,7 @@ extern "C" int cmk_groupnorm_affine(const float* x, const float* gamma, const fl
                                     int groups, float eps, float* out_scale, float* out_shift, void* stream) {
     if (!x || !gamma || !beta || !ws || !out_scale || !out_shift) return fail(CMK_EINVAL, "groupnorm_affine: null pointer%s", "");
     if (!gn_shape_ok(C, groups, ws_chunks)) return fail(CMK_EINVAL, "groupnorm_affine: unsupported C/groups%s", "");
+    if (N < 1 || HW < 1) return fail(CMK_EINVAL, "groupnorm_affine: N, H*W >= 1%s", "");
     hipLaunchKernelGGL(gn_stats_kernel, dim3(ws_chunks, N), dim3(256), 0, (hipStream_t)stream, x, ws, HW, C, groups, ws_chunks);
     int rc = check_launch("gn_stats");
     if (rc) return rc;
@@ -281,6 +283,7 @@ extern "C" int cmk_groupnorm_affine_multi(const float* const* xs, const int* HWs
     if (!xs || !HWs || !gamma || !beta || !ws || !out_scale || !out_shift) return fail(CMK_EINVAL, "groupnorm_affine_multi: null pointer%s", "");
     if (nlev < 1 || nlev > GN_MAXL) return fail(CMK_EINVAL, "groupnorm_affine_multi: 1..5 levels%s", "");
     if (!gn_shape_ok(C, groups, ws_chunks)) return fail(CMK_EINVAL, "groupnorm_affine_multi: unsupported C/groups%s", "");
+    if (N < 1) return fail(CMK_EINVAL, "groupnorm_affine_multi: N >= 1%s", "");
     GnLevels L;
     L.nlev = nlev;
     for (int l = 0; l < GN_MAXL; ++l) {

@@ -35,6 +35,29 @@ def _need_current_device(t: torch.Tensor, what: str) -> None:
                             "`with torch.cuda.device({})` (one process per GPU is the supported layout)".format(what, t.device.index, cur, t.device.index))
 
 
+def _need_dense_nhwc(t: torch.Tensor, what: str) -> None:
+    """The entry points that take a bare pointer and (N, HW, C) read the tensor as dense NHWC: a permuted or sliced view would be
+    normalised along the wrong axis without a word."""
+    if t.dim() != 4 or not t.is_contiguous():
+        raise _lib.CmkError("{}: expected a dense (contiguous) 4-d NHWC tensor, got shape {} strides {}".format(what, tuple(t.shape), tuple(t.stride())))
+    _need_gpu(t, what)
+
+
+def _need_gate(gate: torch.Tensor, n: int, c: int, like: torch.Tensor, what: str) -> None:
+    """An eSE gate is read as N * C consecutive floats on the device of the map it scales."""
+    if tuple(gate.shape) != (n, c) or not gate.is_contiguous():
+        raise _lib.CmkError("{}: the gate must be a contiguous ({}, {}) tensor, got shape {} strides {}".format(what, n, c, tuple(gate.shape), tuple(gate.stride())))
+    if gate.dtype != torch.float32 or gate.device != like.device:
+        raise _lib.CmkError("{}: the gate must be float32 on {}, got {} on {}".format(what, like.device, gate.dtype, gate.device))
+
+
+def _need_same_geometry(v: "View", n: int, h: int, w: int, c: int, like: torch.Tensor, what: str) -> None:
+    if v.nhw != (n, h, w) or v.c != c:
+        raise _lib.CmkError("{}: expected a view of ({}, {}, {}) pixels x {} channels, got {} x {}".format(what, n, h, w, c, tuple(v.nhw), v.c))
+    if v.t.dtype != torch.float32 or v.t.device != like.device:
+        raise _lib.CmkError("{}: expected float32 on {}, got {} on {}".format(what, like.device, v.t.dtype, v.t.device))
+
+
 class View:
     """Channel slice [co, co+c) of a contiguous NHWC tensor (N,H,W,CS)."""
     __slots__ = ("t", "co", "c")
@@ -851,7 +874,9 @@ def maxpool3x3s2_ceil(x: View, y: Optional[View] = None, gate: Optional[torch.Te
         wo -= 1
     if y is None:
         y = View(torch.empty((n, ho, wo, x.c), dtype=torch.float32, device=x.t.device))
-    assert tuple(y.t.shape[:3]) == (n, ho, wo) and y.c == x.c
+    _need_same_geometry(y, n, ho, wo, x.c, x.t, "maxpool3x3s2_ceil output")
+    if gate is not None:
+        _need_gate(gate, n, x.c, x.t, "maxpool3x3s2_ceil")
     check(lib.cmk_maxpool3x3s2_ceil_nhwc(x.t.data_ptr(), x.cs, x.co, y.t.data_ptr(), y.cs, y.co, n, h, w, x.c,
                                          gate.data_ptr() if gate is not None else None, _stream()),
           "cmk_maxpool3x3s2_ceil_nhwc")
@@ -903,8 +928,12 @@ def ese(x: View, fc_w: torch.Tensor, fc_b: torch.Tensor, y: View, identity: Opti
     _need_gpu(x.t, "ese")
     n, h, w = x.nhw
     hw, c = h * w, x.c
+    _need_same_geometry(y, n, h, w, c, x.t, "ese output")
+    if identity is not None:
+        _need_same_geometry(identity, n, h, w, c, x.t, "ese identity")
     if gate is None:
         gate = ese_gate(x, fc_w, fc_b)
+    _need_gate(gate, n, c, x.t, "ese")
     idp, idcs, idco = (identity.t.data_ptr(), identity.cs, identity.co) if identity is not None else (None, 0, 0)
     check(lib.cmk_ese_scale(x.t.data_ptr(), x.cs, x.co, gate.data_ptr(), idp, idcs, idco, y.t.data_ptr(), y.cs, y.co,
                             n, hw, c, _stream()), "cmk_ese_scale")
@@ -919,7 +948,7 @@ def groupnorm_affine(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, g
     """GroupNorm statistics of a dense NHWC tensor as per-(image, channel) (scale, shift); the consumer conv applies
     relu(x*scale + shift) while staging (cmk_conv_desc.in_scale/in_shift), so the normalised tensor is never written."""
     lib = _lib.load()
-    _need_gpu(x, "groupnorm_affine")
+    _need_dense_nhwc(x, "groupnorm_affine")
     n, h, w, c = x.shape
     hw = h * w
     chunks = _gn_chunks(hw)
@@ -955,7 +984,7 @@ def groupnorm_affine_multi(xs: Sequence[torch.Tensor], gamma: torch.Tensor, beta
 def groupnorm_relu_(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int = 32, eps: float = 1e-5, relu: bool = True) -> None:
     """GroupNorm (+ ReLU) in place on a dense NHWC tensor (fcos.py:182-186; relu=False: d2's get_norm("GN") behind a conv without activation)."""
     lib = _lib.load()
-    _need_gpu(x, "groupnorm_relu_")
+    _need_dense_nhwc(x, "groupnorm_relu_")
     n, h, w, c = x.shape
     hw = h * w
     chunks = _gn_chunks(hw)

@@ -248,7 +248,8 @@ int cmk_stem7x7_bn_relu_maxpool_nchw3(const float* x, const float* w, const floa
                                       float* y, int y_cs, int y_co, int N, int H, int W, int Cout, void* stream);
 
 /* ---- max pool k3 s2 ceil_mode, no padding (vovnet.py:349-350); k2 s2 (maskiou_head.py:93,108) ----------------- */
-/* gate: optional (N*C) non-negative channel gate applied after the max (the eSE scale of the producer block, folded in). */
+/* gate: optional (N*C) non-negative channel gate applied after the max (the eSE scale of the producer block, folded in).
+ * A window that holds a NaN comes out NaN (torch max_pool2d); H, W >= 3. */
 int cmk_maxpool3x3s2_ceil_nhwc(const float* x, int x_cs, int x_co, float* y, int y_cs, int y_co,
                                int N, int H, int W, int C, const float* gate, void* stream);
 
@@ -257,7 +258,8 @@ int cmk_maxpool3x3s2_ceil_nhwc(const float* x, int x_cs, int x_co, float* y, int
 int cmk_maxpool1x1s2_nhwc(const float* x, int x_cs, int x_co, float* y, int y_cs, int y_co, int N, int H, int W, int C, void* stream);
 
 /* ---- eSE (vovnet.py:247-260): gate = relu6(W * mean_HW(x) + b + 3) / 6 ; y = x * gate (+ identity) ------------
- * ws: N * ese_chunks * C floats of workspace for the two-stage mean.                                        */
+ * ws: N * ese_chunks * C floats of workspace for the two-stage mean.  A NaN in an image's map makes that image's gates NaN
+ * (torch relu6 keeps it), so the image comes out NaN.  N, HW >= 1, C % 4 == 0, ws_chunks >= 1, else refused.     */
 int cmk_ese_gate(const float* x, int x_cs, int x_co, const float* fc_w /* [C][C] row = out */, const float* fc_b,
                  float* gate /* N*C */, float* ws, int ws_chunks, int N, int HW, int C, void* stream);
 int cmk_ese_scale(const float* x, int x_cs, int x_co, const float* gate, const float* identity, int id_cs, int id_co,
