@@ -80,3 +80,129 @@ def average_precision(preds: List[Dict[str, torch.Tensor]], gts: List[Dict[str, 
         if per_thr:
             aps.append(float(np.mean(per_thr)))
     return float(np.mean(aps)) if aps else float("nan")
+
+
+class COCOEvaluator:
+    """Box and mask AP / AR against a COCO annotation file, with detectron2's reset / process / evaluate protocol: the counterpart of
+    the reference's centermask.evaluation.COCOEvaluator (evaluation/coco_evaluation.py:33-359), segm ranked by `mask_score` (:551-563).
+
+    annotations: path of a COCO json, or the loaded dict.  Model class k is the k-th category id in ascending order
+    (`thing_dataset_id_to_contiguous_id`, as detectron2's COCO registration builds it); predictions are mapped back through it.
+    The scoring protocol is coco_eval.py's restatement of pycocotools, never run beside the real one (see its docstring).
+
+    process() keeps, per image, the COCO result records (wire.instances_to_coco_json) and, when masks are present, the table of
+    integer counts mask IoU is formed from: pixels of every detection in every ground truth of the image, and both areas.  For
+    Instances on a GPU the table comes from ops.mask_intersections and the bitmasks are never downloaded; for CPU Instances from NumPy
+    on the same bits — selected by where the input lies, as in wire.rle_encode_batch.  evaluate() touches no bitmap.
+
+    Not built, refused by name: tasks containing "keypoints" (OKS), and the proposals branch."""
+
+    def __init__(self, annotations, tasks=None, distributed: bool = False, output_dir=None):
+        import json
+        from . import coco_eval
+        if isinstance(annotations, (str, bytes)) or hasattr(annotations, "__fspath__"):
+            with open(annotations) as f:
+                annotations = json.load(f)
+        if tasks is not None:
+            tasks = tuple(tasks)
+            for t in tasks:
+                if t == "keypoints":
+                    raise NotImplementedError('COCOEvaluator: task "keypoints" (OKS) is not built')
+                if t not in ("bbox", "segm"):
+                    raise ValueError("COCOEvaluator: unknown task {!r}".format(t))
+        self._tasks = tasks
+        self._distributed = distributed
+        self._output_dir = output_dir
+        self._gt = coco_eval.GroundTruth(annotations)
+        self._do_evaluation = self._gt.has_annotations         # test-set files carry no annotations
+        self.thing_dataset_id_to_contiguous_id = {c: k for k, c in enumerate(self._gt.cat_ids)}
+        self.thing_classes = [self._gt.cat_names[c] for c in self._gt.cat_ids]
+        self.reset()
+
+    def reset(self):
+        self._predictions = []
+
+    def _table(self, instances, img_id):
+        from . import coco_eval, ops
+        if img_id not in self._gt.images:
+            raise ValueError("COCOEvaluator: image_id {!r} is not in the annotation file".format(img_id))
+        h, w = self._gt.size(img_id)
+        masks = instances.pred_masks
+        if masks.dim() != 3 or tuple(masks.shape[1:]) != (h, w):
+            raise ValueError("COCOEvaluator: pred_masks of image {!r} are {}, the annotated size is {}x{}: post-process the instances to the "
+                             "annotated size".format(img_id, "x".join(str(int(v)) for v in masks.shape[1:]), h, w))
+        counts = self._gt.counts(img_id)
+        if masks.is_cuda:
+            inter, a_dt, a_gt = (t.numpy() for t in ops.mask_intersections(masks, counts, h, w))
+        else:
+            inter, a_dt, a_gt = coco_eval.intersections_host(masks.numpy(), counts, h, w)
+        return inter, a_dt, a_gt
+
+    def process(self, inputs, outputs):
+        from . import wire
+        for inp, out in zip(inputs, outputs):
+            if "proposals" in out:
+                raise NotImplementedError('COCOEvaluator: the "proposals" branch (box proposal AR) is not built')
+            if "instances" not in out:
+                continue
+            inst, img_id = out["instances"], inp["image_id"]
+            pred = {"image_id": img_id, "instances": wire.instances_to_coco_json(inst, img_id)}
+            if self._do_evaluation and len(inst) and inst.has("pred_masks"):
+                pred["table"] = self._table(inst, img_id)
+            self._predictions.append(pred)
+
+    def _gathered(self):
+        import torch.distributed as dist
+        if not (self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return self._predictions
+        rank = dist.get_rank()
+        parts = [None] * dist.get_world_size() if rank == 0 else None
+        dist.gather_object(self._predictions, parts, dst=0)
+        return [p for part in parts for p in part] if rank == 0 else None
+
+    def evaluate(self, img_ids=None):
+        import json
+        import os
+        from . import coco_eval, wire
+        predictions = self._gathered()
+        if predictions is None:                                 # not the main process
+            return {}
+        if len(predictions) == 0:
+            return {}
+        num_classes = len(self._gt.cat_ids)
+        results, tables = [], {}
+        for p in predictions:
+            if "table" in p:
+                tables[p["image_id"]] = p["table"]
+            for k, r in enumerate(p["instances"]):
+                c = r["category_id"]
+                if not 0 <= c < num_classes:
+                    raise ValueError("COCOEvaluator: a prediction has class {}, the annotation file has {} categories".format(c, num_classes))
+                results.append(dict(r, category_id=self._gt.cat_ids[c], _k=k))
+        if self._output_dir:
+            os.makedirs(self._output_dir, exist_ok=True)
+            with open(os.path.join(self._output_dir, "coco_instances_results.json"), "w") as f:
+                json.dump([{k: v for k, v in r.items() if k != "_k"} for r in results], f)
+        if not self._do_evaluation:
+            return {}
+        tasks = self._tasks or (("bbox", "segm") if any("segmentation" in r for r in results) else ("bbox",))
+        out = {}
+        for task in sorted(tasks):
+            names = ("AP", "AP50", "AP75", "APs", "APm", "APl")
+            if not results:
+                out[task] = {n: float("nan") for n in names}
+                continue
+            if task == "segm":
+                missing = sorted(set(r["image_id"] for r in results) - set(tables))
+                if missing:
+                    raise ValueError("COCOEvaluator: no mask table for images {}: their instances had no pred_masks".format(missing[:5]))
+            rs = wire.segm_results_ranked_by_mask_score(results) if task == "segm" else results
+            acc = coco_eval.score(self._gt, rs, task, tables, img_ids)
+            res = {n: (float(v) * 100 if v >= 0 else float("nan")) for n, v in zip(coco_eval.STAT_NAMES, acc["stats"])}
+            if num_classes > 1:
+                for k, name in enumerate(self.thing_classes):
+                    pr = acc["precision"][:, :, k, 0, -1]
+                    pr = pr[pr > -1]
+                    res["AP-" + name] = float(np.mean(pr) * 100) if pr.size else float("nan")
+            out[task] = res
+        return out

@@ -1370,3 +1370,109 @@ def mask_rle(masks: torch.Tensor):
         strings.append(data[7 * off:7 * off + lens[k]].tobytes().decode("ascii"))
         off += n
     return counts, strings
+
+
+def _need_bitmasks(masks, what: str) -> torch.Tensor:
+    """The input check of the mask entries, as mask_rle makes it: (R,H,W) bool on the current GPU, made contiguous."""
+    if not torch.is_tensor(masks) or not masks.is_cuda:
+        raise _lib.CmkError("{}: masks are on {}; the device path needs a GPU (no CPU fallback; coco_eval.intersections_host is the host "
+                            "path)".format(what, masks.device if torch.is_tensor(masks) else type(masks).__name__))
+    if masks.dtype != torch.bool or masks.dim() != 3:
+        raise _lib.CmkError("{}: expected (R,H,W) bool bitmasks, got {} {}".format(what, masks.dtype, tuple(masks.shape)))
+    _need_current_device(masks, what)
+    return masks.contiguous()
+
+
+def mask_words(h: int, w: int) -> int:
+    """64-bit words of one packed (h,w) mask."""
+    return (int(h) * int(w) + 63) // 64
+
+
+def _pack_bits_into(masks: torch.Tensor, words: torch.Tensor, areas: torch.Tensor) -> None:
+    r, h, w = masks.shape
+    check(_lib.load().cmk_mask_pack_bits(masks.data_ptr(), r, h, w, words.data_ptr(), areas.data_ptr(), _stream()), "cmk_mask_pack_bits")
+
+
+def mask_pack_bits(masks: torch.Tensor):
+    """(R,H,W) bool bitmasks on the GPU -> (words, areas) on the GPU: words (R, ceil(H*W/64)) int64 holding the 64-bit words of
+    include/cmk.h's packed masks (bit p % 64 of word p / 64 is the row-major pixel p; unused high bits zero), areas (R,) int32."""
+    masks = _need_bitmasks(masks, "mask_pack_bits")
+    r, h, w = masks.shape
+    if h < 1 or w < 1:
+        raise _lib.CmkError("mask_pack_bits: empty {}x{} masks".format(h, w))
+    words = torch.empty((r, mask_words(h, w)), dtype=torch.int64, device=masks.device)
+    areas = torch.empty((r,), dtype=torch.int32, device=masks.device)
+    if r:
+        _pack_bits_into(masks, words, areas)
+    return words, areas
+
+
+def _rle_prefix_sums(counts_list, h: int, w: int, what: str):
+    """COCO run lengths per mask (lists or int tensors) -> (cum int32 (T,), off int64 (M+1,)) as NumPy arrays, after the check the
+    kernel relies on: no negative run and every mask's runs add up to h*w."""
+    import numpy as np
+    h, w = int(h), int(w)
+    if h < 1 or w < 1 or h * w >= 2 ** 31 - 1:
+        raise _lib.CmkError("{}: size {}x{} is outside what int32 positions hold".format(what, h, w))
+    cums, off = [], [0]
+    for k, c in enumerate(counts_list):
+        c = (c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c)).astype(np.int64).reshape(-1)
+        if c.size == 0 or (c < 0).any() or int(c.sum()) != h * w:
+            raise _lib.CmkError("{}: the runs of mask {} add up to {}, not to {}x{} = {} (or one is negative)".format(
+                what, k, int(c.sum()), h, w, h * w))
+        cums.append(np.cumsum(c).astype(np.int32))
+        off.append(off[-1] + c.size)
+    cum = np.concatenate(cums) if cums else np.zeros((0,), dtype=np.int32)
+    return cum, np.asarray(off, dtype=np.int64)
+
+
+def _rle_decode_pack(counts_list, h: int, w: int, want_bitmasks: bool, words: Optional[torch.Tensor] = None,
+                     areas: Optional[torch.Tensor] = None):
+    """-> (words, areas, bitmasks or None) on the current GPU; words/areas may be views to fill (mask_intersections)."""
+    cum, off = _rle_prefix_sums(counts_list, h, w, "mask_rle_decode")
+    m = len(off) - 1
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if words is None:
+        words = torch.empty((m, mask_words(h, w)), dtype=torch.int64, device=dev)
+        areas = torch.empty((m,), dtype=torch.int32, device=dev)
+    bits = torch.empty((m, int(h), int(w)), dtype=torch.uint8, device=dev) if want_bitmasks else None
+    if m:
+        # one upload: [off (m+1) int64 | cum T int32]
+        host = torch.from_numpy(off).view(torch.uint8)
+        buf = torch.cat([host, torch.from_numpy(cum).view(torch.uint8)]).to(dev)
+        p = buf.data_ptr()
+        check(_lib.load().cmk_rle_decode_pack(p + 8 * (m + 1), p, m, int(h), int(w), words.data_ptr(), areas.data_ptr(),
+                                              bits.data_ptr() if want_bitmasks else None, _stream()), "cmk_rle_decode_pack")
+    return words, areas, bits
+
+
+def mask_rle_decode(counts_list, h: int, w: int, want_bitmasks: bool = True):
+    """The inverse of mask_rle: per mask the COCO run lengths (lists or int32 tensors, as mask_rle returns them; column-major, zeros
+    run first) -> (M,h,w) bool bitmasks on the current GPU.  With want_bitmasks=False the bitmaps are not written and the packed
+    (words, areas) of mask_pack_bits come back instead.  Runs that do not add up to h*w are refused before the launch."""
+    words, areas, bits = _rle_decode_pack(counts_list, h, w, want_bitmasks)
+    return bits.bool() if want_bitmasks else (words, areas)
+
+
+def mask_intersections(det_masks: torch.Tensor, gt_counts, h: int, w: int):
+    """Detection bitmasks (N,h,w) bool on the GPU against M ground truths given as COCO run lengths -> (inter (N,M), det_areas (N,),
+    gt_areas (M,)), int32 CPU tensors: pixels in both, and in each.  The bitmaps stay on the device; what crosses the host link is the
+    runs up and N*M + N + M integers down, in one copy."""
+    det_masks = _need_bitmasks(det_masks, "mask_intersections")
+    n, m = int(det_masks.shape[0]), len(gt_counts)
+    if tuple(det_masks.shape[1:]) != (int(h), int(w)):
+        raise _lib.CmkError("mask_intersections: detections are {}x{}, the ground truth {}x{}".format(det_masks.shape[1], det_masks.shape[2], h, w))
+    nw = mask_words(h, w)
+    dev = det_masks.device
+    out = torch.empty((n * m + n + m,), dtype=torch.int32, device=dev)
+    inter, det_areas, gt_areas = out[:n * m], out[n * m:n * m + n], out[n * m + n:]
+    words = torch.empty((n + m, nw), dtype=torch.int64, device=dev)
+    if n:
+        _pack_bits_into(det_masks, words[:n], det_areas)
+    with torch.cuda.device(dev):
+        _rle_decode_pack(gt_counts, h, w, False, words[n:], gt_areas)
+    if n and m:
+        check(_lib.load().cmk_mask_intersections(words.data_ptr(), n, words[n:].data_ptr(), m, int(h), int(w), inter.data_ptr(), _stream()),
+              "cmk_mask_intersections")
+    host = out.cpu()                                                   # the one download
+    return host[:n * m].reshape(n, m), host[n * m:n * m + n], host[n * m + n:]

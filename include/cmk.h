@@ -421,6 +421,24 @@ int cmk_rle_count(const uint8_t* masks, int R, int H, int W, void* ws, int64_t w
 int cmk_rle_encode(const uint8_t* masks, int R, int H, int W, const void* ws, int64_t ws_bytes, const int32_t* n_runs, int32_t* starts,
                    int32_t* counts, uint8_t* bytes, int64_t* lens, void* stream);
 
+/* ---- mask IoU counts for COCO evaluation (evaluation/coco_evaluation.py:543-591 hands results and annotations to pycocotools, whose
+ * hot loop is the IoU of every detection mask with every ground-truth mask of an image).  A packed mask is ceil(H*W / 64) 64-bit words:
+ * bit p % 64 of word p / 64 is the row-major pixel p = y*W + x, the unused high bits of the last word are zero.  All results are
+ * integers.  Refused: H or W < 1, H*W >= 2^31 - 1 (positions and areas are int32), a mask count above 65535, null pointers (the bitmask
+ * output of the decoder excepted).  A mask count of 0 is CMK_OK with no launch.  Nothing is allocated or synchronised.
+ * evaluation/coco_evaluation.py:543-591, detections: masks (R,H,W) bytes 0/1 as cmk_paste_masks writes them -> words (R, ceil(H*W/64))
+ * and areas[r], the set pixels of mask r. */
+int cmk_mask_pack_bits(const uint8_t* masks, int R, int H, int W, uint64_t* words, int32_t* areas, void* stream);
+/* evaluation/coco_evaluation.py:543-591, ground truth: the inverse of the RLE encoder.  Mask m is given by the inclusive prefix sums
+ * cum[off[m]] .. cum[off[m+1] - 1] of its COCO run lengths (column-major positions x*H + y, zeros run first, possibly 0 long); the last
+ * prefix sum of every mask must be H*W, which the caller checks: the kernel does not.  Writes the packed row-major words, areas, and the
+ * (M,H,W) byte bitmasks unless `bitmasks` is null. */
+int cmk_rle_decode_pack(const int32_t* cum, const int64_t* off, int M, int H, int W, uint64_t* words, int32_t* areas, uint8_t* bitmasks,
+                        void* stream);
+/* evaluation/coco_evaluation.py:543-591, the table: inter[n*M + m] = popcount(det[n] AND gt[m]) over packed det (N, words) and
+ * gt (M, words).  Zeroes inter on the stream, then accumulates with integer atomics.  N == 0 or M == 0: CMK_OK, nothing written. */
+int cmk_mask_intersections(const uint64_t* det, int N, const uint64_t* gt, int M, int H, int W, int32_t* inter, void* stream);
+
 /* ---- multi-GPU result exchange (the reference's analogue: comm.gather in evaluation/coco_evaluation.py:155-156) ----------
  * One fixed-stride float record per image, written straight into the all-gather send buffer:
  * [box 4K | score K | mask_score K | loc 2K | class K (as float) | mask K*hw*hw | count], K*(9 + hw*hw) + 1 floats. */
