@@ -1,7 +1,7 @@
 """centermask2_amd — MI355X-native CenterMask2 inference hot path (VoVNetV2-FPN, FCOS, CenterROIHeads)."""
 __version__ = "0.1.0"
 
-__all__ = ["Predictor", "load_weights", "__version__"]
+__all__ = ["Predictor", "load_weights", "Visualizer", "draw_instance_predictions", "__version__"]
 
 
 def __getattr__(name):
@@ -9,4 +9,7 @@ def __getattr__(name):
     if name in ("Predictor", "load_weights"):
         from . import predictor
         return getattr(predictor, name)
+    if name in ("Visualizer", "draw_instance_predictions"):
+        from . import visualize
+        return getattr(visualize, name)
     raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))

@@ -1,0 +1,387 @@
+// Device-side visualizer: boxes, half-transparent masks with outlines, "NAME score%" labels and keypoints drawn onto a uint8 (H,W,3)
+// image (the reference's visualizer.py:21-38 hands the Instances to detectron2's matplotlib Visualizer on the host; the picture here is
+// this package's own, defined in integer arithmetic so that a NumPy restatement agrees byte for byte: DESIGN §3 "Visualizer").
+//
+//   prepare  : vis_prepare_kernel   — one thread per instance in draw order: integer box rect, label glyphs, plate rect, the three colours,
+//                                     VIS_REC int32 per instance.  Nothing about an instance is computed on the host.
+//   compose  : vis_compose_kernel   — one wave per 64-pixel word of the packed masks (cmk_mask_pack_bits), lane = pixel.  Per 64 instances
+//                                     every lane tests ONE instance against the word (its mask word non-zero, or the word's pixel span
+//                                     meets the rect around its box and plate) and keeps that instance's record, word and neighbour
+//                                     windows in its registers; a ballot leaves the instances that touch the word, and only those are
+//                                     walked, in draw order, their values read from the holding lane: no memory latency in the walk.
+//                                     The outline needs the bits at p-1, p+1, p-W, p+W: four 64-bit windows cut from at most two words
+//                                     each, whatever W % 64 is.  The pixels of a full word are 192 contiguous bytes: 48 lanes move them
+//                                     as dwords and the wave redistributes them with two shuffles each way; the last, partial word
+//                                     moves bytes.
+//   keypoints: vis_kp_clear_kernel  — zeroes the int32 (H,W) winner map;
+//              vis_kp_raise_kernel  — one workgroup per primitive (skeleton segment or keypoint disc): atomicMax of its sequence number
+//                                     into the winner map over the primitive's own bounding box;
+//              vis_kp_colour_kernel — one pass over the winner map colours the pixels some primitive won.  The latest primitive wins a
+//                                     pixel whatever the order of the atomics.
+// Every store is an ordinary vector store, the atomics are vector atomics.
+#include "cmk_common.hpp"
+
+namespace cmk {
+
+constexpr int VIS_REC = 28;          // int32 per instance record, a multiple of 4: every record is 16-byte aligned
+// record layout
+constexpr int VR_HIT = 0;            // hx0, hy0, hx1, hy1: the rect that holds box and plate (empty without a box)
+constexpr int VR_SRC = 4;            // original index of the instance (its mask words, its keypoints)
+constexpr int VR_FLAGS = 5;          // bit 0: box and label are drawn (no NaN coordinate)
+constexpr int VR_LEN = 6;            // label length, <= 32
+constexpr int VR_COL = 7;            // col: bytes 0..2 are the image's channels 0..2
+constexpr int VR_BOX = 8;            // bx0, by0, bx1, by1 (inclusive, unclipped)
+constexpr int VR_PLATE = 12;         // px0, py0, pw, ph
+constexpr int VR_EDGE = 16;          // edge, text colours, two spare ints
+constexpr int VR_TEXT = 17;
+constexpr int VR_GLYPH = 20;         // 32 glyph indices as bytes, 8 ints
+constexpr int VIS_GLYPHS = 41, VIS_G_SPACE = 0, VIS_G_0 = 1, VIS_G_C = 13, VIS_G_PCT = 37, VIS_G_MINUS = 39;     // glyph 40 is "?"
+
+__device__ inline int vis_floor_clamped(float v, float lim) { return (int)floorf(fminf(fmaxf(v, -lim), lim)); }
+__device__ inline int vis_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ inline int vis_pack3(int a, int b, int c) { return a | (b << 8) | (c << 16); }
+
+__device__ inline void vis_put(uint8_t* g, int& len, int glyph) {
+    if (len < 32) g[len++] = (uint8_t)glyph;
+}
+__device__ inline void vis_put_decimal(uint8_t* g, int& len, unsigned long long v) {
+    unsigned long long div = 1;
+    while (v / div >= 10) div *= 10;
+    for (; div; div /= 10) vis_put(g, len, VIS_G_0 + (int)(v / div % 10));
+}
+
+// grid = ceil(n / 64)
+__global__ __launch_bounds__(64) void vis_prepare_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, const long long* __restrict__ classes,
+                                                        const long long* __restrict__ order, const uint8_t* __restrict__ names,
+                                                        const int32_t* __restrict__ name_lens, int num_names, const uint8_t* __restrict__ palette, int n,
+                                                        int H, int W, int scale, int by_class, int32_t* __restrict__ records) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= n) return;
+    long long src = order[j];
+    if (src < 0 || src >= n) src = j;                               // never read outside the inputs, whatever `order` holds
+    int32_t* r = records + (long)j * VIS_REC;
+    const long long cls = classes[src];
+
+    const long long k = by_class ? cls : src;
+    const uint8_t* pal = palette + 3 * (int)(((k % 64) + 64) % 64);
+    int col[3], edge[3], text[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        col[c] = pal[c];
+        edge[c] = (col[c] * 154) >> 8;
+        text[c] = col[c] + (((255 - col[c]) * 179) >> 8);
+    }
+    r[VR_COL] = vis_pack3(col[0], col[1], col[2]);
+    r[VR_EDGE] = vis_pack3(edge[0], edge[1], edge[2]);
+    r[VR_TEXT] = vis_pack3(text[0], text[1], text[2]);
+    r[VR_TEXT + 1] = r[VR_TEXT + 2] = 0;
+    r[VR_SRC] = (int)src;
+
+    // label: NAME + " " + P + "%"
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r[VR_GLYPH + i] = 0;
+    uint8_t* g = (uint8_t*)(r + VR_GLYPH);
+    int len = 0;
+    if (cls >= 0 && cls < num_names) {
+        const int nl = min(max(name_lens[cls], 0), 32);
+        for (int i = 0; i < nl; ++i) vis_put(g, len, min((int)names[cls * 32 + i], VIS_GLYPHS - 1));
+    } else {
+        vis_put(g, len, VIS_G_C);
+        if (cls < 0) vis_put(g, len, VIS_G_MINUS);
+        vis_put_decimal(g, len, cls < 0 ? 0ull - (unsigned long long)cls : (unsigned long long)cls);
+    }
+    const double sc = (double)scores[src];                          // float32 * 100 is exact in float64: contraction changes nothing
+    const double pf = floor(sc * 100.0 + 0.5);
+    const int pct = sc != sc ? 0 : (pf < 0.0 ? 0 : (pf > 100.0 ? 100 : (int)pf));
+    vis_put(g, len, VIS_G_SPACE);
+    vis_put_decimal(g, len, (unsigned long long)pct);
+    vis_put(g, len, VIS_G_PCT);
+    r[VR_LEN] = len;
+
+    const float x1 = boxes[src * 4], y1 = boxes[src * 4 + 1], x2 = boxes[src * 4 + 2], y2 = boxes[src * 4 + 3];
+    const bool nan = x1 != x1 || y1 != y1 || x2 != x2 || y2 != y2;
+    const float lim = 1048576.f;
+    const int bx0 = nan ? 0 : vis_floor_clamped(x1, lim), by0 = nan ? 0 : vis_floor_clamped(y1, lim);
+    const int bx1 = nan ? -1 : vis_floor_clamped(x2, lim), by1 = nan ? -1 : vis_floor_clamped(y2, lim);
+    const int pw = (6 * len + 1) * scale, ph = 9 * scale;
+    r[VR_FLAGS] = nan ? 0 : 1;
+    r[VR_BOX] = bx0, r[VR_BOX + 1] = by0, r[VR_BOX + 2] = bx1, r[VR_BOX + 3] = by1;
+    r[VR_PLATE] = vis_clampi(bx0, 0, max(0, W - pw));
+    r[VR_PLATE + 1] = vis_clampi(by0, 0, max(0, H - ph));
+    r[VR_PLATE + 2] = pw, r[VR_PLATE + 3] = ph;
+    r[VR_HIT] = nan ? 0 : min(bx0, r[VR_PLATE]), r[VR_HIT + 1] = nan ? 0 : min(by0, r[VR_PLATE + 1]);
+    r[VR_HIT + 2] = nan ? -1 : max(bx1, r[VR_PLATE] + pw - 1), r[VR_HIT + 3] = nan ? -1 : max(by1, r[VR_PLATE + 1] + ph - 1);
+}
+
+// 64 mask bits starting at bit position q of a packed mask (wave-uniform); positions outside [0, 64 * nw) read as zero, as the tail does
+__device__ inline unsigned long long vis_bits64(const unsigned long long* __restrict__ w, long q, int nw) {
+    if (q <= -64 || q >= (long)nw * 64) return 0ull;
+    const long wi = q >> 6;                                          // floor: -1 for q in [-63, -1]
+    const int sh = (int)(q & 63);
+    const unsigned long long lo = wi >= 0 ? w[wi] : 0ull;
+    if (!sh) return lo;
+    const unsigned long long hi = wi + 1 < nw ? w[wi + 1] : 0ull;
+    return (lo >> sh) | (hi << (64 - sh));
+}
+
+// does the rect [x0, x1] x [y0, y1] meet the pixel span (columns [sx0, sx1] of rows [sy0, sy1])
+__device__ inline bool vis_meets(int x0, int y0, int x1, int y1, int sx0, int sy0, int sx1, int sy1) {
+    return x0 <= sx1 && x1 >= sx0 && y0 <= sy1 && y1 >= sy0;
+}
+
+// the value lane l (wave-uniform) holds
+__device__ inline int vis_lane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ inline unsigned long long vis_lane(unsigned long long v, int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// grid = ceil(nw / 4), 4 independent waves per workgroup; words may be null (no masks); vec: both images are 4-byte aligned
+__global__ __launch_bounds__(256) void vis_compose_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W, int nw,
+                                                         const unsigned long long* __restrict__ words, const int32_t* __restrict__ recs, int n,
+                                                         const uint8_t* __restrict__ font, int lw, int s, int A, int vec) {
+    const int lane = threadIdx.x & 63;
+    const int wi = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (wi >= nw) return;
+    const long HW = (long)H * W;
+    const long p0 = (long)wi * 64, p = p0 + lane;
+    const bool full = vec && p0 + 64 <= HW;                          // wave-uniform
+    const int y = (int)(p / W), x = (int)(p - (long)y * W);
+
+    int c0 = 0, c1 = 0, c2 = 0;
+    if (full) {
+        const uint32_t d = lane < 48 ? reinterpret_cast<const uint32_t*>(in + p0 * 3)[lane] : 0u;
+        const int di = (lane * 3) >> 2, sh = ((lane * 3) & 3) * 8;
+        const unsigned long long ab = (unsigned long long)__shfl(d, di, 64) | ((unsigned long long)__shfl(d, (di + 1) & 63, 64) << 32);
+        const unsigned pix = (unsigned)(ab >> sh);
+        c0 = pix & 255, c1 = (pix >> 8) & 255, c2 = (pix >> 16) & 255;
+    } else if (p < HW) {
+        c0 = in[p * 3], c1 = in[p * 3 + 1], c2 = in[p * 3 + 2];
+    }
+
+    // the word's pixel span, wave-uniform
+    const long plast = min(p0 + 63, HW - 1);
+    const int sy0 = (int)(p0 / W), sy1 = (int)(plast / W);
+    const int sx0 = sy0 == sy1 ? (int)(p0 - (long)sy0 * W) : 0, sx1 = sy0 == sy1 ? (int)(plast - (long)sy1 * W) : W - 1;
+
+    for (int j0 = 0; j0 < n; j0 += 64) {
+        // lane l holds instance j0 + l: its record as five int4, its word here and the four neighbour windows; does it touch this word
+        int4 q0 = {0, 0, -1, -1}, q1 = {0, 0, 0, 0}, qb = q0, qp = q1, qe = q1;
+        unsigned long long mine = 0ull, up = 0ull, down = 0ull, left = 0ull, right = 0ull;
+        if (j0 + lane < n) {
+            const int4* r = reinterpret_cast<const int4*>(recs + (long)(j0 + lane) * VIS_REC);
+            q0 = r[0], q1 = r[1], qb = r[2], qp = r[3], qe = r[4];
+            if (words) {
+                const unsigned long long* w = words + (long)q1.x * nw;
+                mine = w[wi];
+                if (mine) {
+                    up = vis_bits64(w, p0 - W, nw), down = vis_bits64(w, p0 + W, nw);
+                    left = vis_bits64(w, p0 - 1, nw), right = vis_bits64(w, p0 + 1, nw);
+                }
+            }
+        }
+        unsigned long long todo = __ballot(mine != 0ull || vis_meets(q0.x, q0.y, q0.z, q0.w, sx0, sy0, sx1, sy1));
+        while (todo) {                                               // wave-uniform walk in draw order, no memory in it but the glyphs
+            const int l = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const unsigned long long M = vis_lane(mine, l);
+            const int flags = vis_lane(q1.y, l), col = vis_lane(q1.w, l);
+            if (flags & 1) {
+                const int bx0 = vis_lane(qb.x, l), by0 = vis_lane(qb.y, l), bx1 = vis_lane(qb.z, l), by1 = vis_lane(qb.w, l);
+                if (x >= bx0 && x <= bx1 && y >= by0 && y <= by1 && (x - bx0 < lw || bx1 - x < lw || y - by0 < lw || by1 - y < lw))
+                    c0 = col & 255, c1 = (col >> 8) & 255, c2 = (col >> 16) & 255;
+            }
+            if (M) {
+                const unsigned long long U = vis_lane(up, l), D = vis_lane(down, l), L = vis_lane(left, l), R = vis_lane(right, l);
+                if ((M >> lane) & 1) {
+                    c0 = (c0 * (256 - A) + (col & 255) * A + 128) >> 8;
+                    c1 = (c1 * (256 - A) + ((col >> 8) & 255) * A + 128) >> 8;
+                    c2 = (c2 * (256 - A) + ((col >> 16) & 255) * A + 128) >> 8;
+                    const bool inner = ((U >> lane) & 1) && ((D >> lane) & 1) && x > 0 && ((L >> lane) & 1) && x < W - 1 && ((R >> lane) & 1);
+                    if (!inner) {
+                        const int e = vis_lane(qe.x, l);
+                        c0 = e & 255, c1 = (e >> 8) & 255, c2 = (e >> 16) & 255;
+                    }
+                }
+            }
+            if (flags & 1) {
+                const int lx = x - vis_lane(qp.x, l), ly = y - vis_lane(qp.y, l);
+                if (lx >= 0 && lx < vis_lane(qp.z, l) && ly >= 0 && ly < vis_lane(qp.w, l)) {
+                    c0 = (c0 * 51 + 128) >> 8, c1 = (c1 * 51 + 128) >> 8, c2 = (c2 * 51 + 128) >> 8;
+                    const int cx = lx / s - 1, cy = ly / s - 1;
+                    if (cx >= 0 && cy >= 0 && cy < 7) {
+                        const int gj = cx / 6, gc = cx - gj * 6;
+                        if (gj < vis_lane(q1.z, l) && gj < 32 && gc < 5) {
+                            const uint8_t* glyphs = reinterpret_cast<const uint8_t*>(recs + (long)(j0 + l) * VIS_REC + VR_GLYPH);
+                            const int g = min((int)glyphs[gj], VIS_GLYPHS - 1);
+                            if ((font[g * 7 + cy] >> (4 - gc)) & 1) {
+                                const int t = vis_lane(qe.y, l);
+                                c0 = t & 255, c1 = (t >> 8) & 255, c2 = (t >> 16) & 255;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    if (full) {
+        const unsigned pix = (unsigned)vis_pack3(c0, c1, c2);
+        const int q = min((lane * 4) / 3, 62), sh = (lane * 4 - q * 3) * 8;      // lanes >= 48 shuffle along and store nothing
+        const unsigned a = __shfl(pix, q, 64), b = __shfl(pix, q + 1, 64);
+        const unsigned d = (unsigned)((((unsigned long long)b << 24) | a) >> sh);
+        if (lane < 48) reinterpret_cast<uint32_t*>(out + p0 * 3)[lane] = d;
+    } else if (p < HW) {
+        out[p * 3] = (uint8_t)c0, out[p * 3 + 1] = (uint8_t)c1, out[p * 3 + 2] = (uint8_t)c2;
+    }
+}
+
+// a keypoint (x, y, score) -> its integer centre; false when it is not drawn
+__device__ inline bool vis_kp_visible(const float* __restrict__ kp, float thr, int& x, int& y) {
+    const float fx = kp[0], fy = kp[1], sc = kp[2];
+    if (!(sc > thr) || fx != fx || fy != fy) return false;
+    x = vis_floor_clamped(fx, 32768.f), y = vis_floor_clamped(fy, 32768.f);
+    return true;
+}
+
+// grid = n * (S + K) primitives: of the instance at draw position j first its S segments, then its K discs; sequence number prim + 1
+__global__ __launch_bounds__(256) void vis_kp_raise_kernel(const float* __restrict__ kps, const int32_t* __restrict__ recs, int K, const int32_t* __restrict__ skel,
+                                                          int S, float thr, int lw, int H, int W, int32_t* __restrict__ win) {
+    const int prim = blockIdx.x, j = prim / (S + K), t = prim - j * (S + K);
+    const float* kp = kps + (long)recs[(long)j * VIS_REC + VR_SRC] * K * 3;
+    int ax, ay, bx, by, rad;
+    const bool seg = t < S;
+    if (seg) {
+        const int ka = skel[2 * t], kb = skel[2 * t + 1];
+        if (ka < 0 || ka >= K || kb < 0 || kb >= K) return;
+        if (!vis_kp_visible(kp + 3 * ka, thr, ax, ay) || !vis_kp_visible(kp + 3 * kb, thr, bx, by)) return;
+        rad = lw;                                                    // 4 d^2 <= lw^2: within lw / 2 of the segment
+    } else {
+        if (!vis_kp_visible(kp + 3 * (t - S), thr, ax, ay)) return;
+        bx = ax, by = ay;
+        rad = max(2, lw + 1);
+    }
+    const int x0 = max(min(ax, bx) - rad, 0), x1 = min(max(ax, bx) + rad, W - 1);
+    const int y0 = max(min(ay, by) - rad, 0), y1 = min(max(ay, by) + rad, H - 1);
+    if (x0 > x1 || y0 > y1) return;
+    const long long dx = bx - ax, dy = by - ay, dd = dx * dx + dy * dy, lw2 = (long long)lw * lw;
+    // the bounding box in 16 x 16 tiles, a thread per pixel.  A tile whose centre is further from the segment than the primitive's reach
+    // plus the tile's half diagonal (11.4) holds no pixel of it: a float test with a pixel to spare skips it for the whole workgroup;
+    // which pixels of the other tiles are on is decided by the exact integer test alone.
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const float fdx = (float)dx, fdy = (float)dy, fdd = (float)dd, reach = (float)rad + 13.f;
+    for (int ty0 = y0; ty0 <= y1; ty0 += 16) {
+        for (int tx0 = x0; tx0 <= x1; tx0 += 16) {
+            const float cx = (float)(tx0 - ax) + 7.5f, cy = (float)(ty0 - ay) + 7.5f;
+            const float tc = fdd > 0.f ? fminf(fmaxf((cx * fdx + cy * fdy) / fdd, 0.f), 1.f) : 0.f;
+            const float ex = cx - tc * fdx, ey = cy - tc * fdy;
+            if (ex * ex + ey * ey > reach * reach) continue;         // uniform over the workgroup
+            const int xx = tx0 + tx, yy = ty0 + ty;
+            if (xx > x1 || yy > y1) continue;
+            const long long ux = xx - ax, uy = yy - ay;
+            bool on;
+            if (!seg) {
+                on = ux * ux + uy * uy <= (long long)rad * rad;
+            } else {
+                const long long tt = ux * dx + uy * dy;
+                if (tt <= 0) {
+                    on = 4 * (ux * ux + uy * uy) <= lw2;
+                } else if (tt >= dd) {
+                    const long long vx = xx - bx, vy = yy - by;
+                    on = 4 * (vx * vx + vy * vy) <= lw2;
+                } else {
+                    const long long cr = ux * dy - uy * dx;          // |cr| < 2^34; lw^2 * dd < 2^42, so a |cr| of 2^21 or more is off
+                    on = cr > -(1ll << 21) && cr < (1ll << 21) && 4 * cr * cr <= lw2 * dd;
+                }
+            }
+            if (on) atomicMax(win + (long)yy * W + xx, prim + 1);
+        }
+    }
+}
+
+// the winner map starts at "no primitive": a kernel of the library's own, so that a captured draw replays it like every other node
+__global__ __launch_bounds__(256) void vis_kp_clear_kernel(int32_t* __restrict__ win, long HW) {
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long)gridDim.x * 256) win[p] = 0;
+}
+
+__global__ __launch_bounds__(256) void vis_kp_colour_kernel(uint8_t* __restrict__ image, long HW, const int32_t* __restrict__ win, const int32_t* __restrict__ recs,
+                                                           int S, int K, int kp_col) {
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long)gridDim.x * 256) {
+        const int v = win[p];
+        if (v <= 0) continue;
+        const int j = (v - 1) / (S + K), t = (v - 1) - j * (S + K);
+        const int c = t < S ? recs[(long)j * VIS_REC + VR_COL] : kp_col;
+        image[p * 3] = (uint8_t)(c & 255), image[p * 3 + 1] = (uint8_t)((c >> 8) & 255), image[p * 3 + 2] = (uint8_t)((c >> 16) & 255);
+    }
+}
+
+// shared argument check; the messages name the entry
+inline int vis_check(const char* what, int H, int W, int n) {
+    if (H < 1 || W < 1) return fail(CMK_EINVAL, "%s: H = %ld, W = %ld must be at least 1", what, H, W);
+    if ((int64_t)H * W >= 0x7fffffffLL) return fail(CMK_EINVAL, "%s: H*W of %ld x %ld does not leave int32 pixel positions", what, H, W);
+    if (n < 0 || n > 65535) return fail(CMK_EINVAL, "%s: instance count %ld outside [0, 65535]", what, n);
+    return CMK_OK;
+}
+
+inline int vis_check_width(const char* what, const char* name, int v) {
+    if (v >= 1 && v <= 16) return CMK_OK;
+    snprintf(g_err, sizeof(g_err), "%s: %s = %d outside [1, 16]", what, name, v);
+    return CMK_EINVAL;
+}
+
+}  // namespace cmk
+
+using namespace cmk;
+
+extern "C" int cmk_vis_record_ints(void) { return VIS_REC; }
+
+extern "C" int cmk_vis_prepare(const float* boxes, const float* scores, const int64_t* classes, const int64_t* order, const uint8_t* names,
+                               const int32_t* name_lens, int num_names, const uint8_t* palette, int n, int H, int W, int font_scale, int color_by_class,
+                               int32_t* records, void* stream) {
+    if (int rc = vis_check("vis_prepare", H, W, n)) return rc;
+    if (int rc = vis_check_width("vis_prepare", "font_scale", font_scale)) return rc;
+    if (num_names < 0 || num_names > 65535) return fail(CMK_EINVAL, "%s: %ld names outside [0, 65535]", "vis_prepare", num_names);
+    if (n == 0) return CMK_OK;
+    if (!boxes || !scores || !classes || !order || !palette || !records || (num_names && (!names || !name_lens)))
+        return fail(CMK_EINVAL, "%s: null pointer", "vis_prepare");
+    hipLaunchKernelGGL(vis_prepare_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, boxes, scores, (const long long*)classes,
+                       (const long long*)order, names, name_lens, num_names, palette, n, H, W, font_scale, color_by_class ? 1 : 0, records);
+    return check_launch("vis_prepare");
+}
+
+extern "C" int cmk_vis_compose(const uint8_t* image_in, uint8_t* image_out, int H, int W, const uint64_t* words, const int32_t* records, int n,
+                               const uint8_t* font, int line_width, int font_scale, int alpha256, void* stream) {
+    if (int rc = vis_check("vis_compose", H, W, n)) return rc;
+    if (int rc = vis_check_width("vis_compose", "line_width", line_width)) return rc;
+    if (int rc = vis_check_width("vis_compose", "font_scale", font_scale)) return rc;
+    if (alpha256 < 0 || alpha256 > 256) return fail(CMK_EINVAL, "%s: alpha256 = %ld outside [0, 256]", "vis_compose", alpha256);
+    if (!image_in || !image_out || (n && (!records || !font))) return fail(CMK_EINVAL, "%s: null pointer", "vis_compose");
+    const int64_t bytes = (int64_t)H * W * 3;
+    if (image_in < image_out + bytes && image_out < image_in + bytes)
+        return fail(CMK_EINVAL, "%s: image_out overlaps image_in; the compose pass is out of place", "vis_compose");
+    if ((uintptr_t)records & 15) return fail(CMK_EINVAL, "%s: records must be 16-byte aligned", "vis_compose");
+    const int nw = (int)(((int64_t)H * W + 63) / 64);
+    const int vec = (((uintptr_t)image_in | (uintptr_t)image_out) & 3) == 0;
+    hipLaunchKernelGGL(vis_compose_kernel, dim3(cdiv(nw, 4)), dim3(256), 0, (hipStream_t)stream, image_in, image_out, H, W, nw,
+                       (const unsigned long long*)words, records, n, font, line_width, font_scale, alpha256, vec);
+    return check_launch("vis_compose");
+}
+
+extern "C" int cmk_vis_keypoints(uint8_t* image, int H, int W, const float* keypoints, const int32_t* records, int n, int num_keypoints,
+                                 const int32_t* skeleton, int num_segments, float threshold, int line_width, int keypoint_color, int32_t* winner,
+                                 void* stream) {
+    if (int rc = vis_check("vis_keypoints", H, W, n)) return rc;
+    if (int rc = vis_check_width("vis_keypoints", "line_width", line_width)) return rc;
+    if (num_keypoints < 1 || num_keypoints > 1024) return fail(CMK_EINVAL, "%s: %ld keypoints outside [1, 1024]", "vis_keypoints", num_keypoints);
+    if (num_segments < 0 || num_segments > 4096) return fail(CMK_EINVAL, "%s: %ld skeleton segments outside [0, 4096]", "vis_keypoints", num_segments);
+    if (n == 0) return CMK_OK;
+    if (!image || !keypoints || !records || !winner || (num_segments && !skeleton)) return fail(CMK_EINVAL, "%s: null pointer", "vis_keypoints");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    hipLaunchKernelGGL(vis_kp_clear_kernel, dim3(stream_grid(HW)), dim3(256), 0, st, winner, (long)HW);
+    hipLaunchKernelGGL(vis_kp_raise_kernel, dim3(n * (num_segments + num_keypoints)), dim3(256), 0, st, keypoints, records, num_keypoints, skeleton,
+                       num_segments, threshold, line_width, H, W, winner);
+    hipLaunchKernelGGL(vis_kp_colour_kernel, dim3(stream_grid(HW)), dim3(256), 0, st, image, (long)HW, (const int32_t*)winner, records, num_segments,
+                       num_keypoints, keypoint_color);
+    return check_launch("vis_keypoints");
+}

@@ -1476,3 +1476,73 @@ def mask_intersections(det_masks: torch.Tensor, gt_counts, h: int, w: int):
               "cmk_mask_intersections")
     host = out.cpu()                                                   # the one download
     return host[:n * m].reshape(n, m), host[n * m:n * m + n], host[n * m + n:]
+
+
+# ---- visualizer (csrc/visualize.hip; the contract is in include/cmk.h and DESIGN §3 "Visualizer") ------------------------------------
+def vis_prepare(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, order: torch.Tensor, names: torch.Tensor,
+                name_lens: torch.Tensor, num_names: int, palette: torch.Tensor, h: int, w: int, font_scale: int, color_by_class: bool) -> torch.Tensor:
+    """Per-instance draw records in draw order, (max(n,1), cmk_vis_record_ints()) int32 on the boxes' device.  boxes (n,4) float32,
+    scores (n,) float32, classes and order (n,) int64, names (rows,32) uint8 glyph indices, name_lens int32, palette (64,3) uint8."""
+    n = int(boxes.shape[0])
+    for t, dt, what in ((boxes, torch.float32, "boxes"), (scores, torch.float32, "scores"), (classes, torch.int64, "classes"),
+                        (order, torch.int64, "order"), (names, torch.uint8, "names"), (name_lens, torch.int32, "name_lens"),
+                        (palette, torch.uint8, "palette")):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise _lib.CmkError("vis_prepare: {} must be contiguous {} on the GPU, got {} {} on {}".format(what, dt, t.dtype, tuple(t.shape), t.device))
+    if tuple(boxes.shape) != (n, 4) or scores.numel() != n or classes.numel() != n or order.numel() != n or palette.numel() != 192 \
+            or names.numel() < 32 * num_names or name_lens.numel() < num_names:
+        raise _lib.CmkError("vis_prepare: boxes {}, scores {}, classes {}, order {}, palette {}, names {} do not fit {} instances and {} names".format(
+            tuple(boxes.shape), tuple(scores.shape), tuple(classes.shape), tuple(order.shape), tuple(palette.shape), tuple(names.shape), n, num_names))
+    _need_current_device(boxes, "vis_prepare")
+    lib = _lib.load()
+    records = torch.empty((max(n, 1), lib.cmk_vis_record_ints()), dtype=torch.int32, device=boxes.device)
+    check(lib.cmk_vis_prepare(boxes.data_ptr(), scores.data_ptr(), classes.data_ptr(), order.data_ptr(), names.data_ptr(), name_lens.data_ptr(),
+                              int(num_names), palette.data_ptr(), n, int(h), int(w), int(font_scale), 1 if color_by_class else 0,
+                              records.data_ptr(), _stream()), "cmk_vis_prepare")
+    return records
+
+
+def vis_compose(image: torch.Tensor, words: Optional[torch.Tensor], records: torch.Tensor, n: int, font: torch.Tensor, line_width: int,
+                font_scale: int, alpha256: int) -> torch.Tensor:
+    """The picture of n records on a contiguous (h,w,3) uint8 GPU image -> a new tensor.  words: mask_pack_bits's (n, mask_words(h,w))
+    int64 by original instance, or None for no masks."""
+    if not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or not image.is_contiguous():
+        raise _lib.CmkError("vis_compose: need a contiguous (h,w,3) uint8 image on the GPU, got {} {} on {}".format(image.dtype, tuple(image.shape), image.device))
+    _need_current_device(image, "vis_compose")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    lib = _lib.load()
+    if n and (records.dtype != torch.int32 or records.numel() < n * lib.cmk_vis_record_ints() or records.device != image.device or font.numel() != 41 * 7
+              or font.dtype != torch.uint8 or font.device != image.device):
+        raise _lib.CmkError("vis_compose: records {} {} / font {} {} do not fit {} instances".format(records.dtype, tuple(records.shape), font.dtype,
+                                                                                                   tuple(font.shape), n))
+    if words is not None and (words.dtype != torch.int64 or tuple(words.shape) != (n, mask_words(h, w)) or not words.is_contiguous()
+                              or words.device != image.device):
+        raise _lib.CmkError("vis_compose: words must be contiguous ({}, {}) int64 on {}, got {} {}".format(n, mask_words(h, w), image.device, words.dtype,
+                                                                                                       tuple(words.shape)))
+    out = torch.empty_like(image)
+    check(lib.cmk_vis_compose(image.data_ptr(), out.data_ptr(), h, w, None if words is None else words.data_ptr(), records.data_ptr(), int(n),
+                              font.data_ptr(), int(line_width), int(font_scale), int(alpha256), _stream()), "cmk_vis_compose")
+    return out
+
+
+def vis_keypoints(image: torch.Tensor, keypoints: torch.Tensor, records: torch.Tensor, skeleton: Optional[torch.Tensor], threshold: float,
+                  line_width: int, keypoint_color: int) -> None:
+    """Skeleton segments and keypoint discs of (n,K,3) float32 keypoints, in place on the composed (h,w,3) image.  skeleton: (S,2) int32
+    on the GPU or None; keypoint_color: bytes 0..2 are the image's channels."""
+    if not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or not image.is_contiguous():
+        raise _lib.CmkError("vis_keypoints: need a contiguous (h,w,3) uint8 image on the GPU, got {} {} on {}".format(image.dtype, tuple(image.shape), image.device))
+    if keypoints.dim() != 3 or keypoints.shape[2] != 3 or keypoints.dtype != torch.float32 or not keypoints.is_contiguous() or keypoints.device != image.device:
+        raise _lib.CmkError("vis_keypoints: need contiguous (n,K,3) float32 keypoints on {}, got {} {} on {}".format(image.device, keypoints.dtype,
+                                                                                                                  tuple(keypoints.shape), keypoints.device))
+    _need_current_device(image, "vis_keypoints")
+    n, k = int(keypoints.shape[0]), int(keypoints.shape[1])
+    nseg = 0 if skeleton is None else int(skeleton.shape[0])
+    lib = _lib.load()
+    if n and (records.dtype != torch.int32 or records.numel() < n * lib.cmk_vis_record_ints() or records.device != image.device):
+        raise _lib.CmkError("vis_keypoints: records {} {} do not fit {} instances".format(records.dtype, tuple(records.shape), n))
+    if nseg and (skeleton.dtype != torch.int32 or tuple(skeleton.shape) != (nseg, 2) or not skeleton.is_contiguous() or skeleton.device != image.device):
+        raise _lib.CmkError("vis_keypoints: the skeleton must be contiguous (S,2) int32 on {}, got {} {}".format(image.device, skeleton.dtype, tuple(skeleton.shape)))
+    h, w = int(image.shape[0]), int(image.shape[1])
+    winner = torch.empty((h, w), dtype=torch.int32, device=image.device)
+    check(lib.cmk_vis_keypoints(image.data_ptr(), h, w, keypoints.data_ptr(), records.data_ptr(), n, k, skeleton.data_ptr() if nseg else None, nseg,
+                                float(threshold), int(line_width), int(keypoint_color), winner.data_ptr(), _stream()), "cmk_vis_keypoints")

@@ -439,6 +439,39 @@ int cmk_rle_decode_pack(const int32_t* cum, const int64_t* off, int M, int H, in
  * gt (M, words).  Zeroes inter on the stream, then accumulates with integer atomics.  N == 0 or M == 0: CMK_OK, nothing written. */
 int cmk_mask_intersections(const uint64_t* det, int N, const uint64_t* gt, int M, int H, int W, int32_t* inter, void* stream);
 
+/* ---- visualizer (visualizer.py:21-38 hands the post-processed Instances to detectron2's Visualizer.draw_instance_predictions, which
+ * draws on the host with matplotlib; this picture is the package's own, in integer arithmetic: DESIGN §3 "Visualizer").  Images are
+ * (H,W,3) uint8, colours are bytes in the image's channel order.  Refused by all three: H or W < 1, H*W >= 2^31 - 1, n < 0 or n > 65535,
+ * a line width or font scale outside 1..16, null pointers.  Nothing is allocated or synchronised.
+ * visualizer.py:21-38, the record of one instance: cmk_vis_record_ints() int32, a multiple of 4 (the layout is the library's own);
+ * cmk_vis_compose reads records through 16-byte loads and refuses a records pointer that is not 16-byte aligned. */
+int cmk_vis_record_ints(void);
+/* visualizer.py:21-38, per instance, on the device: records[j] describes instance order[j] (the draw order, largest box first): the
+ * integer box rect floor(clamp(c, +-2^20)) or "no box, no label" for a NaN coordinate, the label NAME + " " + P + "%" as glyph indices of
+ * the 41-glyph font (P = clamp(floor(score * 100 + 0.5), 0, 100) in float64, NaN -> 0; at most 32 glyphs), its plate rect clamped into the
+ * image, and col = palette[k mod 64] (k the original index, or the class with color_by_class), edge = col*154 >> 8,
+ * text = col + ((255 - col)*179 >> 8).  names: num_names rows of 32 glyph indices with name_lens; a class outside [0, num_names) is
+ * named "C<id>".  palette: 64 x 3 bytes.  boxes (n,4), scores (n), classes (n) int64, order (n) int64.  n == 0: CMK_OK, no launch. */
+int cmk_vis_prepare(const float* boxes, const float* scores, const int64_t* classes, const int64_t* order, const uint8_t* names,
+                    const int32_t* name_lens, int num_names, const uint8_t* palette, int n, int H, int W, int font_scale, int color_by_class,
+                    int32_t* records, void* stream);
+/* visualizer.py:21-38, the picture: image_out = image_in with, per record in order, the box frame (line_width thick, opaque col), the
+ * mask fill c = (c*(256 - alpha256) + col*alpha256 + 128) >> 8, the mask outline (set pixels with an unset or outside 4-neighbour,
+ * opaque edge), the label plate c = (c*51 + 128) >> 8 and its glyphs (font: 41 x 7 row bytes, bit 4 the left column; font_scale^2 pixels
+ * per font pixel; opaque text).  words: the packed masks of cmk_mask_pack_bits, (n, ceil(H*W/64)), indexed by ORIGINAL instance; null
+ * draws no masks.  alpha256 in [0, 256].  Out of place: overlapping images are refused.  n == 0 copies the image (records, font unused). */
+int cmk_vis_compose(const uint8_t* image_in, uint8_t* image_out, int H, int W, const uint64_t* words, const int32_t* records, int n,
+                    const uint8_t* font, int line_width, int font_scale, int alpha256, void* stream);
+/* visualizer.py:21-38, keypoints, IN PLACE on the composed image.  keypoints (n, num_keypoints, 3) as (x, y, score), indexed by original
+ * instance; a point is visible iff score > threshold and neither coordinate is NaN; centres floor(clamp(c, +-2^15)).  Per record in
+ * order: the skeleton's segments (num_segments pairs of keypoint indices; both ends visible; pixels within line_width / 2 of the segment,
+ * exact in int64; colour col), then the visible points as discs of radius max(2, line_width + 1) in keypoint_color (bytes 0..2).  The
+ * latest primitive wins a pixel: winner, (H,W) int32 scratch, takes the atomic maximum of the sequence numbers, a second pass colours.
+ * num_keypoints in [1, 1024], num_segments in [0, 4096].  n == 0: CMK_OK, no launch. */
+int cmk_vis_keypoints(uint8_t* image, int H, int W, const float* keypoints, const int32_t* records, int n, int num_keypoints,
+                      const int32_t* skeleton, int num_segments, float threshold, int line_width, int keypoint_color, int32_t* winner,
+                      void* stream);
+
 /* ---- multi-GPU result exchange (the reference's analogue: comm.gather in evaluation/coco_evaluation.py:155-156) ----------
  * One fixed-stride float record per image, written straight into the all-gather send buffer:
  * [box 4K | score K | mask_score K | loc 2K | class K (as float) | mask K*hw*hw | count], K*(9 + hw*hw) + 1 floats. */

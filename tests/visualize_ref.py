@@ -1,0 +1,170 @@
+"""The tests' own NumPy restatement of the visualizer's rendering rules (DESIGN §3 "Visualizer"), written from the contract: it reads
+(n,h,w) bool masks directly, never packed words, and shares nothing with csrc/visualize.hip but the font and palette tables, which it
+imports as data.  Everything is integer arithmetic on Python ints / int64 arrays; `render` returns the (h,w,3) uint8 picture."""
+import math
+
+import numpy as np
+
+from centermask2_amd.visualize import FONT_5X7, FONT_CHARS, PALETTE_RGB
+
+
+def percent(score) -> int:
+    """clamp(floor(score*100 + 0.5), 0, 100) in float64 of the float32 score; NaN -> 0."""
+    v = float(np.float32(score)) * 100.0 + 0.5
+    if v != v:
+        return 0
+    return int(math.floor(min(max(v, 0.0), 100.0)))
+
+
+def label_text(name: str, score) -> str:
+    return (name + " " + str(percent(score)) + "%").upper()[:32]
+
+
+def glyph_indices(text: str):
+    return [FONT_CHARS.index(c) if c in FONT_CHARS else FONT_CHARS.index("?") for c in text]
+
+
+def draw_order(boxes):
+    """Largest float32 box area first (a NaN area counts as the largest, as torch.sort has it), ties by original index."""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    with np.errstate(all="ignore"):
+        area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    return sorted(range(len(b)), key=lambda i: (0, 0.0, i) if area[i] != area[i] else (1, -float(area[i]), i))
+
+
+def colours(k: int, input_format: str):
+    col = PALETTE_RGB[k % 64]
+    if input_format == "BGR":
+        col = col[::-1]
+    col = tuple(int(c) for c in col)
+    return col, tuple((c * 154) >> 8 for c in col), tuple(c + (((255 - c) * 179) >> 8) for c in col)
+
+
+def _floor_clamped(v, lim):
+    return int(math.floor(min(max(float(v), -float(lim)), float(lim))))
+
+
+def on_disc(px, py, kx, ky, kr) -> bool:
+    return (px - kx) ** 2 + (py - ky) ** 2 <= kr * kr
+
+
+def on_segment(px, py, ax, ay, bx, by, lw) -> bool:
+    """Python ints: exact."""
+    dx, dy = bx - ax, by - ay
+    dd = dx * dx + dy * dy
+    ux, uy = px - ax, py - ay
+    t = ux * dx + uy * dy
+    if t <= 0:
+        return 4 * (ux * ux + uy * uy) <= lw * lw
+    if t >= dd:
+        return 4 * ((px - bx) ** 2 + (py - by) ** 2) <= lw * lw
+    cr = ux * dy - uy * dx
+    return 4 * cr * cr <= lw * lw * dd
+
+
+def _window(h, w, x0, y0, x1, y1):
+    """Pixel coordinate arrays of the part of [x0,x1] x [y0,y1] inside the image, exact (object) where int64 squares could overflow."""
+    x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, w - 1), min(y1, h - 1)
+    if x0 > x1 or y0 > y1:
+        return None
+    ys, xs = np.mgrid[y0:y1 + 1, x0:x1 + 1]
+    return xs.astype(np.int64), ys.astype(np.int64), (slice(y0, y1 + 1), slice(x0, x1 + 1))
+
+
+def _paint_disc(img, kx, ky, kr, colour):
+    win = _window(img.shape[0], img.shape[1], kx - kr, ky - kr, kx + kr, ky + kr)
+    if win is None:
+        return
+    xs, ys, sl = win
+    img[sl][(xs - kx) ** 2 + (ys - ky) ** 2 <= kr * kr] = colour
+
+
+def _paint_segment(img, ax, ay, bx, by, lw, colour):
+    win = _window(img.shape[0], img.shape[1], min(ax, bx) - lw, min(ay, by) - lw, max(ax, bx) + lw, max(ay, by) + lw)
+    if win is None:
+        return
+    xs, ys, sl = win
+    if max(abs(v) for v in (ax, ay, bx, by)) >= 2 ** 13 or max(img.shape[:2]) >= 2 ** 13:      # cross^2 * 4 could leave int64: Python ints
+        xs, ys = xs.astype(object), ys.astype(object)
+    dx, dy = bx - ax, by - ay
+    dd = dx * dx + dy * dy
+    ux, uy = xs - ax, ys - ay
+    t = ux * dx + uy * dy
+    cr = ux * dy - uy * dx
+    near_a = 4 * (ux * ux + uy * uy) <= lw * lw
+    near_b = 4 * ((xs - bx) ** 2 + (ys - by) ** 2) <= lw * lw
+    near_line = 4 * cr * cr <= lw * lw * dd
+    on = np.where(t <= 0, near_a, np.where(t >= dd, near_b, near_line)).astype(bool)
+    img[sl][on] = colour
+
+
+def render(image, boxes, scores, classes, masks=None, keypoints=None, class_names=None, alpha=0.5, line_width=None, font_scale=None,
+           color_by="instance", keypoint_threshold=0.05, skeleton=(), input_format="BGR"):
+    """image (h,w,3) uint8; boxes (n,4) float32; scores (n,) float32; classes (n,) ints; masks (n,h,w) bool or None;
+    keypoints (n,K,3) float32 or None; skeleton: pairs of keypoint indices.  -> a new (h,w,3) uint8 array."""
+    img = np.array(image, dtype=np.uint8, copy=True)
+    h, w = img.shape[:2]
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    n = len(boxes)
+    lw = int(line_width) if line_width is not None else max(1, int(math.floor(min(h, w) / 400 + 0.5)))
+    s = int(font_scale) if font_scale is not None else max(1, int(math.floor(min(h, w) / 500 + 0.5)))
+    A = int(math.floor(alpha * 256 + 0.5))
+    ys, xs = np.mgrid[0:h, 0:w]
+    order = draw_order(boxes)
+    cols = {}
+    for i in order:
+        cls = int(classes[i])
+        col, edge, text = colours(i if color_by == "instance" else cls, input_format)
+        cols[i] = col
+        has_box = not bool(np.isnan(boxes[i]).any())
+        if has_box:
+            bx0, by0, bx1, by1 = (_floor_clamped(v, 2 ** 20) for v in boxes[i])
+            inside = (xs >= bx0) & (xs <= bx1) & (ys >= by0) & (ys <= by1)
+            frame = inside & ((xs - bx0 < lw) | (bx1 - xs < lw) | (ys - by0 < lw) | (by1 - ys < lw))
+            img[frame] = col
+        if masks is not None:
+            m = np.asarray(masks[i], dtype=bool)
+            c = img[m].astype(np.int64)
+            img[m] = ((c * (256 - A) + np.array(col, dtype=np.int64) * A + 128) >> 8).astype(np.uint8)
+            pad = np.zeros((h + 2, w + 2), dtype=bool)
+            pad[1:-1, 1:-1] = m
+            inner = pad[:-2, 1:-1] & pad[2:, 1:-1] & pad[1:-1, :-2] & pad[1:-1, 2:]
+            img[m & ~inner] = edge
+        if has_box:
+            name = class_names[cls] if class_names is not None and 0 <= cls < len(class_names) else "C" + str(cls)
+            glyphs = glyph_indices(label_text(name, scores[i]))
+            pw, ph = (6 * len(glyphs) + 1) * s, 9 * s
+            px0, py0 = min(max(bx0, 0), max(0, w - pw)), min(max(by0, 0), max(0, h - ph))
+            plate = img[py0:py0 + ph, px0:px0 + pw]                 # a view: slicing clips at the image's edge
+            plate[...] = ((plate.astype(np.int64) * 51 + 128) >> 8).astype(np.uint8)
+            for j, g in enumerate(glyphs):
+                for row in range(7):
+                    for c5 in range(5):
+                        if (FONT_5X7[g][row] >> (4 - c5)) & 1:
+                            gx, gy = px0 + (1 + 6 * j + c5) * s, py0 + (1 + row) * s
+                            img[gy:gy + s, gx:gx + s] = text
+    if keypoints is not None:
+        kp = np.asarray(keypoints, dtype=np.float32)
+        red = (255, 0, 0)[::-1] if input_format == "BGR" else (255, 0, 0)
+        kr = max(2, lw + 1)
+        for i in order:
+            pts = []
+            for x, y, sc in kp[i]:
+                vis = bool(np.float32(sc) > np.float32(keypoint_threshold)) and not (sc != sc or x != x or y != y)     # a float32 comparison
+                pts.append((_floor_clamped(x, 2 ** 15), _floor_clamped(y, 2 ** 15)) if vis else None)
+            for a, b in skeleton:
+                if pts[a] is not None and pts[b] is not None:
+                    _paint_segment(img, pts[a][0], pts[a][1], pts[b][0], pts[b][1], lw, cols[i])
+            for p in pts:
+                if p is not None:
+                    _paint_disc(img, p[0], p[1], kr, red)
+    return img
+
+
+def render_instances(image, instances, **kw):
+    """`render` on an Instances whose tensors are downloaded here."""
+    def host(t):
+        return t.detach().cpu().numpy()
+    return render(host(image) if hasattr(image, "detach") else image, host(instances.pred_boxes.tensor), host(instances.scores),
+                  host(instances.pred_classes), masks=host(instances.pred_masks) if instances.has("pred_masks") else None,
+                  keypoints=host(instances.pred_keypoints) if instances.has("pred_keypoints") else None, **kw)
