@@ -101,8 +101,10 @@ using namespace cmk;
 extern "C" int cmk_pack_records(const float* box, const float* score, const float* mask_scores, const float* loc, const int64_t* cls,
                                 const float* masks, const int32_t* counts, int N, int K, int mask_hw, float* rec, void* stream) {
     if (!box || !score || !mask_scores || !loc || !cls || !masks || !counts || !rec) return fail(CMK_EINVAL, "pack_records: null pointer%s", "");
-    if (N < 1 || K < 1 || mask_hw < 1) return fail(CMK_EINVAL, "pack_records: bad shape%s", "");
-    const int width = K * (9 + mask_hw * mask_hw) + 1;
+    if (N < 1 || N > 65535 || K < 1 || mask_hw < 1) return fail(CMK_EINVAL, "pack_records: bad shape%s", "");
+    const long lwidth = (long)K * (9 + (long)mask_hw * mask_hw) + 1;
+    if (lwidth > 0x7fffffffL) return fail(CMK_EINVAL, "pack_records: record too wide%s", "");
+    const int width = (int)lwidth;
     hipLaunchKernelGGL(pack_records_kernel, dim3(cdiv(width, 256 * 4), N), dim3(256), 0, (hipStream_t)stream, box, score, mask_scores, loc, cls, masks,
                        counts, K, mask_hw * mask_hw, rec, width);
     return check_launch("pack_records");

@@ -55,7 +55,8 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const RoiLevels L, int C
     const int max_level = L.min_level + L.num_levels - 1;
     float lvf = L.assign_area ? floorf((float)L.canonical_level + log2f(sqrtf(box_area) / L.canonical_size + 2.220446049250313e-16f))
                               : ceilf((float)max_level - log2f(img_area[n] / box_area + 2.220446049250313e-16f));
-    lvf = fminf(fmaxf(lvf, (float)L.min_level), (float)max_level);   // NaN (0/0 areas) propagates like torch.clamp; see host note
+    lvf = fminf(fmaxf(lvf, (float)L.min_level), (float)max_level);   // fmaxf drops a NaN (0/0 areas, the sqrt of a negative area): such a box lands on
+                                                                     // min_level, where torch.clamp keeps the NaN and the cast to int64 is undefined
     int lv = (int)lvf - L.min_level;
     if (!(lv >= 0 && lv < L.num_levels)) lv = 0;
     if (bin == 0 && lane == 0) out_level[r] = lv;
@@ -190,6 +191,9 @@ __global__ __launch_bounds__(256) void mask_predict_kernel(const float* __restri
     }
 }
 
+// max as max_pool2d takes it: a NaN wins (fmaxf would drop it)
+__device__ inline float max_nan(float a, float b) { return (a != a || a > b) ? a : b; }
+
 // maxpool 2x2 of the (R,2S,2S) masks -> channel y_co of the (R,S,S,y_cs) MaskIoU input; the 15 pad channels after it
 // are zeroed so that zero-padded weights never meet uninitialised memory.
 __global__ __launch_bounds__(256) void mask_pool_kernel(const float* __restrict__ masks, float* __restrict__ y, int y_cs, int y_co, int R,
@@ -199,7 +203,7 @@ __global__ __launch_bounds__(256) void mask_pool_kernel(const float* __restrict_
         int w = (int)(i % S), h = (int)((i / S) % S);
         long r = i / ((long)S * S);
         const float* m = masks + (r * 2 * S + 2 * h) * 2 * S + 2 * w;
-        float v = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2 * S], m[2 * S + 1]));
+        float v = max_nan(max_nan(m[0], m[1]), max_nan(m[2 * S], m[2 * S + 1]));
         float* o = y + i * y_cs + y_co;
         o[0] = v;
         for (int j = 1; j < pad; ++j) o[j] = 0.f;
@@ -239,7 +243,11 @@ extern "C" int cmk_roi_align_pool(const float* const* feats, const int* feat_h, 
         L.H[l] = ok ? feat_h[l] : 1;
         L.W[l] = ok ? feat_w[l] : 1;
         L.scale[l] = ok ? scales[l] : 1.f;
+        if (ok && (feat_h[l] < 1 || feat_w[l] < 1)) return fail(CMK_EINVAL, "roi_align: %slevel %ld has no pixels", "", (long)l);
     }
+    // the grid is one dimension of ceil(out^2 / 4) workgroups per RoI slot, the slots padded to a multiple of 8
+    const long lgrid = (((long)out_size * out_size + 3) / 4) * ((((long)N * topk + 7) / 8) * 8);
+    if (lgrid > 0x7fffffffL) return fail(CMK_EINVAL, "roi_align: %s%ld workgroups do not fit the grid", "", lgrid);
     int R = N * topk;
     hipLaunchKernelGGL(roi_align_kernel, dim3(cdiv(out_size * out_size, 4) * (((R + 7) / 8) * 8)), dim3(256), 0, (hipStream_t)stream, L, C, boxes,
                        counts, img_area, topk, out_size, sampling_ratio, y, y_cs, out_level, R);
@@ -256,6 +264,8 @@ extern "C" int cmk_roi_align_ratio(const float* const* feats, const int* feat_h,
 extern "C" int cmk_spatial_attention(float* x, const float* w, const int32_t* counts, int topk, int R, int S, int C, void* stream) {
     if (!x || !w || !counts) return fail(CMK_EINVAL, "spatial_attention: null pointer%s", "");
     if ((C & 3) || S < 1 || R < 1 || topk < 1 || R % topk) return fail(CMK_EINVAL, "spatial_attention: bad shape%s", "");
+    if (3L * S * S * (long)sizeof(float) > 65536L)          // the dynamic LDS a launch may ask for
+        return fail(CMK_EINVAL, "spatial_attention: %sS = %ld needs %ld bytes of LDS, more than 65536", "", (long)S, 3L * S * S * (long)sizeof(float));
     hipLaunchKernelGGL(spatial_attention_kernel, dim3(R), dim3(256), (size_t)3 * S * S * sizeof(float), (hipStream_t)stream, x, w, counts,
                        topk, S, C);
     return check_launch("spatial_attention");
@@ -265,6 +275,7 @@ extern "C" int cmk_mask_predict(const float* deconv_out, const float* pw, const 
                                 int topk, int R, int S, int C, float* masks, float* mask_logits_opt, void* stream) {
     if (!deconv_out || !pw || !pb || !cls || !counts || !masks) return fail(CMK_EINVAL, "mask_predict: null pointer%s", "");
     if ((C & 3) || S < 1 || R < 1 || topk < 1 || R % topk) return fail(CMK_EINVAL, "mask_predict: bad shape%s", "");
+    if (R > 65535 || (long)S * S > 0x7fffffffL) return fail(CMK_EINVAL, "mask_predict: %s%ld RoIs x %ld pixels do not fit the grid", "", (long)R, (long)S * S);
     hipLaunchKernelGGL(mask_predict_kernel, dim3(S * S, R), dim3(256), 0, (hipStream_t)stream, deconv_out, pw, pb, cls, counts, topk, S, C,
                        masks, mask_logits_opt);
     return check_launch("mask_predict");
@@ -272,8 +283,9 @@ extern "C" int cmk_mask_predict(const float* deconv_out, const float* pw, const 
 
 extern "C" int cmk_mask_pool_concat(const float* masks, float* y, int y_cs, int y_co, int R, int S, void* stream) {
     if (!masks || !y) return fail(CMK_EINVAL, "mask_pool: null pointer%s", "");
-    if (R < 1 || S < 1 || y_co >= y_cs) return fail(CMK_EINVAL, "mask_pool: bad shape%s", "");
+    if (R < 1 || S < 1 || y_co < 0 || y_co >= y_cs) return fail(CMK_EINVAL, "mask_pool: bad shape%s", "");
     long total = (long)R * S * S;
+    if ((total + 255) / 256 > 0x7fffffffL) return fail(CMK_EINVAL, "mask_pool: %s%ld outputs do not fit the grid", "", total);
     int grid = (int)((total + 255) / 256);
     hipLaunchKernelGGL(mask_pool_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, masks, y, y_cs, y_co, R, S, y_cs - y_co);
     return check_launch("mask_pool");
@@ -282,6 +294,7 @@ extern "C" int cmk_mask_pool_concat(const float* masks, float* y, int y_cs, int 
 extern "C" int cmk_mask_iou_score(const float* iou, int iou_cs, const float* scores, const int64_t* cls, float* mask_scores, int R,
                                   void* stream) {
     if (!iou || !scores || !cls || !mask_scores) return fail(CMK_EINVAL, "mask_iou_score: null pointer%s", "");
+    if (R < 1 || iou_cs < 1) return fail(CMK_EINVAL, "mask_iou_score: %sR = %ld RoIs, iou_cs = %ld: need at least 1", "", (long)R, (long)iou_cs);
     hipLaunchKernelGGL(mask_iou_score_kernel, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, iou, iou_cs, scores, cls, mask_scores, R);
     return check_launch("mask_iou_score");
 }

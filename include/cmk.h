@@ -331,26 +331,32 @@ int cmk_roi_align_ratio(const float* const* feats /* host array of device pointe
 
 /* The general pooler (pooler.py:192-288): aligned = 1 ROIAlignV2 / 0 ROIAlign v1 (torchvision roi_align aligned flag, :243-255);
  * assign_by_area = 0 the "ratio" rule above / 1 FPN Eqn.(1): floor(canonical_level + log2(sqrt(area) / canonical_box_size + eps))
- * clamped to the levels (pooler.py:121-152; img_area may then be NULL). */
+ * clamped to the levels (pooler.py:121-152; img_area may then be NULL).
+ * CMK_EINVAL before any launch: num_levels outside [1, 4], a level with feat_h or feat_w < 1, C % 4, y_cs < C or y_cs % 4, N, topk or
+ * out_size < 1, canonical_box_size <= 0 under the area rule, or ceil(out_size^2 / 4) * (N*topk rounded up to 8) workgroups above 2^31 - 1. */
 int cmk_roi_align_pool(const float* const* feats, const int* feat_h, const int* feat_w, const float* scales, int num_levels, int min_level,
                        int C, const float* boxes, const int32_t* counts, const float* img_area, int N, int topk, int out_size,
                        int sampling_ratio, int aligned, int assign_by_area, float canonical_box_size, int canonical_level,
                        float* y, int y_cs, int32_t* out_level, void* stream);
 
-/* ---- SAG-Mask spatial attention (sam.py:23-28) in place ------------------------------------------------------- */
+/* ---- SAG-Mask spatial attention (sam.py:23-28) in place -------------------------------------------------------
+ * C % 4 == 0, S, R, topk >= 1, R % topk == 0, and 3*S*S*4 bytes of dynamic LDS at most 65536 (S <= 73): CMK_EINVAL otherwise. */
 int cmk_spatial_attention(float* x /* (R,S,S,C) */, const float* w /* [2][3][3] */, const int32_t* counts, int topk,
                           int R, int S, int C, void* stream);
 
 /* ---- mask predictor for the predicted class only + sigmoid (sam.py:83,97; mask_head.py:202-208) ---------------
- * deconv_out: (R, S, S, 4, C) = relu(deconv) laid out (dh,dw)-major; masks: (R, 2S, 2S).                     */
+ * deconv_out: (R, S, S, 4, C) = relu(deconv) laid out (dh,dw)-major; masks: (R, 2S, 2S).
+ * C % 4 == 0, S, topk >= 1, R in [1, 65535] (the grid's y dimension), R % topk == 0: CMK_EINVAL otherwise.   */
 int cmk_mask_predict(const float* deconv_out, const float* pw /* [classes][C] */, const float* pb,
                      const int64_t* cls, const int32_t* counts, int topk, int R, int S, int C,
                      float* masks, float* mask_logits_opt, void* stream);
 
-/* ---- maxpool 2x2 of the masks into channel `co` of the MaskIoU input (maskiou_head.py:108-112) ---------------- */
+/* ---- maxpool 2x2 of the masks into channel `co` of the MaskIoU input (maskiou_head.py:108-112) ----------------
+ * A NaN wins its window as in max_pool2d.  R, S >= 1 and 0 <= y_co < y_cs: CMK_EINVAL otherwise. */
 int cmk_mask_pool_concat(const float* masks /* (R,2S,2S) */, float* y, int y_cs, int y_co, int R, int S, void* stream);
 
-/* ---- mask_scores = scores * iou[cls] (maskiou_head.py:50-60) -------------------------------------------------- */
+/* ---- mask_scores = scores * iou[cls] (maskiou_head.py:50-60) --------------------------------------------------
+ * R >= 1 and iou_cs >= 1: CMK_EINVAL otherwise. */
 int cmk_mask_iou_score(const float* iou /* (R, classes_stride) */, int iou_cs, const float* scores, const int64_t* cls,
                        float* mask_scores, int R, void* stream);
 
@@ -474,7 +480,8 @@ int cmk_vis_keypoints(uint8_t* image, int H, int W, const float* keypoints, cons
 
 /* ---- multi-GPU result exchange (the reference's analogue: comm.gather in evaluation/coco_evaluation.py:155-156) ----------
  * One fixed-stride float record per image, written straight into the all-gather send buffer:
- * [box 4K | score K | mask_score K | loc 2K | class K (as float) | mask K*hw*hw | count], K*(9 + hw*hw) + 1 floats. */
+ * [box 4K | score K | mask_score K | loc 2K | class K (as float) | mask K*hw*hw | count], K*(9 + hw*hw) + 1 floats.
+ * N in [1, 65535] (the grid's y dimension), K, hw >= 1 and a record width that fits an int: CMK_EINVAL otherwise. */
 int cmk_pack_records(const float* box, const float* score, const float* mask_scores, const float* loc, const int64_t* cls,
                      const float* masks, const int32_t* counts, int N, int K, int mask_hw, float* rec /* N * width */, void* stream);
 
