@@ -1,7 +1,7 @@
 """centermask2_amd — MI355X-native CenterMask2 inference hot path (VoVNetV2-FPN, FCOS, CenterROIHeads)."""
 __version__ = "0.1.0"
 
-__all__ = ["Predictor", "load_weights", "Visualizer", "draw_instance_predictions", "__version__"]
+__all__ = ["Predictor", "load_weights", "GeneralizedRCNNWithTTA", "Visualizer", "draw_instance_predictions", "__version__"]
 
 
 def __getattr__(name):
@@ -9,6 +9,9 @@ def __getattr__(name):
     if name in ("Predictor", "load_weights"):
         from . import predictor
         return getattr(predictor, name)
+    if name == "GeneralizedRCNNWithTTA":
+        from .modeling import test_time_augmentation
+        return test_time_augmentation.GeneralizedRCNNWithTTA
     if name in ("Visualizer", "draw_instance_predictions"):
         from . import visualize
         return getattr(visualize, name)

@@ -48,7 +48,8 @@ _TABLE = dict(
     INPUT=dict(MIN_SIZE_TRAIN=(800,), MIN_SIZE_TEST=800, MAX_SIZE_TEST=1333, FORMAT="BGR"),
     DATASETS=dict(TRAIN=(), TEST=()),
     DATALOADER=dict(NUM_WORKERS=4),
-    TEST=dict(DETECTIONS_PER_IMAGE=100, KEYPOINT_OKS_SIGMAS=[]),
+    TEST=dict(DETECTIONS_PER_IMAGE=100, KEYPOINT_OKS_SIGMAS=[],
+              AUG=dict(ENABLED=False, MIN_SIZES=(400, 500, 600, 700, 800, 900, 1000, 1100, 1200), MAX_SIZE=4000, FLIP=True)),
     SOLVER=dict(CHECKPOINT_PERIOD=5000, IMS_PER_BATCH=16, BASE_LR=0.001, STEPS=(30000,), MAX_ITER=40000),
 )
 

@@ -1318,6 +1318,122 @@ def resize_preprocess_images(images: Sequence[torch.Tensor], short: int, max_siz
     return out, sizes
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# test-time augmentation (modeling/test_time_augmentation.py): the mirrored front end, the box maps and the mask average
+# ---------------------------------------------------------------------------------------------------------------
+def resize_preprocess_augmented(image: torch.Tensor, shapes: Sequence[Tuple[int, int]], flips, mean, std, size_divisibility: int = 32,
+                                reverse_channels: bool = False) -> List[torch.Tensor]:
+    """One raw (h,w,3) uint8 image on the GPU -> one canvas per entry of `shapes` ((new_h, new_w), e.g. from resize_shortest_edge_shape):
+    (1 + flip, 3, H, W) float32 with the image resized to that shape in slot 0 — the bits resize_preprocess_images gives — and, where
+    flips (a bool, or one per shape) says so, the mirror of the RESIZED bytes in slot 1 (detectron2 applies [resize, flip]); zero
+    padding right/bottom in both.  The horizontal pass runs once per shape, the vertical pass once per slot."""
+    _need_u8_hwc(image, "resize_preprocess_augmented")
+    shapes = [(int(nh), int(nw)) for nh, nw in shapes]
+    if len(shapes) == 0 or any(nh < 1 or nw < 1 for nh, nw in shapes):
+        raise _lib.CmkError("resize_preprocess_augmented: need at least one positive (new_h, new_w), got {}".format(shapes))
+    flips = [bool(flips)] * len(shapes) if isinstance(flips, (bool, int)) else [bool(f) for f in flips]
+    if len(flips) != len(shapes):
+        raise _lib.CmkError("resize_preprocess_augmented: {} flip flags for {} shapes".format(len(flips), len(shapes)))
+    lib = _lib.load()
+    dev = image.device
+    image = image.contiguous()
+    h, w = int(image.shape[0]), int(image.shape[1])
+    d = max(1, size_divisibility)
+    need = max([h * nw * 3 for _, nw in shapes if nw != w] or [0])
+    ws = torch.empty((need + 3,), dtype=torch.uint8, device=dev) if need else None
+    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    out = []
+    for (new_h, new_w), flip in zip(shapes, flips):
+        H, W = (new_h + d - 1) // d * d, (new_w + d - 1) // d * d
+        canvas = torch.empty((2 if flip else 1, 3, H, W), dtype=torch.float32, device=dev)
+        mid = _resize_h(lib, image, new_w, ws)
+        by, ky, ksy, keep = _resize_v_args(h, new_h, dev)
+        check(lib.cmk_resize_v_preprocess(mid.data_ptr(), h, new_h, new_w, by, ky, ksy, canvas[0].data_ptr(), H, W, m3, s3,
+                                          int(bool(reverse_channels)), _stream()), "cmk_resize_v_preprocess")
+        if flip:
+            check(lib.cmk_resize_v_preprocess_hflip(mid.data_ptr(), h, new_h, new_w, by, ky, ksy, canvas[1].data_ptr(), H, W, m3, s3,
+                                                    int(bool(reverse_channels)), _stream()), "cmk_resize_v_preprocess_hflip")
+        del keep
+        out.append(canvas)
+    return out
+
+
+def tta_table(augs, h: int, w: int, to_image: bool, device) -> torch.Tensor:
+    """The (A,5) float32 table of the box maps for augmentations [(new_h, new_w, flip)] of an h x w image: (new_w, new_h, rx, ry, flip)
+    with rx, ry = w / new_w, h / new_h (to_image) or their inverses, each computed in double and rounded once to fp32."""
+    import numpy as np
+    rows = [(nw, nh, np.float32(w / nw if to_image else nw / w), np.float32(h / nh if to_image else nh / h), 1.0 if flip else 0.0)
+            for nh, nw, flip in augs]
+    return torch.tensor(np.asarray(rows, dtype=np.float32)).to(device)
+
+
+def _need_tta(t, dtype, shape, what: str) -> None:
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.CmkError("{}: need a contiguous {} tensor of shape {}, got {}".format(
+            what, dtype, tuple(shape), "{} {}".format(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+    if not t.is_cuda:
+        raise _lib.CmkError("{}: tensor is on {}; the CenterMask2 HIP path needs a GPU (no CPU fallback)".format(what, t.device))
+    _need_current_device(t, what)
+
+
+def tta_boxes_to_image(det: dict, table: torch.Tensor, height: int, width: int) -> dict:
+    """det: the padded detections of A augmentations (box (A,K,4), score (A,K), cls (A,K) int64, loc (A,K,2), counts (A) int32) and the
+    to_image table -> one ops.nms_topk candidate set (1, A*K, ..) in the frame of the height x width image: flipped back, scaled,
+    clipped; compacted in augmentation order, counts = [the sum]."""
+    lib = _lib.load()
+    a, k = int(det["score"].shape[0]), int(det["score"].shape[1])
+    dev = det["score"].device
+    for name, dt, shp in (("box", torch.float32, (a, k, 4)), ("score", torch.float32, (a, k)), ("cls", torch.int64, (a, k)),
+                          ("loc", torch.float32, (a, k, 2)), ("counts", torch.int32, (a,))):
+        _need_tta(det[name], dt, shp, "tta_boxes_to_image " + name)
+    _need_tta(table, torch.float32, (a, 5), "tta_boxes_to_image table")
+    cap = a * k
+    cand = dict(box=torch.empty((1, cap, 4), dtype=torch.float32, device=dev), score=torch.empty((1, cap), dtype=torch.float32, device=dev),
+                cls=torch.empty((1, cap), dtype=torch.int32, device=dev), loc=torch.empty((1, cap, 2), dtype=torch.float32, device=dev),
+                counts=torch.empty((1,), dtype=torch.int32, device=dev), cap=cap)
+    check(lib.cmk_tta_boxes_to_image(det["box"].data_ptr(), det["score"].data_ptr(), det["cls"].data_ptr(), det["loc"].data_ptr(),
+                                     det["counts"].data_ptr(), table.data_ptr(), a, k, int(width), int(height), cand["box"].data_ptr(),
+                                     cand["score"].data_ptr(), cand["cls"].data_ptr(), cand["loc"].data_ptr(), cand["counts"].data_ptr(),
+                                     _stream()), "cmk_tta_boxes_to_image")
+    return cand
+
+
+def tta_boxes_to_aug(box: torch.Tensor, count: torch.Tensor, table: torch.Tensor):
+    """Merged boxes (K,4) in the image frame, count (1) int32 and the to_aug table (A,5) -> (boxes (A,K,4) in every augmentation's frame
+    with zero rows at and beyond the count, counts (A) int32)."""
+    lib = _lib.load()
+    k, a = int(box.shape[0]), int(table.shape[0])
+    _need_tta(box, torch.float32, (k, 4), "tta_boxes_to_aug box")
+    _need_tta(count, torch.int32, (1,), "tta_boxes_to_aug count")
+    _need_tta(table, torch.float32, (a, 5), "tta_boxes_to_aug table")
+    out = torch.empty((a, k, 4), dtype=torch.float32, device=box.device)
+    counts = torch.empty((a,), dtype=torch.int32, device=box.device)
+    check(lib.cmk_tta_boxes_to_aug(box.data_ptr(), count.data_ptr(), table.data_ptr(), a, k, out.data_ptr(), counts.data_ptr(), _stream()),
+          "cmk_tta_boxes_to_aug")
+    return out, counts
+
+
+def tta_reduce_masks(masks: torch.Tensor, flips: torch.Tensor, mask_scores: Optional[torch.Tensor], count: torch.Tensor):
+    """masks (A,K,S,S) soft masks, flips (A) int32, mask_scores (A,K) or None, count (1) int32 -> (masks (K,S,S), mask_scores (K) or
+    None): the mean over the augmentations with the flipped ones mirrored along x, summed in augmentation order from 0 and divided once
+    by float(A); zero rows at and beyond the count."""
+    lib = _lib.load()
+    if not torch.is_tensor(masks) or masks.dim() != 4 or masks.shape[2] != masks.shape[3]:
+        raise _lib.CmkError("tta_reduce_masks: need (A,K,S,S) masks")
+    a, k, s = int(masks.shape[0]), int(masks.shape[1]), int(masks.shape[2])
+    _need_tta(masks, torch.float32, (a, k, s, s), "tta_reduce_masks masks")
+    _need_tta(flips, torch.int32, (a,), "tta_reduce_masks flips")
+    _need_tta(count, torch.int32, (1,), "tta_reduce_masks count")
+    if mask_scores is not None:
+        _need_tta(mask_scores, torch.float32, (a, k), "tta_reduce_masks mask_scores")
+    out = torch.empty((k, s, s), dtype=torch.float32, device=masks.device)
+    out_ms = torch.empty((k,), dtype=torch.float32, device=masks.device) if mask_scores is not None else None
+    check(lib.cmk_tta_reduce_masks(masks.data_ptr(), flips.data_ptr(), mask_scores.data_ptr() if mask_scores is not None else None,
+                                   count.data_ptr(), a, k, s, out.data_ptr(), out_ms.data_ptr() if out_ms is not None else None, _stream()),
+          "cmk_tta_reduce_masks")
+    return out, out_ms
+
+
 def paste_masks(masks: torch.Tensor, boxes: torch.Tensor, height: int, width: int, threshold: float = 0.5) -> torch.Tensor:
     """(R,S,S) float masks + (R,4) boxes -> (R,height,width) bool bitmasks."""
     lib = _lib.load()

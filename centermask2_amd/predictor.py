@@ -43,6 +43,10 @@ class Predictor:
         self.input_format = cfg.INPUT.FORMAT
         if self.input_format not in ("BGR", "RGB"):
             raise _lib.CmkError("Predictor: INPUT.FORMAT must be BGR or RGB, got {!r}".format(self.input_format))
+        self.tta = None                         # cfg.TEST.AUG: multi-scale + flip inference, merged on the device
+        if cfg.TEST.AUG.ENABLED:
+            from .modeling.test_time_augmentation import GeneralizedRCNNWithTTA
+            self.tta = GeneralizedRCNNWithTTA(cfg, self.model)
 
     def _upload(self, image) -> torch.Tensor:
         if not torch.is_tensor(image):
@@ -59,6 +63,9 @@ class Predictor:
     def predict_batch(self, images: Sequence) -> List[Dict[str, Instances]]:
         """One model call over raw BGR images that may differ in size; results at each image's own resolution."""
         raw = [self._upload(im) for im in images]
+        if self.tta is not None:
+            return [{"instances": self.tta.inference_one_image(im, int(im.shape[0]), int(im.shape[1]),
+                                                               reverse_channels=self.input_format == "RGB")} for im in raw]
         model = self.model
         batch, sizes = ops.resize_preprocess_images(raw, self.min_size, self.max_size, model.pixel_mean.flatten().tolist(),
                                                     model.pixel_std.flatten().tolist(), model.backbone.size_divisibility,

@@ -404,6 +404,37 @@ int cmk_resize_v_u8(const uint8_t* src, int h, int new_h, int new_w, const int32
 int cmk_resize_v_preprocess(const uint8_t* src, int h, int new_h, int new_w, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y,
                             float* dst, int H, int W, const float* mean3, const float* std3, int reverse_channels, void* stream);
 
+/* ---- test-time augmentation (detectron2 GeneralizedRCNNWithTTA, modeling/test_time_augmentation.py): the geometry of the input
+ * pipeline, mirrored, and its inverses.  An augmentation a is (new_w, new_h, flip): the image resized to new_h x new_w and, with flip,
+ * the resized bytes mirrored along x (d2 applies [resize, flip]).
+ *   cmk_resize_v_preprocess_hflip   cmk_resize_v_preprocess writing column new_w - 1 - x: the mirrored image in its zero-padded slot, the
+ *                                   padding still on the right and bottom; every pixel has the bits the plain entry gives it.
+ * The box maps take a per-augmentation table in DEVICE memory, 5 floats each: (new_w, new_h, rx, ry, flip != 0).  The ratios are
+ * computed in double on the host and rounded once to fp32; every step is one fp32 operation, nothing is fused.
+ *   cmk_tta_boxes_to_image   the detections of all augmentations -> one cmk_nms_topk candidate set of capacity A*K in the image frame
+ *                            (rx = w / new_w, ry = h / new_h).  det_* are the padded (A,K,..) outputs of cmk_nms_topk, det_counts (A)
+ *                            clamped to [0, K].  Per valid detection: with flip x0' = new_w - x1, x1' = new_w - x0; then x * rx, y * ry;
+ *                            then clipped to [0,img_w] x [0,img_h] (d2 Boxes.clip).  loc is mapped as a point by the same rule, without
+ *                            the clip; score is copied, cls narrowed to int32.  Candidates are written compacted in augmentation order
+ *                            and in the detector's order within an augmentation; cand_count[0] = sum of the clamped counts.
+ *   cmk_tta_boxes_to_aug     the inverse for the mask pass (rx = new_w / w, ry = new_h / h): box (K,4) in the image frame, count[0]
+ *                            clamped to [0, K] -> out_box (A,K,4): x * rx, y * ry, then with flip x0' = new_w - x1, x1' = new_w - x0; rows
+ *                            at and beyond the count are zeros; out_counts[a] = the clamped count for every a.
+ *   cmk_tta_reduce_masks     masks (A,K,S,S) soft masks, flips (A) int32, mask_scores (A,K), count[0] clamped to [0, K] ->
+ *                            out_masks[k] = (sum_a m_a[k]) / A with the masks of flipped augmentations mirrored along x, out_scores[k]
+ *                            likewise: fp32, added in augmentation order starting from 0, one division by (float)A; rows at and beyond
+ *                            the count are zeros.  mask_scores and out_scores may both be NULL (MASKIOU_ON off).
+ * Refused: null pointers, A < 1 or A > 4096, K < 1 or K > 65535, S < 1 or S > 1024, img_w / img_h not in [1, 65535]. -------------- */
+int cmk_resize_v_preprocess_hflip(const uint8_t* src, int h, int new_h, int new_w, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y,
+                                  float* dst, int H, int W, const float* mean3, const float* std3, int reverse_channels, void* stream);
+int cmk_tta_boxes_to_image(const float* det_box, const float* det_score, const int64_t* det_cls, const float* det_loc,
+                           const int32_t* det_counts, const float* table, int A, int K, int img_w, int img_h, float* cand_box,
+                           float* cand_score, int32_t* cand_cls, float* cand_loc, int32_t* cand_count, void* stream);
+int cmk_tta_boxes_to_aug(const float* box, const int32_t* count, const float* table, int A, int K, float* out_box, int32_t* out_counts,
+                         void* stream);
+int cmk_tta_reduce_masks(const float* masks, const int32_t* flips, const float* mask_scores, const int32_t* count, int A, int K, int S,
+                         float* out_masks, float* out_scores, void* stream);
+
 /* ---- output side: paste (R,S,S) soft masks into (R,H,W) uint8 bitmasks at `threshold` (deploy_utils.py:151-156 ->
  * d2 ROIMasks.to_bitmasks: bilinear grid_sample, align_corners=False, zero padding); boxes (R,4) are the rescaled and
  * clipped output boxes. ------------------------------------------------------------------------------------------------ */
