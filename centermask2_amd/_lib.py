@@ -115,6 +115,8 @@ SIGNATURES = {
     "cmk_mask_pack_bits": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cmk_rle_decode_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cmk_mask_intersections": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cmk_mask_boundary_bits": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cmk_mask_unpack_bits": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cmk_vis_record_ints": (c_int, []),
     "cmk_vis_prepare": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p]),

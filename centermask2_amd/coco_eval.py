@@ -9,6 +9,9 @@ evaluation.average_precision where the two protocols coincide, and the rasterise
 The IoU of masks is formed here from integer counts (pixels in both, pixels in each); where those counts come from is the caller's
 business: ops.mask_intersections for bitmasks on a GPU, intersections_host for bitmasks on the host.  Nothing here touches a bitmap
 after the counts exist.
+
+iouType "boundary" (Boundary AP; Cheng et al., "Boundary IoU", CVPR 2021) is the same protocol with IoU = min(mask IoU, IoU of the mask
+boundaries).  boundary_host restates the rule from the publication and is unpinned against the real boundary-iou-api in the same way.
 """
 from typing import Dict, List, Optional, Sequence
 
@@ -139,6 +142,62 @@ def intersections_host(det_masks: np.ndarray, gt_counts: Sequence[Sequence[int]]
     det_areas = _POP8[dp].sum(axis=1, dtype=np.int64).astype(np.int32)
     gt_areas = np.array([int(_POP8[g].sum(dtype=np.int64)) for g in gp], dtype=np.int32)
     return inter, det_areas, gt_areas
+
+
+def boundary_dilation(h: int, w: int, ratio: float = 0.02) -> int:
+    """The erosion distance of Boundary IoU for an (h,w) image: ratio times the diagonal, rounded with Python's round, at least 1."""
+    return max(1, int(round(float(ratio) * float(np.sqrt(int(h) * int(h) + int(w) * int(w))))))
+
+
+def _all_set_in_window(a: np.ndarray, d: int, axis: int) -> np.ndarray:
+    """out[i] = every element of a[i-d .. i+d] along `axis` is set and inside the array."""
+    n, k = a.shape[axis], 2 * d + 1
+    out = np.zeros(a.shape, dtype=bool)
+    if k > n:
+        return out
+    a = np.moveaxis(a, axis, -1)
+    c = np.concatenate([np.zeros(a.shape[:-1] + (1,), dtype=np.int32), np.cumsum(a, axis=-1, dtype=np.int32)], axis=-1)
+    np.moveaxis(out, axis, -1)[..., d:n - d] = (c[..., k:] - c[..., :-k]) == k
+    return out
+
+
+def boundary_host(masks_np: np.ndarray, d: int) -> np.ndarray:
+    """(R,h,w) 0/1 -> (R,h,w) bool, the boundary of Boundary IoU (Cheng et al., CVPR 2021): mask AND NOT eroded, where eroded is the
+    mask zero-padded by one pixel and eroded d times with a 3x3 all-ones element, which is: every pixel of the (2d+1)x(2d+1) square
+    around the pixel lies inside the image and is set.  The square is separable: a window of 2d+1 along x, then along y, each by one
+    running sum.  The host path of ops.mask_boundary_bits, on the same bits."""
+    m = np.asarray(masks_np).astype(bool)
+    if m.ndim != 3:
+        raise ValueError("boundary_host: expected (R,h,w) masks, got {}".format(m.shape))
+    d = int(d)
+    if d < 1:
+        raise ValueError("boundary_host: erosion distance {} must be at least 1".format(d))
+    if m.shape[0] == 0:
+        return m
+    return m & ~_all_set_in_window(_all_set_in_window(m, d, 2), d, 1)
+
+
+def _pair_counts(dp: np.ndarray, gp: List[np.ndarray]):
+    inter = np.zeros((dp.shape[0], len(gp)), dtype=np.int32)
+    for j, g in enumerate(gp):
+        inter[:, j] = _POP8[dp & g[None, :]].sum(axis=1, dtype=np.int64)
+    det_areas = _POP8[dp].sum(axis=1, dtype=np.int64).astype(np.int32)
+    gt_areas = np.array([int(_POP8[g].sum(dtype=np.int64)) for g in gp], dtype=np.int32)
+    return inter, det_areas, gt_areas
+
+
+def boundary_intersections_host(det_masks: np.ndarray, gt_counts: Sequence[Sequence[int]], h: int, w: int, d: int):
+    """The host path of ops.mask_boundary_intersections, on the same bits: the three arrays of intersections_host for the masks, then
+    the same three for their boundaries at erosion distance d."""
+    det = np.asarray(det_masks).astype(bool).reshape(len(det_masks), -1)
+    if det.shape[1] != h * w:
+        raise ValueError("detections of {} pixels against ground truth of {}x{}".format(det.shape[1], h, w))
+    det = det.reshape(-1, h, w)
+    gts = [counts_to_mask(c, h, w).astype(bool) for c in gt_counts]
+    out = _pair_counts(np.packbits(det.reshape(len(det), -1), axis=1), [np.packbits(g.reshape(-1)) for g in gts])
+    bd = boundary_host(det, d)
+    bg = boundary_host(np.stack(gts), d) if gts else np.zeros((0, h, w), dtype=bool)
+    return out + _pair_counts(np.packbits(bd.reshape(len(bd), -1), axis=1), [np.packbits(g.reshape(-1)) for g in bg])
 
 
 def mask_iou_from_counts(inter, det_areas, gt_areas, iscrowd) -> np.ndarray:
@@ -295,12 +354,16 @@ class GroundTruth:
         return self._counts[img_id]
 
 
-def score(gt: GroundTruth, results: List[Dict], iou_type: str, tables: Optional[Dict] = None, img_ids=None) -> Dict:
+def score(gt: GroundTruth, results: List[Dict], iou_type: str, tables: Optional[Dict] = None, img_ids=None,
+          btables: Optional[Dict] = None) -> Dict:
     """COCOeval for one iouType.  results: COCO result dicts with dataset category ids; for "segm" each carries `_k`, its row in its
     image's table, and tables[img_id] = (inter (n, m), det_areas (n,), gt_areas (m,)) with the columns in gt.anns[img_id] order.
+    "boundary" (Boundary AP) is "segm" with another IoU: btables[img_id] holds the same three arrays for the boundaries of the masks,
+    and the IoU is the smaller of the mask IoU and the boundary IoU, a crowd ground truth taking the crowd rule in both; areas and
+    everything else stay those of "segm".
     -> {"stats": the twelve numbers, "precision": ..., "recall": ...}."""
-    if iou_type not in ("bbox", "segm"):
-        raise ValueError("iouType {!r} is not built: only bbox and segm".format(iou_type))
+    if iou_type not in ("bbox", "segm", "boundary"):
+        raise ValueError("iouType {!r} is not built: only bbox, segm and boundary".format(iou_type))
     imgs = sorted(gt.images) if img_ids is None else sorted(set(img_ids))
     cat_index = {c: k for k, c in enumerate(gt.cat_ids)}
     by_img_cat: Dict = {}
@@ -332,6 +395,11 @@ def score(gt: GroundTruth, results: List[Dict], iou_type: str, tables: Optional[
                     d_area = [float(a_dt[k]) for k in rows]
                     ious = mask_iou_from_counts(inter[np.ix_(rows, g_idx)] if g_idx else np.zeros((len(rows), 0)),
                                                 [a_dt[k] for k in rows], [a_gt[j] for j in g_idx], crowd)
+                    if iou_type == "boundary":
+                        b_inter, b_dt, b_gt = btables[img]
+                        b_inter = np.asarray(b_inter).reshape(len(b_dt), len(b_gt))
+                        ious = np.minimum(ious, mask_iou_from_counts(b_inter[np.ix_(rows, g_idx)] if g_idx else np.zeros((len(rows), 0)),
+                                                                     [b_dt[k] for k in rows], [b_gt[j] for j in g_idx], crowd))
                 else:
                     d_area, ious = [], np.zeros((0, len(g)))
             scores = [float(d["score"]) for d in dts]

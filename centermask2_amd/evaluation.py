@@ -95,9 +95,15 @@ class COCOEvaluator:
     Instances on a GPU the table comes from ops.mask_intersections and the bitmasks are never downloaded; for CPU Instances from NumPy
     on the same bits — selected by where the input lies, as in wire.rle_encode_batch.  evaluate() touches no bitmap.
 
+    tasks: None means bbox, and segm when masks are present.  "boundary" is opt-in: Boundary AP (Cheng et al., CVPR 2021), COCOeval as
+    for segm with IoU = min(mask IoU, IoU of the mask boundaries at erosion distance round(boundary_dilation_ratio * image diagonal)).
+    process() then also keeps pred["boundary_table"], the same counts for the boundaries (ops.mask_boundary_intersections on the GPU,
+    coco_eval.boundary_intersections_host on the host).  The rule is restated from the publication in coco_eval.boundary_host and is
+    unpinned against the real boundary-iou-api, as the rest is against pycocotools.
+
     Not built, refused by name: tasks containing "keypoints" (OKS), and the proposals branch."""
 
-    def __init__(self, annotations, tasks=None, distributed: bool = False, output_dir=None):
+    def __init__(self, annotations, tasks=None, distributed: bool = False, output_dir=None, boundary_dilation_ratio: float = 0.02):
         import json
         from . import coco_eval
         if isinstance(annotations, (str, bytes)) or hasattr(annotations, "__fspath__"):
@@ -108,9 +114,11 @@ class COCOEvaluator:
             for t in tasks:
                 if t == "keypoints":
                     raise NotImplementedError('COCOEvaluator: task "keypoints" (OKS) is not built')
-                if t not in ("bbox", "segm"):
+                if t not in ("bbox", "segm", "boundary"):
                     raise ValueError("COCOEvaluator: unknown task {!r}".format(t))
         self._tasks = tasks
+        self._boundary = tasks is not None and "boundary" in tasks
+        self._boundary_ratio = float(boundary_dilation_ratio)
         self._distributed = distributed
         self._output_dir = output_dir
         self._gt = coco_eval.GroundTruth(annotations)
@@ -132,11 +140,18 @@ class COCOEvaluator:
             raise ValueError("COCOEvaluator: pred_masks of image {!r} are {}, the annotated size is {}x{}: post-process the instances to the "
                              "annotated size".format(img_id, "x".join(str(int(v)) for v in masks.shape[1:]), h, w))
         counts = self._gt.counts(img_id)
+        if self._boundary:                                      # both tables from one pass: (mask 3-tuple, boundary 3-tuple)
+            d = coco_eval.boundary_dilation(h, w, self._boundary_ratio)
+            if masks.is_cuda:
+                six = tuple(t.numpy() for t in ops.mask_boundary_intersections(masks, counts, h, w, d))
+            else:
+                six = coco_eval.boundary_intersections_host(masks.numpy(), counts, h, w, d)
+            return six[:3], six[3:]
         if masks.is_cuda:
             inter, a_dt, a_gt = (t.numpy() for t in ops.mask_intersections(masks, counts, h, w))
         else:
             inter, a_dt, a_gt = coco_eval.intersections_host(masks.numpy(), counts, h, w)
-        return inter, a_dt, a_gt
+        return (inter, a_dt, a_gt), None
 
     def process(self, inputs, outputs):
         from . import wire
@@ -148,7 +163,9 @@ class COCOEvaluator:
             inst, img_id = out["instances"], inp["image_id"]
             pred = {"image_id": img_id, "instances": wire.instances_to_coco_json(inst, img_id)}
             if self._do_evaluation and len(inst) and inst.has("pred_masks"):
-                pred["table"] = self._table(inst, img_id)
+                pred["table"], btable = self._table(inst, img_id)
+                if btable is not None:
+                    pred["boundary_table"] = btable
             self._predictions.append(pred)
 
     def _gathered(self):
@@ -170,10 +187,12 @@ class COCOEvaluator:
         if len(predictions) == 0:
             return {}
         num_classes = len(self._gt.cat_ids)
-        results, tables = [], {}
+        results, tables, btables = [], {}, {}
         for p in predictions:
             if "table" in p:
                 tables[p["image_id"]] = p["table"]
+            if "boundary_table" in p:
+                btables[p["image_id"]] = p["boundary_table"]
             for k, r in enumerate(p["instances"]):
                 c = r["category_id"]
                 if not 0 <= c < num_classes:
@@ -192,12 +211,13 @@ class COCOEvaluator:
             if not results:
                 out[task] = {n: float("nan") for n in names}
                 continue
-            if task == "segm":
-                missing = sorted(set(r["image_id"] for r in results) - set(tables))
+            if task in ("segm", "boundary"):
+                have = set(tables) if task == "segm" else set(tables) & set(btables)
+                missing = sorted(set(r["image_id"] for r in results) - have)
                 if missing:
                     raise ValueError("COCOEvaluator: no mask table for images {}: their instances had no pred_masks".format(missing[:5]))
-            rs = wire.segm_results_ranked_by_mask_score(results) if task == "segm" else results
-            acc = coco_eval.score(self._gt, rs, task, tables, img_ids)
+            rs = wire.segm_results_ranked_by_mask_score(results) if task in ("segm", "boundary") else results
+            acc = coco_eval.score(self._gt, rs, task, tables, img_ids, btables)
             res = {n: (float(v) * 100 if v >= 0 else float("nan")) for n, v in zip(coco_eval.STAT_NAMES, acc["stats"])}
             if num_classes > 1:
                 for k, name in enumerate(self.thing_classes):

@@ -1594,6 +1594,93 @@ def mask_intersections(det_masks: torch.Tensor, gt_counts, h: int, w: int):
     return host[:n * m].reshape(n, m), host[n * m:n * m + n], host[n * m + n:]
 
 
+def boundary_dilation(h: int, w: int, ratio: float = 0.02) -> int:
+    """The erosion distance of Boundary IoU (Cheng et al., CVPR 2021) for an (h,w) image, on the host:
+    max(1, int(round(ratio * sqrt(h*h + w*w)))) with Python's round."""
+    from . import coco_eval
+    return coco_eval.boundary_dilation(h, w, ratio)
+
+
+def _boundary_bits_into(words: torch.Tensor, h: int, w: int, dilation: int, bwords: torch.Tensor, bareas: torch.Tensor) -> None:
+    check(_lib.load().cmk_mask_boundary_bits(words.data_ptr(), int(words.shape[0]), int(h), int(w), int(dilation), bwords.data_ptr(),
+                                             bareas.data_ptr(), _stream()), "cmk_mask_boundary_bits")
+
+
+def _need_words(words, h: int, w: int, what: str) -> torch.Tensor:
+    if not torch.is_tensor(words) or not words.is_cuda:
+        raise _lib.CmkError("{}: words are on {}; the device path needs a GPU (no CPU fallback; coco_eval.boundary_host is the host "
+                            "path)".format(what, words.device if torch.is_tensor(words) else type(words).__name__))
+    if int(h) < 1 or int(w) < 1:
+        raise _lib.CmkError("{}: empty {}x{} masks".format(what, h, w))
+    if words.dtype != torch.int64 or words.dim() != 2 or words.shape[1] != mask_words(h, w):
+        raise _lib.CmkError("{}: expected (R, {}) int64 packed words of {}x{} masks, got {} {}".format(what, mask_words(h, w), h, w, words.dtype,
+                                                                                                   tuple(words.shape)))
+    _need_current_device(words, what)
+    return words.contiguous()
+
+
+def mask_boundary_bits(words: torch.Tensor, h: int, w: int, dilation: int):
+    """Packed masks (R, mask_words(h,w)) int64 on the GPU, as mask_pack_bits and mask_rle_decode(.., want_bitmasks=False) give them ->
+    (bwords, bareas) on the GPU in the same conventions: the packed boundary of each mask at erosion distance `dilation` (mask AND NOT
+    its (2d+1)x(2d+1) square erosion, outside the image background; include/cmk.h) and its set pixels.  No bitmap is touched."""
+    words = _need_words(words, h, w, "mask_boundary_bits")
+    bwords = torch.empty_like(words)
+    bareas = torch.empty((words.shape[0],), dtype=torch.int32, device=words.device)
+    if words.shape[0]:
+        _boundary_bits_into(words, h, w, dilation, bwords, bareas)
+    return bwords, bareas
+
+
+def mask_unpack_bits(words: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """The inverse of mask_pack_bits: (R, mask_words(h,w)) int64 on the GPU -> (R,h,w) bool."""
+    words = _need_words(words, h, w, "mask_unpack_bits")
+    r = int(words.shape[0])
+    out = torch.empty((r, int(h), int(w)), dtype=torch.uint8, device=words.device)
+    if r:
+        check(_lib.load().cmk_mask_unpack_bits(words.data_ptr(), r, int(h), int(w), out.data_ptr(), _stream()), "cmk_mask_unpack_bits")
+    return out.bool()
+
+
+def mask_boundary(masks: torch.Tensor, dilation: Optional[int] = None) -> torch.Tensor:
+    """(R,h,w) bool bitmasks on the GPU -> (R,h,w) bool, their boundaries: packed, eroded on the packed words and unpacked, all on the
+    device.  dilation defaults to boundary_dilation(h, w)."""
+    masks = _need_bitmasks(masks, "mask_boundary")
+    h, w = int(masks.shape[1]), int(masks.shape[2])
+    words, _ = mask_pack_bits(masks)
+    bwords, _ = mask_boundary_bits(words, h, w, boundary_dilation(h, w) if dilation is None else dilation)
+    return mask_unpack_bits(bwords, h, w)
+
+
+def mask_boundary_intersections(det_masks: torch.Tensor, gt_counts, h: int, w: int, dilation: int):
+    """mask_intersections and the same for the boundaries of the masks (Boundary IoU): -> (inter (N,M), det_areas (N,), gt_areas (M,),
+    inter_b (N,M), det_areas_b (N,), gt_areas_b (M,)), int32 CPU tensors.  The detections are packed and the ground truths decoded once,
+    both sets eroded on the packed words (cmk_mask_boundary_bits), the table kernel runs twice; one download of 2*(N*M + N + M) integers."""
+    det_masks = _need_bitmasks(det_masks, "mask_boundary_intersections")
+    n, m = int(det_masks.shape[0]), len(gt_counts)
+    if tuple(det_masks.shape[1:]) != (int(h), int(w)):
+        raise _lib.CmkError("mask_boundary_intersections: detections are {}x{}, the ground truth {}x{}".format(det_masks.shape[1], det_masks.shape[2],
+                                                                                                         h, w))
+    nw = mask_words(h, w)
+    dev = det_masks.device
+    one = n * m + n + m
+    out = torch.empty((2 * one,), dtype=torch.int32, device=dev)
+    words = torch.empty((2, n + m, nw), dtype=torch.int64, device=dev)           # the masks, then their boundaries
+    if n:
+        _pack_bits_into(det_masks, words[0, :n], out[n * m:n * m + n])
+    with torch.cuda.device(dev):
+        _rle_decode_pack(gt_counts, h, w, False, words[0, n:], out[n * m + n:one])
+    if n + m:
+        _boundary_bits_into(words[0], h, w, dilation, words[1], out[one + n * m:])
+    if n and m:
+        lib = _lib.load()
+        for k in (0, 1):
+            check(lib.cmk_mask_intersections(words[k].data_ptr(), n, words[k, n:].data_ptr(), m, int(h), int(w), out[k * one:].data_ptr(), _stream()),
+                  "cmk_mask_intersections")
+    host = out.cpu()                                                   # the one download
+    return tuple(host[k * one + a:k * one + b].reshape(shape) for k in (0, 1)
+                 for a, b, shape in ((0, n * m, (n, m)), (n * m, n * m + n, (n,)), (n * m + n, one, (m,))))
+
+
 # ---- visualizer (csrc/visualize.hip; the contract is in include/cmk.h and DESIGN §3 "Visualizer") ------------------------------------
 def vis_prepare(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, order: torch.Tensor, names: torch.Tensor,
                 name_lens: torch.Tensor, num_names: int, palette: torch.Tensor, h: int, w: int, font_scale: int, color_by_class: bool) -> torch.Tensor:

@@ -475,6 +475,19 @@ int cmk_rle_decode_pack(const int32_t* cum, const int64_t* off, int M, int H, in
 /* evaluation/coco_evaluation.py:543-591, the table: inter[n*M + m] = popcount(det[n] AND gt[m]) over packed det (N, words) and
  * gt (M, words).  Zeroes inter on the stream, then accumulates with integer atomics.  N == 0 or M == 0: CMK_OK, nothing written. */
 int cmk_mask_intersections(const uint64_t* det, int N, const uint64_t* gt, int M, int H, int W, int32_t* inter, void* stream);
+/* Boundary IoU (Cheng et al., CVPR 2021; iouType "boundary" of the published boundary evaluation API, restated in DESIGN §3 "COCO
+ * evaluation" and never run beside it): the boundary of a mask m is m AND NOT eroded, where eroded(y,x) = 1 iff every pixel of the
+ * (2d+1)x(2d+1) square centred on (y,x) lies inside the image and is set (the mask zero-padded by one pixel, eroded d times with a 3x3
+ * all-ones element).  words: R packed masks as the two producers above write them; bwords (R, ceil(H*W/64)) gets the packed boundary of
+ * each in the same layout, unused high bits zero, bareas[r] its set pixels.  Out of place: bwords must not overlap words.  No byte
+ * bitmap is read or written.  bwords and bareas are zeroed on the stream and filled with integer OR / add atomics (a 64-pixel word of the
+ * linear layout belongs to several rows or tiles).  With 2d+1 > min(H, W) no square fits, the erosion is empty and bwords is a copy of words, for any
+ * d >= 1.  Otherwise d is at most CMK_BOUNDARY_MAX_D at any W: the halo of 2d rows lies in 64 KiB of LDS.  Refused before any launch:
+ * the conditions above, d < 1, d > CMK_BOUNDARY_MAX_D where a square fits.  R == 0 is CMK_OK with no launch. */
+#define CMK_BOUNDARY_MAX_D 128
+int cmk_mask_boundary_bits(const uint64_t* words, int R, int H, int W, int d, uint64_t* bwords, int32_t* bareas, void* stream);
+/* The inverse of cmk_mask_pack_bits: packed words (R, ceil(H*W/64)) -> masks (R,H,W) bytes 0/1. */
+int cmk_mask_unpack_bits(const uint64_t* words, int R, int H, int W, uint8_t* masks, void* stream);
 
 /* ---- visualizer (visualizer.py:21-38 hands the post-processed Instances to detectron2's Visualizer.draw_instance_predictions, which
  * draws on the host with matplotlib; this picture is the package's own, in integer arithmetic: DESIGN §3 "Visualizer").  Images are

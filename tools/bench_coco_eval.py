@@ -20,6 +20,12 @@ Kernel times come from a run of their own, with no counters in it:
 
 The second command adds the mask IoU kernels' time per image to the json beside their memory bounds at the 6.3 TB/s an MI355X achieves
 from HBM: the pack kernel reads R*H*W bytes, the intersection kernel (N + M)*H*W/8 bytes.
+
+The Boundary AP leg is a run of its own (boundary_leg below; written to the key "boundary" of --out, the rest of the file kept):
+
+    python tools/bench_coco_eval.py --boundary [--rounds 10] [--host-rounds 3] [--out profiles/bench_coco_eval.json]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o bnd -- python tools/bench_coco_eval.py --boundary --trace-body
+    python tools/bench_coco_eval.py --boundary --kernel-stats DIR/.../bnd_kernel_stats.csv --out profiles/bench_coco_eval.json
 """
 import argparse
 import csv
@@ -117,14 +123,108 @@ def kernel_stats(path):
             "intersections_share_of_memory_bound": round(inter_bound / us["mask_inter_kernel"], 3)}
 
 
+def boundary_leg(a, dev):
+    """--boundary: what the task "boundary" (Boundary AP) adds to process() at the same shape, erosion distance 30.  Three timings in
+    alternating rounds after a warm-up of all: process() on GPU Instances without and with the task, and with it on the CPU copies (fewer
+    rounds: a host round takes seconds).  Both tables of the two paths are asserted equal first.  The entry cmk_mask_boundary_bits on the
+    60 packed masks of one image is timed on its own with device events (the zeroing of words and areas and the boundary kernel together)
+    beside the memory floor of the boundary kernel: the words read once and written once."""
+    ds, gpu_images = workload(dev)
+    torch.cuda.synchronize()
+    plain, with_b = COCOEvaluator(ds), COCOEvaluator(ds, tasks=("bbox", "segm", "boundary"))
+    d = ops.boundary_dilation(H, W)
+    cpu_images = [(img, inst.to("cpu")) for img, inst in gpu_images]
+    _round(plain, gpu_images)
+    _round(with_b, gpu_images)
+    on_gpu = [p["table"] + p["boundary_table"] for p in with_b._predictions]
+    _round(with_b, cpu_images)
+    on_cpu = [p["table"] + p["boundary_table"] for p in with_b._predictions]
+    for ta, tb in zip(on_gpu, on_cpu):
+        assert len(ta) == 6 and all(np.array_equal(x, y) for x, y in zip(ta, tb)), "mask or boundary tables of the two paths differ"
+    t_plain, t_b, t_host = [], [], []
+    for k in range(a.rounds):
+        t_plain.append(_round(plain, gpu_images))
+        t_b.append(_round(with_b, gpu_images))
+        if k < a.host_rounds:
+            t_host.append(_round(with_b, cpu_images))
+    # the entry alone, on the packed masks of one image
+    inst = gpu_images[0][1]
+    words = torch.cat([ops.mask_pack_bits(inst.pred_masks)[0], ops.mask_rle_decode(with_b._gt.counts(gpu_images[0][0]), H, W, want_bitmasks=False)[0]])
+    for _ in range(5):
+        ops.mask_boundary_bits(words, H, W, d)
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(max(a.rounds, 20)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ops.mask_boundary_bits(words, H, W, d)
+        e1.record()
+        e1.synchronize()
+        us.append(e0.elapsed_time(e1) * 1e3)
+    floor_us = 2 * words.numel() * 8 / HBM_BYTES_PER_S * 1e6
+    return {
+        "workload": "{} images x {} detections against {} ground truths of {}x{}, erosion distance {}".format(B, TOPK, NGT, H, W, d),
+        "tables_equal": True,
+        "device_ms_per_image_without_boundary": _spread(t_plain),
+        "device_ms_per_image_with_boundary": _spread(t_b),
+        "host_ms_per_image_with_boundary": _spread(t_host),
+        "host_over_device_median": round(statistics.median(t_host) / statistics.median(t_b), 2),
+        "boundary_entry_us": {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2), "calls": len(us),
+                              "masks": int(words.shape[0]),
+                              "what": "cmk_mask_boundary_bits between two device events: zeroing of words and areas, mask_boundary_kernel"},
+        "boundary_memory_floor_us": round(floor_us, 2),
+        "boundary_memory_floor": "2 * R * ceil(H*W/64) * 8 bytes (words read once, written once) at 6.3 TB/s",
+        "boundary_entry_share_of_memory_floor": round(floor_us / statistics.median(us), 3),
+        "timing": "host clock around each round of {} process() calls, the three alternating, {} device and {} host rounds after a warm-up "
+                  "of all".format(B, a.rounds, len(t_host)),
+        "device": torch.cuda.get_device_name(0),
+    }
+
+
+BOUNDARY_TRACE_CALLS = 20
+
+
+def boundary_trace_body(dev):
+    """--boundary --trace-body: the entry alone on the 60 packed masks of the first image, for rocprofv3 --kernel-trace."""
+    ds, gpu_images = workload(dev)
+    img, inst = gpu_images[0]
+    gt = COCOEvaluator(ds)._gt.counts(img)
+    words = torch.cat([ops.mask_pack_bits(inst.pred_masks)[0], ops.mask_rle_decode(gt, H, W, want_bitmasks=False)[0]])
+    for _ in range(BOUNDARY_TRACE_CALLS):
+        ops.mask_boundary_bits(words, H, W, ops.boundary_dilation(H, W))
+    torch.cuda.synchronize()
+
+
+def boundary_kernel_stats(path):
+    """kernel_stats.csv of a --boundary --trace-body run -> the boundary kernel's time per call beside its memory floor."""
+    rows = {r["Name"]: r for r in csv.DictReader(open(path))}
+    name = [n for n in rows if "mask_boundary_kernel" in n]
+    if not name or int(rows[name[0]]["Calls"]) != BOUNDARY_TRACE_CALLS:
+        raise SystemExit("{}: not the {} mask_boundary_kernel launches of a --boundary --trace-body run".format(path, BOUNDARY_TRACE_CALLS))
+    us = float(rows[name[0]]["TotalDurationNs"]) / 1e3 / BOUNDARY_TRACE_CALLS
+    floor_us = 2 * (TOPK + NGT) * ((H * W + 63) // 64) * 8 / HBM_BYTES_PER_S * 1e6
+    return {"source": "rocprofv3 --kernel-trace --stats, {} calls of the entry on {} masks".format(BOUNDARY_TRACE_CALLS, TOPK + NGT),
+            "mask_boundary_kernel_us": round(us, 2), "memory_floor_us": round(floor_us, 2),
+            "share_of_memory_floor": round(floor_us / us, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--boundary", action="store_true", help="the Boundary AP leg; written to the key \"boundary\" of --out")
+    ap.add_argument("--host-rounds", type=int, default=3, help="--boundary: rounds of the host path")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-body", action="store_true", help="only run the device path a few times (for rocprofv3 --kernel-trace)")
     ap.add_argument("--kernel-stats", default=None, help="kernel_stats.csv of a --trace-body run; merged into --out")
     a = ap.parse_args()
 
+    if a.kernel_stats and a.boundary:
+        res = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}
+        res.setdefault("boundary", {})["kernel"] = boundary_kernel_stats(a.kernel_stats)
+        print(json.dumps(res["boundary"]["kernel"]))
+        if a.out:
+            json.dump(res, open(a.out, "w"), indent=1)
+        return
     if a.kernel_stats:
         res = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}
         res["kernels"] = kernel_stats(a.kernel_stats)
@@ -138,6 +238,21 @@ def main():
     if a.rounds < 10 and not a.trace_body:
         raise SystemExit("at least 10 rounds of each path")
     dev = torch.device("cuda:0")
+    if a.boundary and a.trace_body:
+        boundary_trace_body(dev)
+        return
+    if a.boundary:
+        if a.host_rounds < 3:
+            raise SystemExit("at least 3 rounds of the host path")
+        res = boundary_leg(a, dev)
+        print(json.dumps(res))
+        if a.out:
+            old = json.load(open(a.out)) if os.path.exists(a.out) else {}
+            if "kernel" in old.get("boundary", {}):
+                res["kernel"] = old["boundary"]["kernel"]
+            old["boundary"] = res
+            json.dump(old, open(a.out, "w"), indent=1)
+        return
     ds, gpu_images = workload(dev)
     torch.cuda.synchronize()
     ev = COCOEvaluator(ds)
