@@ -43,7 +43,7 @@ def boxes_to_image(box, score, cls, loc, counts, augs, h, w):
         if aug[2]:
             x0, x1 = _flip_x(aug[1], x0, x1)
             lx = F(aug[1]) - lx
-        clip = lambda v, hi: np.minimum(np.maximum(v, F(0)), F(hi))
+        clip = lambda v, hi: np.fmin(np.fmax(v, F(0)), F(hi))          # fminf / fmaxf: a NaN coordinate clips to a bound
         ob.append(np.stack([clip(x0 * rx, w), clip(y0 * ry, h), clip(x1 * rx, w), clip(y1 * ry, h)], axis=1).astype(F))
         ol.append(np.stack([lx * rx, ly * ry], axis=1).astype(F))
         os_.append(score[a, :n])
