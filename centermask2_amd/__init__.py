@@ -1,7 +1,8 @@
 """centermask2_amd — MI355X-native CenterMask2 inference hot path (VoVNetV2-FPN, FCOS, CenterROIHeads)."""
 __version__ = "0.1.0"
 
-__all__ = ["Predictor", "load_weights", "GeneralizedRCNNWithTTA", "Visualizer", "draw_instance_predictions", "__version__"]
+__all__ = ["Predictor", "load_weights", "GeneralizedRCNNWithTTA", "Visualizer", "draw_instance_predictions", "InstanceTracker",
+           "VideoVisualizer", "__version__"]
 
 
 def __getattr__(name):
@@ -15,4 +16,7 @@ def __getattr__(name):
     if name in ("Visualizer", "draw_instance_predictions"):
         from . import visualize
         return getattr(visualize, name)
+    if name in ("InstanceTracker", "VideoVisualizer"):
+        from . import video
+        return getattr(video, name)
     raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))

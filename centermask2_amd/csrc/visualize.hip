@@ -18,6 +18,14 @@
 //                                     into the winner map over the primitive's own bounding box;
 //              vis_kp_colour_kernel — one pass over the winner map colours the pixels some primitive won.  The latest primitive wins a
 //                                     pixel whatever the order of the atomics.
+//   video    : vis_track_iou_kernel    — box mode: one thread per (old row, new instance), the float64 IoU table;
+//              vis_track_assign_kernel — ONE workgroup of 16 waves matches a frame's instances to the track table (DESIGN §3 "Video"):
+//                                        a wave per old row finds the first maximum of its row, candidates claim their instance with an
+//                                        integer atomicMin in LDS (the smallest old index wins whatever the order), two ballot scans
+//                                        number the unmatched instances (new ids) and the surviving missed rows (slots of the next table);
+//              vis_track_gather_kernel — mask mode: the packed words and areas of the next table, row by row from the new instances or
+//                                        the old table, into the other half of the ping-pong pair.
+//              The counters (n_tracks, next_id, dropped) stay on the device; nothing is read back.
 // Every store is an ordinary vector store, the atomics are vector atomics.
 #include "cmk_common.hpp"
 
@@ -54,7 +62,8 @@ __device__ inline void vis_put_decimal(uint8_t* g, int& len, unsigned long long 
 __global__ __launch_bounds__(64) void vis_prepare_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, const long long* __restrict__ classes,
                                                         const long long* __restrict__ order, const uint8_t* __restrict__ names,
                                                         const int32_t* __restrict__ name_lens, int num_names, const uint8_t* __restrict__ palette, int n,
-                                                        int H, int W, int scale, int by_class, int32_t* __restrict__ records) {
+                                                        int H, int W, int scale, int by_class, const int32_t* __restrict__ color_ids,
+                                                        int32_t* __restrict__ records) {
     const int j = blockIdx.x * 64 + threadIdx.x;
     if (j >= n) return;
     long long src = order[j];
@@ -62,7 +71,7 @@ __global__ __launch_bounds__(64) void vis_prepare_kernel(const float* __restrict
     int32_t* r = records + (long)j * VIS_REC;
     const long long cls = classes[src];
 
-    const long long k = by_class ? cls : src;
+    const long long k = color_ids ? (long long)color_ids[src] : (by_class ? cls : src);    // color_ids: the caller's colour index (track ids)
     const uint8_t* pal = palette + 3 * (int)(((k % 64) + 64) % 64);
     int col[3], edge[3], text[3];
 #pragma unroll
@@ -315,6 +324,169 @@ __global__ __launch_bounds__(256) void vis_kp_colour_kernel(uint8_t* __restrict_
     }
 }
 
+// ---- video: the track table ---------------------------------------------------------------------------------------------------------
+constexpr int VT_MAX = 1024;         // rows of a track table and new instances of a frame: one thread each in the assign workgroup
+constexpr int VT_NONE = 0x7fffffff;  // "no old row claims this instance"
+constexpr int VC_TRACKS = 0, VC_NEXT = 1, VC_DROPPED = 2;      // counters
+
+// pycocotools' box IoU on the corners, float64, every operation rounded on its own: the NumPy restatement does the same operations
+__device__ inline double vis_box_iou(const float* __restrict__ a, const float* __restrict__ b) {
+#pragma clang fp contract(off)
+    const double ax1 = a[0], ay1 = a[1], ax2 = a[2], ay2 = a[3], bx1 = b[0], by1 = b[1], bx2 = b[2], by2 = b[3];
+    if (ax1 != ax1 || ay1 != ay1 || ax2 != ax2 || ay2 != ay2 || bx1 != bx1 || by1 != by1 || bx2 != bx2 || by2 != by2) return 0.0;
+    const double iw = (ax2 < bx2 ? ax2 : bx2) - (ax1 > bx1 ? ax1 : bx1), ih = (ay2 < by2 ? ay2 : by2) - (ay1 > by1 ? ay1 : by1);
+    const double inter = (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
+    const double aa = (ax2 - ax1) * (ay2 - ay1), ab = (bx2 - bx1) * (by2 - by1);
+    const double u = aa + ab - inter;
+    if (!(u != 0.0)) return 0.0;                                     // a zero union, or a NaN one (inf - inf)
+    const double v = inter / u;
+    return v != v ? 0.0 : v;
+}
+
+// grid = ceil(rows * n / 256)
+__global__ __launch_bounds__(256) void vis_track_iou_kernel(const float* __restrict__ old_boxes, int rows, const float* __restrict__ new_boxes, int n,
+                                                           double* __restrict__ iou) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= rows * n) return;
+    const int i = k / n, j = k - i * n;
+    iou[k] = vis_box_iou(old_boxes + 4 * i, new_boxes + 4 * j);
+}
+
+// exclusive scan of one flag per thread over the 1024 threads of the assign workgroup; total: how many are set
+__device__ inline int vis_scan_flags(bool flag, int* wsum, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(flag);
+    __syncthreads();                                                 // the readers of the scan before this one are done with wsum
+    if (lane == 0) wsum[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < VT_MAX / 64; ++k) {
+        const int s = wsum[k];
+        before += k < wave ? s : 0;
+        total += s;
+    }
+    return before + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+// grid = 1.  Thread t is new instance t and old row t; wave w walks the old rows w, w + 16, ..
+__global__ __launch_bounds__(VT_MAX) void vis_track_assign_kernel(
+    const double* __restrict__ iou, const int32_t* __restrict__ inter, const int32_t* __restrict__ old_areas, const int32_t* __restrict__ new_areas, int rows,
+    const float* __restrict__ old_boxes, const long long* __restrict__ old_cls, const int32_t* __restrict__ old_ids, const int32_t* __restrict__ old_ttl,
+    const float* __restrict__ new_boxes, const long long* __restrict__ new_cls, int n, int cap, int ttl, double thr, float* __restrict__ out_boxes,
+    long long* __restrict__ out_cls, int32_t* __restrict__ out_ids, int32_t* __restrict__ out_ttl, int32_t* __restrict__ src,
+    int32_t* __restrict__ track_ids, int32_t* counters) {
+    __shared__ int claim[VT_MAX], best[VT_MAX], wsum[VT_MAX / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int T = min(max(counters[VC_TRACKS], 0), rows);            // rows at or beyond n_tracks are never read as tracks
+    const int next_id = counters[VC_NEXT], dropped = counters[VC_DROPPED];
+    claim[t] = VT_NONE;
+    best[t] = -1;
+    __syncthreads();
+
+    for (int i = wave; i < T; i += VT_MAX / 64) {
+        const long long ci = old_cls[i];
+        double bv = 0.0;
+        int bj = VT_NONE;                                            // lanes walk j upwards: a later equal value never replaces an earlier one
+        for (int j = lane; j < n; j += 64) {
+            double v = 0.0;
+            if (new_cls[j] == ci) {
+                if (iou) {
+                    v = iou[(long)i * n + j];
+                } else {
+                    const long long in = inter[(long)i * n + j], u = (long long)old_areas[i] + (long long)new_areas[j] - in;
+                    v = u != 0 ? (double)in / (double)u : 0.0;
+                }
+                if (v != v) v = 0.0;
+            }
+            if (bj == VT_NONE || v > bv) bv = v, bj = j;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {                           // first maximum of the row: the larger value, then the smaller j
+            const double ov = __shfl_xor(bv, o, 64);
+            const int oj = __shfl_xor(bj, o, 64);
+            if (oj != VT_NONE && (bj == VT_NONE || ov > bv || (ov == bv && oj < bj))) bv = ov, bj = oj;
+        }
+        if (lane == 0 && bj != VT_NONE && bv > thr) {
+            best[i] = bj;
+            atomicMin(&claim[bj], i);
+        }
+    }
+    __syncthreads();
+
+    // new instances: the claimed ones inherit, the others are numbered in order of j
+    const bool is_new = t < n;
+    const int owner = is_new ? claim[t] : VT_NONE;
+    const bool fresh = is_new && owner == VT_NONE;
+    int n_fresh;
+    const int rank = vis_scan_flags(fresh, wsum, n_fresh);
+    if (is_new) {
+        const int id = fresh ? next_id + rank : old_ids[owner];
+        track_ids[t] = id;
+        out_ids[t] = id, out_ttl[t] = ttl, out_cls[t] = new_cls[t], src[t] = t;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out_boxes[4 * t + c] = new_boxes[4 * t + c];
+    }
+
+    // old rows: a row that did not hand its id on ages, and survives behind the new instances while it has time to live and a slot
+    bool extra = false;
+    int left = 0;
+    if (t < T) {
+        const int b = best[t];
+        left = old_ttl[t] - 1;
+        extra = !(b >= 0 && claim[b] == t) && left > 0;
+    }
+    int n_extra;
+    const int slot = n + vis_scan_flags(extra, wsum, n_extra);
+    if (extra && slot < cap) {
+        out_ids[slot] = old_ids[t], out_ttl[slot] = left, out_cls[slot] = old_cls[t], src[slot] = n + t;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out_boxes[4 * slot + c] = old_boxes[4 * t + c];
+    }
+    if (t == 0) {                                                    // every thread read the counters before the first barrier
+        const int kept = min(n_extra, cap - n);
+        counters[VC_TRACKS] = n + kept;
+        counters[VC_NEXT] = next_id + n_fresh;
+        counters[VC_DROPPED] = dropped + (n_extra - kept);
+    }
+}
+
+// grid = (min(ceil(nw / 256), 256), rows): out row s from new instance src[s] or old row src[s] - n
+__global__ __launch_bounds__(256) void vis_track_gather_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ counters,
+                                                              const unsigned long long* __restrict__ old_words, const int32_t* __restrict__ old_areas,
+                                                              const unsigned long long* __restrict__ new_words, const int32_t* __restrict__ new_areas, int n,
+                                                              int cap, int nw, unsigned long long* __restrict__ out_words, int32_t* __restrict__ out_areas) {
+    const int s = blockIdx.y;
+    if (s >= min(counters[VC_TRACKS], cap)) return;
+    const int v = src[s];
+    const unsigned long long* from;
+    int area;
+    if (v >= 0 && v < n) {
+        from = new_words + (long)v * nw, area = new_areas[v];
+    } else if (v >= n && v - n < cap) {
+        from = old_words + (long)(v - n) * nw, area = old_areas[v - n];
+    } else {
+        return;                                                      // never read outside the tables, whatever src holds
+    }
+    unsigned long long* to = out_words + (long)s * nw;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nw; i += gridDim.x * 256) to[i] = from[i];
+    if (blockIdx.x == 0 && threadIdx.x == 0) out_areas[s] = area;
+}
+
+// shared argument check of the track entries
+inline int vis_track_check(const char* what, int n, int rows, int max_tracks) {
+    if (max_tracks < 1 || max_tracks > VT_MAX) return fail(CMK_EINVAL, "%s: max_tracks = %ld outside [1, 1024]", what, max_tracks);
+    if (n < 0 || n > max_tracks) return fail(CMK_EINVAL, "%s: %ld instances outside [0, max_tracks = %ld]", what, n, max_tracks);
+    if (rows < 0 || rows > max_tracks) return fail(CMK_EINVAL, "%s: %ld rows outside [0, max_tracks = %ld]", what, rows, max_tracks);
+    return CMK_OK;
+}
+
+inline bool vis_overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
+}
+
 // shared argument check; the messages name the entry
 inline int vis_check(const char* what, int H, int W, int n) {
     if (H < 1 || W < 1) return fail(CMK_EINVAL, "%s: H = %ld, W = %ld must be at least 1", what, H, W);
@@ -335,18 +507,85 @@ using namespace cmk;
 
 extern "C" int cmk_vis_record_ints(void) { return VIS_REC; }
 
+// cmk_vis_prepare (color_ids null) and cmk_vis_prepare_ids
+static int vis_prepare_launch(const char* what, const float* boxes, const float* scores, const int64_t* classes, const int64_t* order,
+                              const uint8_t* names, const int32_t* name_lens, int num_names, const uint8_t* palette, int n, int H, int W, int font_scale,
+                              int color_by_class, const int32_t* color_ids, int32_t* records, void* stream) {
+    if (int rc = vis_check(what, H, W, n)) return rc;
+    if (int rc = vis_check_width(what, "font_scale", font_scale)) return rc;
+    if (num_names < 0 || num_names > 65535) return fail(CMK_EINVAL, "%s: %ld names outside [0, 65535]", what, num_names);
+    if (n == 0) return CMK_OK;
+    if (!boxes || !scores || !classes || !order || !palette || !records || (num_names && (!names || !name_lens)))
+        return fail(CMK_EINVAL, "%s: null pointer", what);
+    hipLaunchKernelGGL(vis_prepare_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, boxes, scores, (const long long*)classes,
+                       (const long long*)order, names, name_lens, num_names, palette, n, H, W, font_scale, color_by_class ? 1 : 0, color_ids, records);
+    return check_launch(what);
+}
+
 extern "C" int cmk_vis_prepare(const float* boxes, const float* scores, const int64_t* classes, const int64_t* order, const uint8_t* names,
                                const int32_t* name_lens, int num_names, const uint8_t* palette, int n, int H, int W, int font_scale, int color_by_class,
                                int32_t* records, void* stream) {
-    if (int rc = vis_check("vis_prepare", H, W, n)) return rc;
-    if (int rc = vis_check_width("vis_prepare", "font_scale", font_scale)) return rc;
-    if (num_names < 0 || num_names > 65535) return fail(CMK_EINVAL, "%s: %ld names outside [0, 65535]", "vis_prepare", num_names);
-    if (n == 0) return CMK_OK;
-    if (!boxes || !scores || !classes || !order || !palette || !records || (num_names && (!names || !name_lens)))
-        return fail(CMK_EINVAL, "%s: null pointer", "vis_prepare");
-    hipLaunchKernelGGL(vis_prepare_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, boxes, scores, (const long long*)classes,
-                       (const long long*)order, names, name_lens, num_names, palette, n, H, W, font_scale, color_by_class ? 1 : 0, records);
-    return check_launch("vis_prepare");
+    return vis_prepare_launch("vis_prepare", boxes, scores, classes, order, names, name_lens, num_names, palette, n, H, W, font_scale, color_by_class,
+                              nullptr, records, stream);
+}
+
+extern "C" int cmk_vis_prepare_ids(const float* boxes, const float* scores, const int64_t* classes, const int64_t* order, const uint8_t* names,
+                                   const int32_t* name_lens, int num_names, const uint8_t* palette, int n, int H, int W, int font_scale,
+                                   int color_by_class, const int32_t* color_ids, int32_t* records, void* stream) {
+    return vis_prepare_launch("vis_prepare_ids", boxes, scores, classes, order, names, name_lens, num_names, palette, n, H, W, font_scale,
+                              color_by_class, color_ids, records, stream);
+}
+
+extern "C" int cmk_vis_track_iou_boxes(const float* old_boxes, int rows, const float* new_boxes, int n, double* iou, void* stream) {
+    if (int rc = vis_track_check("vis_track_iou_boxes", n, rows, VT_MAX)) return rc;
+    if (rows == 0 || n == 0) return CMK_OK;
+    if (!old_boxes || !new_boxes || !iou) return fail(CMK_EINVAL, "%s: null pointer", "vis_track_iou_boxes");
+    hipLaunchKernelGGL(vis_track_iou_kernel, dim3(cdiv(rows * n, 256)), dim3(256), 0, (hipStream_t)stream, old_boxes, rows, new_boxes, n, iou);
+    return check_launch("vis_track_iou_boxes");
+}
+
+extern "C" int cmk_vis_track_assign(const double* iou, const int32_t* inter, const int32_t* old_areas, const int32_t* new_areas, int rows,
+                                    const float* old_boxes, const int64_t* old_classes, const int32_t* old_ids, const int32_t* old_ttl,
+                                    const float* new_boxes, const int64_t* new_classes, int n, int max_tracks, int ttl, double threshold,
+                                    float* out_boxes, int64_t* out_classes, int32_t* out_ids, int32_t* out_ttl, int32_t* src, int32_t* track_ids,
+                                    int32_t* counters, void* stream) {
+    const char* what = "vis_track_assign";
+    if (int rc = vis_track_check(what, n, rows, max_tracks)) return rc;
+    if (ttl < 1 || ttl > 255) return fail(CMK_EINVAL, "%s: ttl = %ld outside [1, 255]", what, ttl);
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(CMK_EINVAL, "%s: the IoU threshold is outside [0, 1]", what);
+    if (!old_boxes || !old_classes || !old_ids || !old_ttl || !out_boxes || !out_classes || !out_ids || !out_ttl || !src || !counters ||
+        (n && (!new_boxes || !new_classes || !track_ids)))
+        return fail(CMK_EINVAL, "%s: null pointer", what);
+    if (n && rows) {
+        if ((iou != nullptr) == (inter != nullptr)) return fail(CMK_EINVAL, "%s: exactly one of the iou and inter tables must be given", what);
+        if (inter && (!old_areas || !new_areas)) return fail(CMK_EINVAL, "%s: null pointer (the inter table needs both area arrays)", what);
+    }
+    if (old_boxes == out_boxes || old_classes == out_classes || old_ids == out_ids || old_ttl == out_ttl)
+        return fail(CMK_EINVAL, "%s: the new table overlaps the old one; the update is out of place", what);
+    hipLaunchKernelGGL(vis_track_assign_kernel, dim3(1), dim3(VT_MAX), 0, (hipStream_t)stream, (n && rows) ? iou : nullptr, inter, old_areas, new_areas,
+                       rows, old_boxes, (const long long*)old_classes, old_ids, old_ttl, new_boxes, (const long long*)new_classes, n, max_tracks, ttl,
+                       threshold, out_boxes, (long long*)out_classes, out_ids, out_ttl, src, track_ids, counters);
+    return check_launch(what);
+}
+
+extern "C" int cmk_vis_track_gather(const int32_t* src, const int32_t* counters, const uint64_t* old_words, const int32_t* old_areas,
+                                    const uint64_t* new_words, const int32_t* new_areas, int n, int rows, int max_tracks, int H, int W,
+                                    uint64_t* out_words, int32_t* out_areas, void* stream) {
+    const char* what = "vis_track_gather";
+    if (int rc = vis_check(what, H, W, 0)) return rc;
+    if (int rc = vis_track_check(what, n, rows, max_tracks)) return rc;
+    if (!src || !counters || !old_words || !old_areas || !out_words || !out_areas || (n && (!new_words || !new_areas)))
+        return fail(CMK_EINVAL, "%s: null pointer", what);
+    const int nw = (int)(((int64_t)H * W + 63) / 64);
+    const int64_t row = (int64_t)nw * 8;
+    if (vis_overlap(out_words, row * max_tracks, old_words, row * max_tracks) || (n && vis_overlap(out_words, row * max_tracks, new_words, row * n)) ||
+        vis_overlap(out_areas, 4 * (int64_t)max_tracks, old_areas, 4 * (int64_t)max_tracks))
+        return fail(CMK_EINVAL, "%s: the new table overlaps the old one or the new instances; the gather is out of place", what);
+    if (rows == 0) return CMK_OK;
+    hipLaunchKernelGGL(vis_track_gather_kernel, dim3(min(cdiv(nw, 256), 256), rows), dim3(256), 0, (hipStream_t)stream, src, counters,
+                       (const unsigned long long*)old_words, old_areas, (const unsigned long long*)new_words, new_areas, n, max_tracks, nw,
+                       (unsigned long long*)out_words, out_areas);
+    return check_launch(what);
 }
 
 extern "C" int cmk_vis_compose(const uint8_t* image_in, uint8_t* image_out, int H, int W, const uint64_t* words, const int32_t* records, int n,

@@ -1682,27 +1682,46 @@ def mask_boundary_intersections(det_masks: torch.Tensor, gt_counts, h: int, w: i
 
 
 # ---- visualizer (csrc/visualize.hip; the contract is in include/cmk.h and DESIGN §3 "Visualizer") ------------------------------------
+def _vis_prepare(entry: str, boxes, scores, classes, order, names, name_lens, num_names, palette, h, w, font_scale, color_by_class, color_ids):
+    n = int(boxes.shape[0])
+    for t, dt, what in ((boxes, torch.float32, "boxes"), (scores, torch.float32, "scores"), (classes, torch.int64, "classes"),
+                        (order, torch.int64, "order"), (names, torch.uint8, "names"), (name_lens, torch.int32, "name_lens"),
+                        (palette, torch.uint8, "palette")) + (((color_ids, torch.int32, "color_ids"),) if color_ids is not None else ()):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise _lib.CmkError("{}: {} must be contiguous {} on the GPU, got {} {} on {}".format(entry, what, dt, t.dtype, tuple(t.shape), t.device))
+    if tuple(boxes.shape) != (n, 4) or scores.numel() != n or classes.numel() != n or order.numel() != n or palette.numel() != 192 \
+            or names.numel() < 32 * num_names or name_lens.numel() < num_names:
+        raise _lib.CmkError("{}: boxes {}, scores {}, classes {}, order {}, palette {}, names {} do not fit {} instances and {} names".format(
+            entry, tuple(boxes.shape), tuple(scores.shape), tuple(classes.shape), tuple(order.shape), tuple(palette.shape), tuple(names.shape), n, num_names))
+    if color_ids is not None and (tuple(color_ids.shape) != (n,) or color_ids.device != boxes.device):
+        raise _lib.CmkError("{}: color_ids {} on {} do not fit {} instances on {}".format(entry, tuple(color_ids.shape), color_ids.device, n, boxes.device))
+    _need_current_device(boxes, entry)
+    lib = _lib.load()
+    records = torch.empty((max(n, 1), lib.cmk_vis_record_ints()), dtype=torch.int32, device=boxes.device)
+    args = (boxes.data_ptr(), scores.data_ptr(), classes.data_ptr(), order.data_ptr(), names.data_ptr(), name_lens.data_ptr(), int(num_names),
+            palette.data_ptr(), n, int(h), int(w), int(font_scale), 1 if color_by_class else 0)
+    if color_ids is None:
+        check(lib.cmk_vis_prepare(*args, records.data_ptr(), _stream()), "cmk_vis_prepare")
+    else:
+        check(lib.cmk_vis_prepare_ids(*args, color_ids.data_ptr(), records.data_ptr(), _stream()), "cmk_vis_prepare_ids")
+    return records
+
+
 def vis_prepare(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, order: torch.Tensor, names: torch.Tensor,
                 name_lens: torch.Tensor, num_names: int, palette: torch.Tensor, h: int, w: int, font_scale: int, color_by_class: bool) -> torch.Tensor:
     """Per-instance draw records in draw order, (max(n,1), cmk_vis_record_ints()) int32 on the boxes' device.  boxes (n,4) float32,
     scores (n,) float32, classes and order (n,) int64, names (rows,32) uint8 glyph indices, name_lens int32, palette (64,3) uint8."""
-    n = int(boxes.shape[0])
-    for t, dt, what in ((boxes, torch.float32, "boxes"), (scores, torch.float32, "scores"), (classes, torch.int64, "classes"),
-                        (order, torch.int64, "order"), (names, torch.uint8, "names"), (name_lens, torch.int32, "name_lens"),
-                        (palette, torch.uint8, "palette")):
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise _lib.CmkError("vis_prepare: {} must be contiguous {} on the GPU, got {} {} on {}".format(what, dt, t.dtype, tuple(t.shape), t.device))
-    if tuple(boxes.shape) != (n, 4) or scores.numel() != n or classes.numel() != n or order.numel() != n or palette.numel() != 192 \
-            or names.numel() < 32 * num_names or name_lens.numel() < num_names:
-        raise _lib.CmkError("vis_prepare: boxes {}, scores {}, classes {}, order {}, palette {}, names {} do not fit {} instances and {} names".format(
-            tuple(boxes.shape), tuple(scores.shape), tuple(classes.shape), tuple(order.shape), tuple(palette.shape), tuple(names.shape), n, num_names))
-    _need_current_device(boxes, "vis_prepare")
-    lib = _lib.load()
-    records = torch.empty((max(n, 1), lib.cmk_vis_record_ints()), dtype=torch.int32, device=boxes.device)
-    check(lib.cmk_vis_prepare(boxes.data_ptr(), scores.data_ptr(), classes.data_ptr(), order.data_ptr(), names.data_ptr(), name_lens.data_ptr(),
-                              int(num_names), palette.data_ptr(), n, int(h), int(w), int(font_scale), 1 if color_by_class else 0,
-                              records.data_ptr(), _stream()), "cmk_vis_prepare")
-    return records
+    return _vis_prepare("vis_prepare", boxes, scores, classes, order, names, name_lens, num_names, palette, h, w, font_scale, color_by_class, None)
+
+
+def vis_prepare_ids(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, order: torch.Tensor, names: torch.Tensor,
+                    name_lens: torch.Tensor, num_names: int, palette: torch.Tensor, h: int, w: int, font_scale: int, color_by_class: bool,
+                    color_ids: torch.Tensor) -> torch.Tensor:
+    """vis_prepare with the colour index of every instance given: color_ids (n,) int32 by original instance (track ids);
+    col = palette[color_ids[k] mod 64], the remainder non-negative; color_by_class is not consulted."""
+    if not torch.is_tensor(color_ids):
+        raise _lib.CmkError("vis_prepare_ids: color_ids must be an (n,) int32 tensor on the GPU, got {}".format(type(color_ids).__name__))
+    return _vis_prepare("vis_prepare_ids", boxes, scores, classes, order, names, name_lens, num_names, palette, h, w, font_scale, color_by_class, color_ids)
 
 
 def vis_compose(image: torch.Tensor, words: Optional[torch.Tensor], records: torch.Tensor, n: int, font: torch.Tensor, line_width: int,
@@ -1749,3 +1768,115 @@ def vis_keypoints(image: torch.Tensor, keypoints: torch.Tensor, records: torch.T
     winner = torch.empty((h, w), dtype=torch.int32, device=image.device)
     check(lib.cmk_vis_keypoints(image.data_ptr(), h, w, keypoints.data_ptr(), records.data_ptr(), n, k, skeleton.data_ptr() if nseg else None, nseg,
                                 float(threshold), int(line_width), int(keypoint_color), winner.data_ptr(), _stream()), "cmk_vis_keypoints")
+
+
+# ---- video (csrc/visualize.hip; include/cmk.h and DESIGN §3 "Video") -----------------------------------------------------------------
+MAX_TRACKS = 1024
+
+
+def _need_track(t, dt, shape, dev, entry: str, what: str) -> None:
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or (dev is not None and t.device != dev):
+        raise _lib.CmkError("{}: {} must be contiguous {} {} on {}, got {}".format(
+            entry, what, dt, tuple(shape), dev if dev is not None else "the GPU",
+            "{} {} on {}".format(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__))
+
+
+def vis_track_iou_boxes(old_boxes: torch.Tensor, rows: int, new_boxes: torch.Tensor, iou: torch.Tensor) -> None:
+    """Box mode: iou[:rows * n] (float64, row-major (rows, n)) of the first `rows` rows of a track table's boxes (max_tracks,4) float32
+    against the new (n,4) float32 boxes.  iou: a flat float64 workspace of at least rows * n elements."""
+    if not torch.is_tensor(old_boxes) or old_boxes.dim() != 2:
+        raise _lib.CmkError("vis_track_iou_boxes: old_boxes must be a (max_tracks,4) tensor")
+    cap, n, rows = int(old_boxes.shape[0]), int(new_boxes.shape[0]) if torch.is_tensor(new_boxes) and new_boxes.dim() == 2 else -1, int(rows)
+    if not 1 <= cap <= MAX_TRACKS or not 0 <= n <= cap or not 0 <= rows <= cap:
+        raise _lib.CmkError("vis_track_iou_boxes: max_tracks = {} (in [1, {}]), n = {}, rows = {} (both in [0, max_tracks])".format(cap, MAX_TRACKS, n, rows))
+    _need_track(old_boxes, torch.float32, (cap, 4), None, "vis_track_iou_boxes", "old_boxes")
+    dev = old_boxes.device
+    _need_track(new_boxes, torch.float32, (n, 4), dev, "vis_track_iou_boxes", "new_boxes")
+    if not torch.is_tensor(iou) or iou.dtype != torch.float64 or iou.device != dev or not iou.is_contiguous() or iou.numel() < rows * n:
+        raise _lib.CmkError("vis_track_iou_boxes: iou must be contiguous float64 with at least {} elements on {}".format(rows * n, dev))
+    _need_current_device(old_boxes, "vis_track_iou_boxes")
+    check(_lib.load().cmk_vis_track_iou_boxes(old_boxes.data_ptr(), rows, new_boxes.data_ptr(), n, iou.data_ptr(), _stream()), "cmk_vis_track_iou_boxes")
+
+
+def vis_track_assign(old: dict, out: dict, new_boxes: torch.Tensor, new_classes: torch.Tensor, rows: int, ttl: int, threshold: float,
+                     src: torch.Tensor, counters: torch.Tensor, iou: Optional[torch.Tensor] = None, inter: Optional[torch.Tensor] = None,
+                     new_areas: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One frame of the association rule (include/cmk.h) -> track_ids (n,) int32.  old / out: the two halves of the track table, dicts of
+    boxes (max_tracks,4) float32, classes (max_tracks,) int64, ids and ttl (max_tracks,) int32 and, in mask mode, areas (max_tracks,) int32;
+    src (max_tracks,) int32 and counters (4,) int32 (n_tracks, next_id, dropped, spare) on the same device.  Give `iou` (box mode, the
+    workspace vis_track_iou_boxes filled) or `inter` with new_areas (mask mode, the table of cmk_mask_intersections).  Nothing is read back."""
+    e = "vis_track_assign"
+    if not isinstance(old, dict) or not isinstance(out, dict) or not torch.is_tensor(old.get("boxes")) or old["boxes"].dim() != 2:
+        raise _lib.CmkError("vis_track_assign: old and out must be dicts of the table's tensors (boxes, classes, ids, ttl)")
+    cap = int(old["boxes"].shape[0])
+    n = int(new_boxes.shape[0]) if torch.is_tensor(new_boxes) and new_boxes.dim() == 2 else -1
+    rows, ttl, threshold = int(rows), int(ttl), float(threshold)
+    if not 1 <= cap <= MAX_TRACKS:
+        raise _lib.CmkError("vis_track_assign: max_tracks = {} outside [1, {}]".format(cap, MAX_TRACKS))
+    if not 0 <= n <= cap:
+        raise _lib.CmkError("vis_track_assign: {} instances (boxes {}) outside [0, max_tracks = {}]".format(
+            n, tuple(new_boxes.shape) if torch.is_tensor(new_boxes) else None, cap))
+    if not 0 <= rows <= cap or not 1 <= ttl <= 255 or not 0.0 <= threshold <= 1.0:
+        raise _lib.CmkError("vis_track_assign: rows = {} (in [0, {}]), ttl = {} (in [1, 255]), threshold = {} (in [0, 1])".format(rows, cap, ttl, threshold))
+    dev = old["boxes"].device
+    for half, name in ((old, "old"), (out, "out")):
+        for key, dt, shape in (("boxes", torch.float32, (cap, 4)), ("classes", torch.int64, (cap,)), ("ids", torch.int32, (cap,)), ("ttl", torch.int32, (cap,))):
+            _need_track(half.get(key), dt, shape, dev, e, name + "." + key)
+    if any(old[k].data_ptr() == out[k].data_ptr() for k in ("boxes", "classes", "ids", "ttl")):
+        raise _lib.CmkError("vis_track_assign: out is old; the update is out of place (two halves of a ping-pong pair)")
+    _need_track(new_boxes, torch.float32, (n, 4), dev, e, "new_boxes")
+    _need_track(new_classes, torch.int64, (n,), dev, e, "new_classes")
+    _need_track(src, torch.int32, (cap,), dev, e, "src")
+    _need_track(counters, torch.int32, (4,), dev, e, "counters")
+    if n and rows:
+        if (iou is None) == (inter is None):
+            raise _lib.CmkError("vis_track_assign: give exactly one of iou (box mode) and inter (mask mode)")
+        table, dt = (iou, torch.float64) if iou is not None else (inter, torch.int32)
+        if not torch.is_tensor(table) or table.dtype != dt or table.device != dev or not table.is_contiguous() or table.numel() < rows * n:
+            raise _lib.CmkError("vis_track_assign: the {} table must be contiguous {} with at least {} elements on {}".format(
+                "iou" if iou is not None else "inter", dt, rows * n, dev))
+        if inter is not None:
+            _need_track(old.get("areas"), torch.int32, (cap,), dev, e, "old.areas")
+            _need_track(new_areas, torch.int32, (n,), dev, e, "new_areas")
+    _need_current_device(old["boxes"], e)
+    track_ids = torch.empty((n,), dtype=torch.int32, device=dev)
+    use = bool(n and rows)
+    check(_lib.load().cmk_vis_track_assign(
+        iou.data_ptr() if use and iou is not None else None, inter.data_ptr() if use and inter is not None else None,
+        old["areas"].data_ptr() if use and inter is not None else None, new_areas.data_ptr() if use and inter is not None else None, rows,
+        old["boxes"].data_ptr(), old["classes"].data_ptr(), old["ids"].data_ptr(), old["ttl"].data_ptr(),
+        new_boxes.data_ptr() if n else None, new_classes.data_ptr() if n else None, n, cap, ttl, threshold,
+        out["boxes"].data_ptr(), out["classes"].data_ptr(), out["ids"].data_ptr(), out["ttl"].data_ptr(), src.data_ptr(),
+        track_ids.data_ptr() if n else None, counters.data_ptr(), _stream()), "cmk_vis_track_assign")
+    return track_ids
+
+
+def vis_track_gather(src: torch.Tensor, counters: torch.Tensor, old: dict, out: dict, new_words: torch.Tensor, new_areas: torch.Tensor,
+                     rows: int, h: int, w: int) -> None:
+    """Mask mode, after vis_track_assign: the words (max_tracks, mask_words(h,w)) int64 and areas (max_tracks,) int32 of `out` from the new
+    instances' (n, mask_words(h,w)) words / (n,) areas and the `old` half, following src.  rows: an upper bound of the new n_tracks."""
+    e = "vis_track_gather"
+    h, w, rows = int(h), int(w), int(rows)
+    if h < 1 or w < 1 or h * w >= 2 ** 31 - 1:
+        raise _lib.CmkError("vis_track_gather: size {}x{} is outside what int32 positions hold".format(h, w))
+    if not isinstance(old, dict) or not isinstance(out, dict) or not torch.is_tensor(old.get("words")) or old["words"].dim() != 2:
+        raise _lib.CmkError("vis_track_gather: old and out must be dicts with the table's words and areas")
+    cap, nw = int(old["words"].shape[0]), mask_words(h, w)
+    n = int(new_words.shape[0]) if torch.is_tensor(new_words) and new_words.dim() == 2 else -1
+    if not 1 <= cap <= MAX_TRACKS or not 0 <= n <= cap or not 0 <= rows <= cap:
+        raise _lib.CmkError("vis_track_gather: max_tracks = {} (in [1, {}]), n = {}, rows = {} (both in [0, max_tracks])".format(cap, MAX_TRACKS, n, rows))
+    _need_track(old["words"], torch.int64, (cap, nw), None, e, "old.words")
+    dev = old["words"].device
+    _need_track(old.get("areas"), torch.int32, (cap,), dev, e, "old.areas")
+    _need_track(out.get("words"), torch.int64, (cap, nw), dev, e, "out.words")
+    _need_track(out.get("areas"), torch.int32, (cap,), dev, e, "out.areas")
+    _need_track(new_words, torch.int64, (n, nw), dev, e, "new_words")
+    _need_track(new_areas, torch.int32, (n,), dev, e, "new_areas")
+    _need_track(src, torch.int32, (cap,), dev, e, "src")
+    _need_track(counters, torch.int32, (4,), dev, e, "counters")
+    if old["words"].data_ptr() == out["words"].data_ptr() or old["areas"].data_ptr() == out["areas"].data_ptr():
+        raise _lib.CmkError("vis_track_gather: out is old; the gather is out of place (two halves of a ping-pong pair)")
+    _need_current_device(src, e)
+    check(_lib.load().cmk_vis_track_gather(src.data_ptr(), counters.data_ptr(), old["words"].data_ptr(), old["areas"].data_ptr(),
+                                           new_words.data_ptr() if n else None, new_areas.data_ptr() if n else None, n, rows, cap, h, w,
+                                           out["words"].data_ptr(), out["areas"].data_ptr(), _stream()), "cmk_vis_track_gather")

@@ -172,6 +172,11 @@ class Visualizer:
         return sk
 
     # ---- drawing -----------------------------------------------------------------------------------------------------------------
+    def _color_ids(self, instances, boxes, classes, words, areas, h, w):
+        """The colour index per instance, (n,) int32 on the device, or None for color_by's rule.  Called once per draw, empty frames
+        included, with the frame's float32 boxes, int64 classes and packed masks (video.VideoVisualizer tracks here)."""
+        return None
+
     def draw(self, image, instances: Instances) -> torch.Tensor:
         """-> a new (h,w,3) uint8 tensor on the instances' device; `image` is left as it is."""
         if not isinstance(instances, Instances) or not instances.has("pred_boxes") or not instances.has("scores") or not instances.has("pred_classes"):
@@ -224,11 +229,18 @@ class Visualizer:
             classes = classes.detach().to(device=dev, dtype=torch.int64).contiguous()
             area = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
             order = torch.sort(area, descending=True, stable=True).indices.contiguous()       # plumbing; everything else is the library's
-            records = ops.vis_prepare(boxes, scores, classes, order, t["names"], t["name_lens"], t["num_names"], t["palette"], h, w, fs,
-                                      self.color_by == "class")
+            areas = None
             if masks is not None:
-                words, _ = ops.mask_pack_bits(masks)
+                words, areas = ops.mask_pack_bits(masks)
+            color_ids = self._color_ids(instances, boxes, classes, words, areas, h, w)
+            if color_ids is None:
+                records = ops.vis_prepare(boxes, scores, classes, order, t["names"], t["name_lens"], t["num_names"], t["palette"], h, w, fs,
+                                          self.color_by == "class")
+            else:
+                records = ops.vis_prepare_ids(boxes, scores, classes, order, t["names"], t["name_lens"], t["num_names"], t["palette"], h, w, fs,
+                                              self.color_by == "class", color_ids)
         else:
+            self._color_ids(instances, boxes.detach().to(torch.float32).reshape(0, 4), classes.detach().to(device=dev, dtype=torch.int64), None, None, h, w)
             records = t["font"].new_empty((0,), dtype=torch.int32)
         out = ops.vis_compose(image, words, records, n, t["font"], lw, fs, self.alpha256)
         if kps is not None and n:

@@ -521,6 +521,43 @@ int cmk_vis_compose(const uint8_t* image_in, uint8_t* image_out, int H, int W, c
 int cmk_vis_keypoints(uint8_t* image, int H, int W, const float* keypoints, const int32_t* records, int n, int num_keypoints,
                       const int32_t* skeleton, int num_segments, float threshold, int line_width, int keypoint_color, int32_t* winner,
                       void* stream);
+/* cmk_vis_prepare with the colour of an instance chosen by the caller: col = palette[color_ids[k] mod 64] (k the original index, the
+ * remainder taken non-negative; color_by_class is not consulted).  color_ids (n) int32 by ORIGINAL instance, e.g. the track ids of
+ * cmk_vis_track_assign.  A null color_ids is cmk_vis_prepare, bit for bit. */
+int cmk_vis_prepare_ids(const float* boxes, const float* scores, const int64_t* classes, const int64_t* order, const uint8_t* names,
+                        const int32_t* name_lens, int num_names, const uint8_t* palette, int n, int H, int W, int font_scale, int color_by_class,
+                        const int32_t* color_ids, int32_t* records, void* stream);
+
+/* ---- video: instance ids that follow objects from frame to frame (the reference's demo.py --video-input draws with detectron2's
+ * VideoVisualizer, whose _assign_colors matches a frame's instances to the previous frame's by IoU on the host; restated in DESIGN §3
+ * "Video").  The track table lives on the device: max_tracks rows of box (4 float), class (int64), id (int32), ttl (int32) and, in mask
+ * mode, packed mask words and area, plus counters (4 int32: n_tracks, next_id, dropped, spare).  A frame's update reads one table and
+ * writes another (the two halves of a ping-pong pair, never in place); counters are updated in place.  Nothing is read back, allocated or
+ * synchronised.  Refused by all: null pointers, max_tracks outside [1, 1024], n outside [0, max_tracks], rows outside [0, max_tracks].
+ * The float64 table iou[i*n + j] of old row i < rows against new instance j < n, boxes as (x1, y1, x2, y2): iw = min(x2) - max(x1),
+ * ih = min(y2) - max(y1), inter = iw*ih if both are positive, else 0, iou = inter / (a_old + a_new - inter) with a = (x2-x1)*(y2-y1),
+ * all in float64 without contraction; a zero union or a NaN gives 0.  rows == 0 or n == 0: CMK_OK, no launch. */
+int cmk_vis_track_iou_boxes(const float* old_boxes, int rows, const float* new_boxes, int n, double* iou, void* stream);
+/* One frame of the association rule.  With T = min(n_tracks, rows): value[i][j] of old row i < T and new instance j is 0 where the
+ * classes differ, else iou[i*n + j] (box mode, `iou` given) or inter[i*n + j] / (old_areas[i] + new_areas[j] - inter[i*n + j]) in float64
+ * (mask mode, `inter` given, the table of cmk_mask_intersections(old words, rows, new words, n); a zero union gives 0); exactly one of iou
+ * and inter is non-null unless n == 0.  best[i] is the first j that attains the row maximum; i is a candidate iff the maximum is
+ * > threshold.  New j takes the id of the smallest candidate i with best[i] == j, every other new instance next_id, next_id + 1, .. in
+ * order of j.  Every other old row misses: ttl - 1, and survives iff that is > 0.  The new table: the n new instances in order with
+ * ttl = `ttl`, then the survivors in old order while they fit in max_tracks; the rest add to `dropped`.  src[slot] = j for a new row,
+ * n + i for a survivor (the map cmk_vis_track_gather follows); track_ids[j] is the id of new instance j.  Always launches (n == 0 ages the
+ * table).  ttl in [1, 255], threshold in [0, 1]; an out table that is an old table is refused. */
+int cmk_vis_track_assign(const double* iou, const int32_t* inter, const int32_t* old_areas, const int32_t* new_areas, int rows,
+                         const float* old_boxes, const int64_t* old_classes, const int32_t* old_ids, const int32_t* old_ttl,
+                         const float* new_boxes, const int64_t* new_classes, int n, int max_tracks, int ttl, double threshold,
+                         float* out_boxes, int64_t* out_classes, int32_t* out_ids, int32_t* out_ttl, int32_t* src, int32_t* track_ids,
+                         int32_t* counters, void* stream);
+/* Mask mode, after cmk_vis_track_assign on the same src and counters: out row s < n_tracks gets the ceil(H*W/64) words and the area of
+ * new instance src[s], or of old row src[s] - n.  rows: how many out rows can be live (n_tracks <= rows is the caller's bound; the grid).
+ * Out of place: out_words overlapping old_words or new_words is refused, as is H*W >= 2^31 - 1.  rows == 0: CMK_OK, no launch. */
+int cmk_vis_track_gather(const int32_t* src, const int32_t* counters, const uint64_t* old_words, const int32_t* old_areas,
+                         const uint64_t* new_words, const int32_t* new_areas, int n, int rows, int max_tracks, int H, int W,
+                         uint64_t* out_words, int32_t* out_areas, void* stream);
 
 /* ---- multi-GPU result exchange (the reference's analogue: comm.gather in evaluation/coco_evaluation.py:155-156) ----------
  * One fixed-stride float record per image, written straight into the all-gather send buffer:
