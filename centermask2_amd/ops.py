@@ -6,7 +6,7 @@ an OSA concat buffer.  Every function raises if the tensors are not on a GPU —
 """
 import ctypes
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -248,6 +248,11 @@ def fold_frozen_bn(weight, bias, running_mean, running_var, eps=1e-5):
     return scale.float(), shift.float()
 
 
+def _out_hw(h: int, w: int, stride: int) -> Tuple[int, int]:
+    """Output size of a conv here: 'same' padding, stride 1 or 2."""
+    return (h, w) if stride == 1 else ((h - 1) // 2 + 1, (w - 1) // 2 + 1)
+
+
 def _fill_desc(d: ConvDesc, x: View, pc: PackedConv, y: View, relu, relu_upto, res, res_upsample, in_relu, in_affine=None) -> None:
     _need_gpu(x.t, "conv2d")
     n, h, w = x.nhw
@@ -269,9 +274,7 @@ def _fill_desc(d: ConvDesc, x: View, pc: PackedConv, y: View, relu, relu_upto, r
     d.N, d.H, d.W, d.Cin, d.Cout = n, h, w, pc.cin_pad, pc.cout
     assert x.c == pc.cin_pad, "conv2d: input view has {} channels, packed weights expect {}".format(x.c, pc.cin_pad)
     assert y.c == pc.cout
-    ho = h if pc.stride == 1 else (h - 1) // 2 + 1
-    wo = w if pc.stride == 1 else (w - 1) // 2 + 1
-    assert tuple(y.t.shape[:3]) == (n, ho, wo), (tuple(y.t.shape), (n, ho, wo))
+    assert tuple(y.t.shape[:3]) == (n,) + _out_hw(h, w, pc.stride), (tuple(y.t.shape), (n,) + _out_hw(h, w, pc.stride))
     d.ksize, d.stride = pc.k, pc.stride
     d.relu_upto = (pc.cout if relu else 0) if relu_upto is None else relu_upto
     d.in_relu = int(in_relu)
@@ -298,7 +301,7 @@ TUNE_ONLY = None          # callable(key) -> [(wm, sc, wn, splitk), ...]: the tu
                           # re-tuning: tools/tune_sp3.py); TUNE_REPS timed launches per candidate, best of TUNE_ROUNDS interleaved rounds
 TUNE_REPS, TUNE_ROUNDS = 2, 1
 AUTOTUNE = False          # when True, the first call of every distinct conv problem times the variant menu (needs an idle, non-capturing stream)
-_TUNED = {}               # problem key -> (wm, sc, wn)
+_TUNED = {}               # problem key -> plain tuple, Variant.stored(): (wm, sc, wn[, splitk[, tail ways]])
 
 
 def set_autotune(flag: bool) -> None:
@@ -323,6 +326,30 @@ def _str_to_key(s: str):
     return (int(k), int(stride), vals[0], vals[1], vals[2], vals[3], vals[4], tuple(tuple(int(v) for v in t.split("x")) for t in shapes.split("+")))
 
 
+class Variant(NamedTuple):
+    """A tile variant, canonical: tune_wm / tune_sc / tune_wn of cmk_conv_desc, split-K ways (1 = none), tail split-K ways (cmk.h splitk_tail; 0 = off)."""
+    wm: int
+    sc: int
+    wn: int
+    splitk: int = 1
+    tail: int = 0
+
+    @classmethod
+    def of(cls, tv) -> "Variant":
+        """From any accepted spelling: (wm, sc, wn[, splitk[, tail]]) as a tuple, a JSON list or a Variant; tail ways 0 and 1 both mean off."""
+        wm, sc, wn, splitk, tail = (tuple(tv) + (1, 0))[:5]
+        return cls(wm, sc, wn, splitk, int(tail) if tail > 1 else 0)
+
+    def stored(self, least: int = 3) -> tuple:
+        """The plain tuple _TUNED holds and save_tuned writes: (wm, sc, wn), (wm, sc, wn, splitk) or, with a tail, all five (least = 4: TUNE_LOG's names)."""
+        return tuple(self) if self.tail else tuple(self[:max(least, 4 if self.splitk != 1 else 3)])
+
+
+def _variant5(tv) -> tuple:
+    """(wm, sc, wn[, splitk[, tail]]) -> (wm, sc, wn, splitk) or, with a tail, (wm, sc, wn, splitk, tail): a candidate's name in TUNE_LOG."""
+    return Variant.of(tv).stored(4)
+
+
 def save_tuned(path: str) -> None:
     """Write the measured variant table (problem -> [wm, sc, wn[, splitk[, tail ways]]]) as JSON; shipped tables live in centermask2_amd/tuned/."""
     import json
@@ -330,26 +357,9 @@ def save_tuned(path: str) -> None:
         json.dump({_key_to_str(k): list(v) for k, v in sorted(_TUNED.items(), key=lambda kv: _key_to_str(kv[0]))}, f, indent=0)
 
 
-def _variant4(tv) -> tuple:
-    """(wm, sc, wn[, splitk]) -> (wm, sc, wn, splitk)."""
-    return tuple(tv[:3]) + (tv[3] if len(tv) > 3 else 1,)
-
-
-def _variant_tail(tv) -> int:
-    """The optional fifth element: the ways of the tail split-K of a RoI-pair Winograd launch (cmk.h splitk_tail); 0 = off."""
-    return int(tv[4]) if len(tv) > 4 and tv[4] > 1 else 0
-
-
-def _variant5(tv) -> tuple:
-    """(wm, sc, wn[, splitk[, tail]]) -> (wm, sc, wn, splitk) or, with a tail, (wm, sc, wn, splitk, tail)."""
-    t = _variant_tail(tv)
-    return _variant4(tv) + ((t,) if t else ())
-
-
 def _variant_on_menu(tv) -> bool:
     """(wm, sc, wn[, splitk[, tail]]) names a kernel this library has (older tables may carry variants that were removed since)."""
-    wm, sc, wn, sk = _variant4(tv)
-    tail = _variant_tail(tv)
+    wm, sc, wn, sk, tail = Variant.of(tv)
     if tail and not (wm == 6 and sc in (16, 32) and wn == 2 and sk == 1 and tail in (2, 4, 8)):
         return False                  # the tail is a feature of the RoI-pair F(4x4) forms alone
     if wm == 6 and sc == 64:          # F(4x4,3x3), shared-V form (conv_wino6s.hip)
@@ -380,16 +390,14 @@ def load_tuned(path: str) -> int:
 
 
 def _out_pixels(d) -> int:
-    ho = d.H if d.stride == 1 else (d.H - 1) // 2 + 1
-    wo = d.W if d.stride == 1 else (d.W - 1) // 2 + 1
+    ho, wo = _out_hw(d.H, d.W, d.stride)
     return d.N * ho * wo
 
 
-def _set_variant(descs, n, tv):
-    """Write a (wm, sc, wn[, splitk[, tail]]) choice into the descriptors; returns the split-K (or tail) workspace (keep it alive until
-    the launch)."""
-    wm, sc, wn, sk = _variant4(tv)
-    tail = _variant_tail(tv)
+def _set_variant(descs, n, tv, tail_tiles=None):
+    """Write a variant (any spelling) into the descriptors; returns the split-K (or tail) workspace (keep it alive until the launch).
+    tail_tiles: the tile count of a tail (cmk.h splitk_tail_tiles); None = TAIL_TILES."""
+    wm, sc, wn, sk, tail = Variant.of(tv)
     for i in range(n):
         descs[i].tune_wm, descs[i].tune_sc, descs[i].tune_wn = wm, sc, wn
         descs[i].splitk, descs[i].splitk_ws = 0, None
@@ -397,7 +405,7 @@ def _set_variant(descs, n, tv):
     ws = None
     if tail:
         d = descs[0]
-        d.splitk_tail, d.splitk_tail_tiles = tail, TAIL_TILES
+        d.splitk_tail, d.splitk_tail_tiles = tail, TAIL_TILES if tail_tiles is None else tail_tiles
         floats = _lib.load().cmk_conv_tail_ws_floats(ctypes.byref(d))      # 0: no ragged round on this device, the launch runs without a tail
         if floats > 0:
             ws = torch.empty((floats,), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
@@ -408,106 +416,6 @@ def _set_variant(descs, n, tv):
                          device=torch.device("cuda", torch.cuda.current_device()))       # == the inputs' device (_need_current_device)
         d.splitk, d.splitk_ws = sk, ws.data_ptr()
     return ws
-
-
-def _tune(descs, n, key) -> None:
-    """Time every available (wm, sc, wn, splitk) variant on the real buffers and remember the fastest.  The direct variants
-    (incl. the gather form and split-K, whose K order is unchanged up to the final sum) agree to rounding; variants the
-    library rejects for this shape are skipped."""
-    lib = _lib.load()
-    st = _stream()
-    d0 = descs[0]
-
-    def run():
-        return lib.cmk_conv2d_nhwc_multi(descs, n, st) if n > 1 else lib.cmk_conv2d_nhwc(ctypes.byref(descs[0]), st)
-
-    best, best_ms = (0, 0, 0), float("inf")
-    small = n == 1 and d0.res_mode != 2 and _out_pixels(d0) <= 32768      # few M tiles: split-K / gather forms can pay
-    sks = (1, 2, 4, 8) if small else (1,)
-    cands = [(wm, sc, wn, sk) for wn in range(1, 8) for wm in (1, 2) for sc in (16, 32) for sk in sks]
-    if small and d0.ksize == 3:
-        cands += [(7, 32, wn, sk) for wn in (1, 2, 4) for sk in sks]      # gather form
-    if d0.ksize == 3:
-        cands += [(9, 32, mt, sk) for mt in (4, 2) for sk in sks]   # gather form of a 3x3 conv on the pointwise GEMM kernel (conv_pw.hip GA)
-        if ALLOW_SPLIT_BF16:
-            cands += [(10, 32, 4, 1)]                               # ... and its opt-in bf16-split form
-        if ALLOW_SPLIT_F16:
-            cands += [(12, 32, 4, 1)]                               # ... and the fp16 two-piece form of the gather GEMM
-            cands += [(11, 2, g, 1) for g in range(4)]              # opt-in: direct 3x3 on two fp16 pieces per operand (conv_sp3.hip), four tile geometries
-            cands += [(11, 21, g, 1) for g in range(4)]             # ... one cout tile per wave: less cout padding, more and smaller workgroups
-    if d0.ksize == 1:
-        cands += [(8, 32, mt, sk) for mt in (4, 2) for sk in sks]   # pointwise GEMM kernel (conv_pw.hip), 256- or 128-pixel workgroups; same K order, same bits
-        if ALLOW_SPLIT_BF16:
-            cands += [(10, 32, 4, 1)]                               # ... its opt-in bf16-split form (the library refuses it where it does not apply)
-        if ALLOW_SPLIT_F16:
-            cands += [(12, 32, 4, 1)]                               # ... its opt-in fp16-split form (two pieces, three products)
-    if ALLOW_WINOGRAD:
-        cands += [(5, 16, 2, 1)]                  # fused Winograd F(2x2,3x3)
-        cands += [(6, 16, 1, 1), (6, 16, 2, 1)]   # fused Winograd F(4x4,3x3): map tiles / pairs of RoI maps (the library rejects what does not apply)
-        cands += [(6, 64, 1, 1), (6, 64, 2, 1)]   # ... its shared-V form: 64 couts per workgroup from one frequency image (conv_wino6s.hip)
-        cands += [(6, 32, 1, 1), (6, 32, 2, 1)]   # ... its paired form: 64 couts per workgroup sharing the halo loads and pass 1
-        if n == 1 and d0.ksize == 3:
-            for sc in (16, 32):                   # ... the RoI-pair forms with the ragged last round of workgroups split over K, where there is one
-                _set_variant(descs, n, (6, sc, 2, 1, 2))
-                if lib.cmk_conv_tail_ws_floats(ctypes.byref(descs[0])) > 0:
-                    cands += [(6, sc, 2, 1, t) for t in (2, 4, 8)]
-        if small and d0.ksize == 3:
-            cands += [(6, sc, 1, sk) for sc in (16, 32) for sk in (2, 4)]      # ... with the chunk loop split over 2 / 4 workgroups (launches of about one round)
-    if TUNE_ONLY is not None:
-        cands = [_variant5(tv) for tv in TUNE_ONLY(key)]
-    times = {}
-    for _ in range(TUNE_ROUNDS):
-        for tv in cands:
-            if times.get(tv) == float("inf"):
-                continue
-            ws = _set_variant(descs, n, tv)
-            if run() != 0:
-                times[tv] = float("inf")          # not on the menu for this shape
-                continue
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _r in range(TUNE_REPS):
-                run()
-            e1.record()
-            e1.synchronize()
-            times[tv] = min(times.get(tv, float("inf")), e0.elapsed_time(e1) / TUNE_REPS)
-            del ws
-    for tv in cands:                              # first of equals wins, as before
-        if times.get(tv, float("inf")) < best_ms:
-            best, best_ms = (tv[:3] if tv[3] == 1 and len(tv) == 4 else tv), times[tv]
-    _TUNED[key] = best
-    TUNE_LOG.append((key, {tv: times[tv] for tv in cands if tv in times}))
-
-
-def _default_variant(d):
-    """No table entry and no tuner: library defaults, plus split-K for skinny 1x1 GEMMs (maskiou_fc1: 400 x 12544 x 1024)."""
-    if d.ksize == 1 and d.res_mode != 2 and _out_pixels(d) <= 1024 and d.Cin >= 4096:
-        chunks = d.Cin // 16
-        for sk in (4, 2):
-            if chunks % (2 * sk) == 0:
-                return (0, 0, 0, sk)
-    return (0, 0, 0)
-
-
-def _apply_tuning(descs, n, key, with_gn_stats=False, tune=True):
-    """Write an explicit variant into the descriptors: FORCE_VARIANT, else the loaded table, else (tune) the start-up tuner, else the split-K
-    default, with zero tune fields made explicit by the library (cmk_conv_resolve; with_gn_stats: as for a launch with fused GroupNorm
-    statistics).  Returns the (wm, sc, wn, splitk) written and the split-K workspace (keep it alive until the launch)."""
-    tv = FORCE_VARIANT if FORCE_VARIANT is not None else _TUNED.get(key)
-    if tv is None and tune and AUTOTUNE and not torch.cuda.is_current_stream_capturing():
-        _tune(descs, n, key)
-        tv = _TUNED[key]
-    if tv is None:
-        tv = _default_variant(descs[0]) if n == 1 else (0, 0, 0)
-    ws = _set_variant(descs, n, tv)
-    tv = _variant4(tv)
-    if tv[:3] == (0, 0, 0):
-        v = (ctypes.c_int * 3)()
-        check(_lib.load().cmk_conv_resolve(descs, n, int(with_gn_stats), v), "cmk_conv_resolve")
-        for i in range(n):
-            descs[i].tune_wm, descs[i].tune_sc, descs[i].tune_wn = v
-        tv = tuple(v) + tv[3:]
-    return tv, ws
 
 
 def _problem_key(descs, n):
@@ -525,13 +433,52 @@ def _plan(descs, n):
     return name.value.decode(), flops.value, list(recs)
 
 
-def _launch(descs, n, ws, xs, ys, pcs, single=False, what="cmk_conv2d_nhwc_multi") -> None:
-    """Launch the filled descriptors (cmk_conv2d_nhwc if single, else the _multi entry) with the split-K workspace ws alive across the
-    call.  When PROFILE is a list, the launch is timed and recorded under the kernel the library says it runs."""
-    lib = _lib.load()
-    if PROFILE is not None:
-        kernel, executed, _ = _plan(descs, n)
-        pc = pcs[0]
+class _ConvLaunch:
+    """One conv launch of the wrappers below and of the tuner: the descriptors of problems (xs[i], pcs[i]) -> ys[i], the variant written into them, the
+    split-K (or tail) workspace, which lives as long as this object, and the entry they go through (cmk_conv2d_nhwc if single, else the _multi one)."""
+
+    def __init__(self, xs, pcs, ys, relu=False, relu_upto=None, res=None, res_upsample=False, in_relu=False, in_affine=None, single=False):
+        self.xs, self.pcs, self.ys, self.n, self.single, self.ws = xs, pcs, ys, len(xs), single, None
+        self.descs = (ConvDesc * self.n)()
+        for i in range(self.n):
+            _fill_desc(self.descs[i], xs[i], pcs[i], ys[i], relu, relu_upto, res, res_upsample, in_relu, in_affine[i] if in_affine is not None else None)
+
+    def set(self, v) -> None:
+        self.ws = _set_variant(self.descs, self.n, v)
+
+    def choose(self, first=None, with_gn_stats=False) -> Variant:
+        """Write an explicit variant into the descriptors and return it: FORCE_VARIANT, else the loaded table, else the start-up tuner, else
+        the split-K default, with zero tune fields made explicit by the library (cmk_conv_resolve; with_gn_stats: as for a launch with fused
+        GroupNorm statistics).  first = k: the first k problems alone name the problem and get the variant, and nothing is tuned."""
+        descs, k = self.descs, self.n if first is None else first
+        key = _problem_key(descs, k)
+        tv = FORCE_VARIANT if FORCE_VARIANT is not None else _TUNED.get(key)
+        if tv is None and first is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing():
+            _tune(self, key)
+            tv = _TUNED[key]
+        if tv is None:
+            tv = _default_variant(descs[0]) if k == 1 else (0, 0, 0)
+        v = Variant.of(tv)
+        self.ws = _set_variant(descs, k, v)
+        if v[:3] == (0, 0, 0):
+            r = (ctypes.c_int * 3)()
+            check(_lib.load().cmk_conv_resolve(descs, k, int(with_gn_stats), r), "cmk_conv_resolve")
+            for i in range(k):
+                descs[i].tune_wm, descs[i].tune_sc, descs[i].tune_wn = r
+            v = v._replace(wm=r[0], sc=r[1], wn=r[2])
+        return v
+
+    def run(self) -> int:
+        lib = _lib.load()
+        return lib.cmk_conv2d_nhwc(ctypes.byref(self.descs[0]), _stream()) if self.single else lib.cmk_conv2d_nhwc_multi(self.descs, self.n, _stream())
+
+    def launch(self, what=None) -> None:
+        """run(), checked.  When PROFILE is a list, the launch is timed and recorded under the kernel the library says it runs."""
+        what = what or ("cmk_conv2d_nhwc" if self.single else "cmk_conv2d_nhwc_multi")
+        if PROFILE is None:
+            return check(self.run(), what)
+        xs, ys, pcs, pc = self.xs, self.ys, self.pcs, self.pcs[0]
+        kernel, executed, _ = _plan(self.descs, self.n)
         taps = pc.k * pc.k
         pix = lambda v: v.t.shape[0] * v.t.shape[1] * v.t.shape[2]
         flops = sum(2.0 * pix(y) * pc.cin * pc.cout * taps for y in ys)
@@ -539,42 +486,107 @@ def _launch(descs, n, ws, xs, ys, pcs, single=False, what="cmk_conv2d_nhwc_multi
         nbytes = sum(4.0 * (pix(x) * pc.cin + pix(y) * pc.cout) for x, y in zip(xs, ys)) + weights * 4.0 * pc.cin * pc.cout * taps
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    check(lib.cmk_conv2d_nhwc(ctypes.byref(descs[0]), _stream()) if single else lib.cmk_conv2d_nhwc_multi(descs, n, _stream()), what)
-    if PROFILE is not None:
+        check(self.run(), what)
         e1.record()
-        shape = tuple(xs[0].nhw) + (pc.cin, pc.cout, pc.k, pc.stride) if single else None
+        shape = tuple(xs[0].nhw) + (pc.cin, pc.cout, pc.k, pc.stride) if self.single else None
         PROFILE.append((kernel, flops, nbytes, e0, e1, shape, executed))
-    del ws                  # referenced until the launch has been issued
+
+
+def _tune(launch: _ConvLaunch, key) -> None:
+    """Time every available variant on the real buffers and remember the fastest.  The direct variants (incl. the gather form and
+    split-K, whose K order is unchanged up to the final sum) agree to rounding; variants the library rejects for this shape are skipped."""
+    n, d0 = launch.n, launch.descs[0]
+    small = n == 1 and d0.res_mode != 2 and _out_pixels(d0) <= 32768      # few M tiles: split-K / gather forms can pay
+    sks = (1, 2, 4, 8) if small else (1,)
+    cands = [(wm, sc, wn, sk) for wn in range(1, 8) for wm in (1, 2) for sc in (16, 32) for sk in sks]
+    if small and d0.ksize == 3:
+        cands += [(7, 32, wn, sk) for wn in (1, 2, 4) for sk in sks]      # gather form
+    if d0.ksize in (1, 3):
+        # pointwise GEMM kernel (conv_pw.hip), 256- or 128-pixel workgroups: a 1x1 conv (8; same K order, same bits) or the gather form of a 3x3 conv (9, GA)
+        cands += [(8 if d0.ksize == 1 else 9, 32, mt, sk) for mt in (4, 2) for sk in sks]
+        if ALLOW_SPLIT_BF16:
+            cands += [(10, 32, 4, 1)]                               # ... its opt-in bf16-split form (the library refuses it where it does not apply)
+        if ALLOW_SPLIT_F16:
+            cands += [(12, 32, 4, 1)]                               # ... its opt-in fp16-split form (two pieces, three products)
+        if ALLOW_SPLIT_F16 and d0.ksize == 3:                       # opt-in: direct 3x3 on two fp16 pieces per operand (conv_sp3.hip), four tile geometries,
+            cands += [(11, sc, g, 1) for sc in (2, 21) for g in range(4)]      # two cout tiles per wave or one (21: less cout padding, more and smaller workgroups)
+    if ALLOW_WINOGRAD:
+        cands += [(5, 16, 2, 1)]                  # fused Winograd F(2x2,3x3)
+        cands += [(6, 16, 1, 1), (6, 16, 2, 1)]   # fused Winograd F(4x4,3x3): map tiles / pairs of RoI maps (the library rejects what does not apply)
+        cands += [(6, 64, 1, 1), (6, 64, 2, 1)]   # ... its shared-V form: 64 couts per workgroup from one frequency image (conv_wino6s.hip)
+        cands += [(6, 32, 1, 1), (6, 32, 2, 1)]   # ... its paired form: 64 couts per workgroup sharing the halo loads and pass 1
+        if n == 1 and d0.ksize == 3:
+            for sc in (16, 32):                   # ... the RoI-pair forms with the ragged last round of workgroups split over K, where there is one
+                launch.set((6, sc, 2, 1, 2))
+                if _lib.load().cmk_conv_tail_ws_floats(ctypes.byref(d0)) > 0:
+                    cands += [(6, sc, 2, 1, t) for t in (2, 4, 8)]
+        if small and d0.ksize == 3:
+            cands += [(6, sc, 1, sk) for sc in (16, 32) for sk in (2, 4)]      # ... with the chunk loop split over 2 / 4 workgroups (launches of about one round)
+    if TUNE_ONLY is not None:
+        cands = TUNE_ONLY(key)
+    cands = [Variant.of(tv) for tv in cands]
+    times = {}
+    for _ in range(TUNE_ROUNDS):
+        for v in cands:
+            if times.get(v) == float("inf"):
+                continue
+            launch.set(v)
+            if launch.run() != 0:
+                times[v] = float("inf")           # not on the menu for this shape
+                continue
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _r in range(TUNE_REPS):
+                launch.run()
+            e1.record()
+            e1.synchronize()
+            times[v] = min(times.get(v, float("inf")), e0.elapsed_time(e1) / TUNE_REPS)
+    best, best_ms = Variant(0, 0, 0), float("inf")
+    for v in cands:                               # first of equals wins, as before
+        if times.get(v, float("inf")) < best_ms:
+            best, best_ms = v, times[v]
+    _TUNED[key] = best.stored()
+    TUNE_LOG.append((key, {v.stored(4): times[v] for v in cands if v in times}))
+
+
+def _default_variant(d) -> Variant:
+    """No table entry and no tuner: library defaults, plus split-K for skinny 1x1 GEMMs (maskiou_fc1: 400 x 12544 x 1024)."""
+    if d.ksize == 1 and d.res_mode != 2 and _out_pixels(d) <= 1024 and d.Cin >= 4096:
+        chunks = d.Cin // 16
+        for sk in (4, 2):
+            if chunks % (2 * sk) == 0:
+                return Variant(0, 0, 0, sk)
+    return Variant(0, 0, 0)
+
+
+def _new_outputs(xs: Sequence[View], pc: PackedConv) -> List[View]:
+    return [View(torch.empty((x.t.shape[0],) + _out_hw(x.t.shape[1], x.t.shape[2], pc.stride) + (pc.cout,), dtype=torch.float32, device=x.t.device)) for x in xs]
 
 
 def conv2d(x: View, pc: PackedConv, y: View, relu: bool = False, relu_upto: Optional[int] = None,
            res: Optional[View] = None, res_upsample: bool = False, in_relu: bool = False, pool: Optional[list] = None) -> None:
     """pool: a list that receives (partial sums, rows per record) when the kernel this conv runs on also leaves the average-pool partial
     sums of its output behind (cmk_conv_desc.pool_ws: the pointwise GEMM kernel, for the eSE gate); left empty otherwise."""
-    descs = (ConvDesc * 1)()
-    _fill_desc(descs[0], x, pc, y, relu, relu_upto, res, res_upsample, in_relu)
-    _, ws = _apply_tuning(descs, 1, _problem_key(descs, 1))
+    launch = _ConvLaunch([x], [pc], [y], relu, relu_upto, res, res_upsample, in_relu, single=True)
+    launch.choose()
     if pool is not None and FUSE_POOL:
-        rows = _lib.load().cmk_conv_pool_rows(ctypes.byref(descs[0]))
+        d = launch.descs[0]
+        rows = _lib.load().cmk_conv_pool_rows(ctypes.byref(d))
         if rows > 0:
-            d = descs[0]
             pws = torch.empty((2 * (-(-(d.N * d.H * d.W) // rows)), pc.cout), dtype=torch.float32, device=y.t.device)
             d.pool_ws = pws.data_ptr()
             pool.append((pws, rows))
-    _launch(descs, 1, ws, [x], [y], [pc], single=True, what="cmk_conv2d_nhwc")
+    launch.launch()
 
 
 def conv2d_multi(xs: Sequence[View], pcs: Sequence[PackedConv], ys: Sequence[View], relu: bool = False,
                  relu_upto: Optional[int] = None, in_affine=None) -> None:
     """One launch over several inputs that share the packed weights (pcs[i].w is the same tensor; scale/shift may differ).
     in_affine[i] = (scale, shift) of shape (N, Cin): the producer's GroupNorm+ReLU applied while staging input i."""
-    n = len(xs)
-    descs = (ConvDesc * n)()
-    for i in range(n):
-        assert pcs[i].w.data_ptr() == pcs[0].w.data_ptr()
-        _fill_desc(descs[i], xs[i], pcs[i], ys[i], relu, relu_upto, None, False, False, in_affine[i] if in_affine is not None else None)
-    _, ws = _apply_tuning(descs, n, _problem_key(descs, n))
-    _launch(descs, n, ws, xs, ys, pcs)
+    assert all(p.w.data_ptr() == pcs[0].w.data_ptr() for p in pcs)
+    launch = _ConvLaunch(xs, pcs, ys, relu, relu_upto, in_affine=in_affine)
+    launch.choose()
+    launch.launch()
 
 
 def _gn_records(descs, ys, groups):
@@ -617,20 +629,16 @@ def conv_gn_multi(xs: Sequence[View], pcs: Sequence[PackedConv], gamma: torch.Te
     """Tower conv (no activation) over several levels + the statistics of the GroupNorm that follows (fcos.py:182-186).
     Returns (raw conv outputs, [(scale, shift)] per level) — the affine is applied by the NEXT conv while staging.
     When the Winograd kernel runs the conv, its epilogue produces the statistics (no pass over the output)."""
-    n = len(xs)
-    pc = pcs[0]
-    ys = [View(torch.empty((x.t.shape[0], x.t.shape[1], x.t.shape[2], pc.cout), dtype=torch.float32, device=x.t.device)) for x in xs]
-    descs = (ConvDesc * n)()
-    for i in range(n):
-        assert pcs[i].w.data_ptr() == pc.w.data_ptr()
-        _fill_desc(descs[i], xs[i], pcs[i], ys[i], False, None, None, False, False, in_affine[i] if in_affine is not None else None)
-    fusable = _gn_fusable(xs, pc.cout, groups)
-    _, ws = _apply_tuning(descs, n, _problem_key(descs, n), with_gn_stats=fusable)
-    affine = _gn_records(descs, ys, groups) if fusable else None
-    _launch(descs, n, ws, xs, ys, pcs)
+    assert all(p.w.data_ptr() == pcs[0].w.data_ptr() for p in pcs)
+    ys = _new_outputs(xs, pcs[0])
+    launch = _ConvLaunch(xs, pcs, ys, in_affine=in_affine)
+    fusable = _gn_fusable(xs, pcs[0].cout, groups)
+    launch.choose(with_gn_stats=fusable)
+    affine = _gn_records(launch.descs, ys, groups) if fusable else None
+    launch.launch()
     if affine is None:
         return ys, groupnorm_affine_multi([y.t for y in ys], gamma, beta, groups, eps)
-    return ys, affine(0, n, gamma, beta, eps)
+    return ys, affine(0, len(xs), gamma, beta, eps)
 
 
 def conv_gn_multi_pair(xs_a: Sequence[View], pc_a: PackedConv, gn_a, xs_b: Sequence[View], pc_b: PackedConv, gn_b, groups: int = 32, eps: float = 1e-5,
@@ -642,44 +650,34 @@ def conv_gn_multi_pair(xs_a: Sequence[View], pc_a: PackedConv, gn_a, xs_b: Seque
     the two towers separately).  Returns ((ys_a, affine_a), (ys_b, affine_b)) like two conv_gn_multi calls."""
     na, nb = len(xs_a), len(xs_b)
     n = na + nb
-    if not PAIR_TOWERS:
-        return None
-    if na != nb or n > 10 or pc_a.cout != pc_b.cout or pc_a.cin_pad != pc_b.cin_pad:
+    if not PAIR_TOWERS or na != nb or n > 10 or pc_a.cout != pc_b.cout or pc_a.cin_pad != pc_b.cin_pad or not _gn_fusable(xs_a, pc_a.cout, groups):
         return None
     if (in_affine_a is None) != (in_affine_b is None) or any(tuple(a.t.shape) != tuple(b.t.shape) for a, b in zip(xs_a, xs_b)):
         return None
-    if not _gn_fusable(xs_a, pc_a.cout, groups):
-        return None
     xs, pcs = list(xs_a) + list(xs_b), [pc_a] * na + [pc_b] * nb
-    affs = (list(in_affine_a) + list(in_affine_b)) if in_affine_a is not None else None
-    ys = [View(torch.empty((x.t.shape[0], x.t.shape[1], x.t.shape[2], pc_a.cout), dtype=torch.float32, device=x.t.device)) for x in xs]
-    descs = (ConvDesc * n)()
-    for i in range(n):
-        _fill_desc(descs[i], xs[i], pcs[i], ys[i], False, None, None, False, False, affs[i] if affs is not None else None)
+    ys = _new_outputs(xs, pc_a)
+    launch = _ConvLaunch(xs, pcs, ys, in_affine=(list(in_affine_a) + list(in_affine_b)) if in_affine_a is not None else None)
     # the variant of ONE tower's launch (the table is keyed by the 5 level shapes, problems 0..na-1) decides; the 10-problem launch has no
     # entry of its own and is not timed by the tuner
-    tv, _ = _apply_tuning(descs, na, _problem_key(descs, na), with_gn_stats=True, tune=False)
-    wino6 = tv[0] == 6 and tv[2] == 1 and pc_a.w_wino6 is not None and pc_b.w_wino6 is not None
-    sp3 = tv[0] == 11 and pc_a.w_splith is not None and pc_b.w_splith is not None      # opt-in direct fp16-split form
-    if tv[3] > 1 or not (wino6 or sp3):
+    v = launch.choose(first=na, with_gn_stats=True)
+    wino6 = v.wm == 6 and v.wn == 1 and pc_a.w_wino6 is not None and pc_b.w_wino6 is not None
+    sp3 = v.wm == 11 and pc_a.w_splith is not None and pc_b.w_splith is not None      # opt-in direct fp16-split form
+    if v.splitk > 1 or not (wino6 or sp3):
         return None
-    _set_variant(descs, n, tv)
-    affine = _gn_records(descs, ys, groups)
-    _launch(descs, n, None, xs, ys, pcs, what="cmk_conv2d_nhwc_multi (tower pair)")
+    launch.set(v._replace(tail=0))          # all 2 x levels problems; a launch of several problems has no tail
+    affine = _gn_records(launch.descs, ys, groups)
+    launch.launch("cmk_conv2d_nhwc_multi (tower pair)")
     return (ys[:na], affine(0, na, gn_a[0], gn_a[1], eps)), (ys[na:], affine(na, n, gn_b[0], gn_b[1], eps))
 
 
 def conv_out_multi(xs: Sequence[View], pcs: Sequence[PackedConv], **kw) -> List[View]:  # kw: relu, relu_upto, in_affine
-    ys = [View(torch.empty((x.t.shape[0], x.t.shape[1], x.t.shape[2], pcs[0].cout), dtype=torch.float32, device=x.t.device)) for x in xs]
+    ys = _new_outputs(xs, pcs[0])
     conv2d_multi(xs, pcs, ys, **kw)
     return ys
 
 
 def conv_out(x: View, pc: PackedConv, **kw) -> View:
-    n, h, w = x.nhw
-    ho = h if pc.stride == 1 else (h - 1) // 2 + 1
-    wo = w if pc.stride == 1 else (w - 1) // 2 + 1
-    y = View(torch.empty((n, ho, wo, pc.cout), dtype=torch.float32, device=x.t.device))
+    y, = _new_outputs([x], pc)
     conv2d(x, pc, y, **kw)
     return y
 

@@ -323,12 +323,13 @@ def fill_descs(c, _lib, ptr=None, bufs=None, ops=None):
                 d.in_scale = d.in_shift = ptr
             d.tune_wm, d.tune_sc, d.tune_wn = c["tv"][:3]
             d.gn_groups, d.gn_ws = c["gn_groups"], (ptr if c["gn_groups"] else None)
+        from centermask2_amd.ops import Variant
         d = descs[0]
-        tv = c["tv"]
-        if len(tv) > 3 and tv[3] > 1:
-            d.splitk, d.splitk_ws = tv[3], ptr
-        if len(tv) > 4 and tv[4] > 1:
-            d.splitk_tail, d.splitk_ws, d.splitk_tail_tiles = tv[4], ptr, c["tail_tiles"]
+        v = Variant.of(c["tv"])
+        if v.splitk > 1:
+            d.splitk, d.splitk_ws = v.splitk, ptr
+        if v.tail:
+            d.splitk_tail, d.splitk_ws, d.splitk_tail_tiles = v.tail, ptr, c["tail_tiles"]
         if c["pool"]:
             d.pool_ws = ptr
         return descs
@@ -338,12 +339,7 @@ def fill_descs(c, _lib, ptr=None, bufs=None, ops=None):
         res = View(bufs["res"][i], c["res_view"][1] if c["res_view"] else 0, c["cout"]) if c["res_mode"] else None
         ops._fill_desc(descs[i], bufs["xv"][i], bufs["pcs"][i], bufs["yv"][i], False, relu_upto, res, c["res_mode"] == 2, c["in_relu"],
                        bufs["aff"][i] if c["in_affine"] else None)
-    old_tail = ops.TAIL_TILES
-    ops.TAIL_TILES = c["tail_tiles"]
-    try:
-        ws = ops._set_variant(descs, n, c["tv"])
-    finally:
-        ops.TAIL_TILES = old_tail
+    ws = ops._set_variant(descs, n, c["tv"], c["tail_tiles"])
     keep = {"ws": ws, "pool": None, "gn": None, "affine": None}
     if ws is not None:
         ws.fill_(float("nan"))            # a slab the kernel leaves unwritten and the reduce reads shows in the output; a refusal leaves all of it

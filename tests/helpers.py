@@ -83,6 +83,34 @@ def build_gpu_model(conv_body="V-39-eSE", seed=0):
     return model, sd
 
 
+def raw_conv(x, pc, y, variant=None, relu=False, relu_upto=None, res=None, res_upsample=False, in_relu=False, in_affine=None, gn=None,
+             launch=True):
+    """One conv launch through the C ABI on descriptors filled as the wrappers of ops.py fill them, with the tile variant (wm, sc, wn[, splitk[,
+    tail ways]]; None = the library's default) written into them as the tuner does.  x, pc, y (and in_affine): one problem, or lists of them
+    for the _multi entry.  gn = (workspace, groups) of the fused GroupNorm records.  Returns (rc, descs, keep): the library's return code after
+    a synchronize (None with launch=False: fill only, for tests that ask about the descriptor or change it first — cmk_conv_pool_rows and
+    pool_ws — and then relaunch), the descriptors, and what they borrow pointers of (keep["ws"]: the split-K or tail workspace, or None)."""
+    from centermask2_amd import _lib, ops
+    xs, pcs, ys, affs = (x, pc, y, in_affine) if isinstance(x, (list, tuple)) else ([x], [pc], [y], [in_affine])
+    descs = (_lib.ConvDesc * len(xs))()
+    for i, d in enumerate(descs):
+        ops._fill_desc(d, xs[i], pcs[i], ys[i], relu, relu_upto, res, res_upsample, in_relu, affs[i] if affs is not None else None)
+        if gn is not None:
+            d.gn_ws, d.gn_groups = gn[0].data_ptr(), gn[1]
+    keep = {"ws": ops._set_variant(descs, len(xs), variant) if variant is not None else None, "tensors": (xs, pcs, ys, res, affs, gn)}
+    return (relaunch(descs) if launch else None), descs, keep
+
+
+def relaunch(descs):
+    """Launch filled conv descriptors (cmk_conv2d_nhwc for one, else the _multi entry) on the current stream and wait; returns the library's code."""
+    import ctypes
+    from centermask2_amd import _lib, ops
+    lib, n = _lib.load(), len(descs)
+    rc = lib.cmk_conv2d_nhwc(ctypes.byref(descs[0]), ops._stream()) if n == 1 else lib.cmk_conv2d_nhwc_multi(descs, n, ops._stream())
+    torch.cuda.synchronize()
+    return rc
+
+
 def load_shipped_variant_table():
     """The measured conv variant table bench.py uses (Winograd where it wins), so parity is checked on the same kernels."""
     from centermask2_amd import ops

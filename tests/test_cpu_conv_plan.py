@@ -1,5 +1,5 @@
 """cmk_conv_plan, the library's own account of a conv launch (kernel name, executed FLOPs, fused-GroupNorm records), against the answers the
-Python mirrors it replaced gave at the last commit that had them (tests/golden/conv_plan_cases.json, written by make_conv_plan_cases.py):
+Python mirrors it replaced gave at the last commit that had them (tests/golden/conv_plan_cases.json; DESIGN.md, "The plan golden", says how it was recorded):
 every (key, variant) of the shipped tables and the start-up tuner's whole menu on tiny problems, refusals with their text.  No GPU: dummy
 aligned pointers, nothing is launched."""
 import ctypes

@@ -187,6 +187,56 @@ def test_shipped_variant_tables_name_existing_kernels(tmp_path):
         ops._TUNED.update(saved)
 
 
+# spelling of a conv tile variant -> (ops.Variant, the stored form, ops._variant5: a tuner candidate's name in TUNE_LOG).  A tail of 0 or 1 ways
+# means off; a split-K of 1 is dropped from the stored form only when there is no tail; a candidate's name always carries its split-K.
+VARIANT_FORMS = [
+    ((1, 16, 2),       (1, 16, 2, 1, 0), (1, 16, 2),       (1, 16, 2, 1)),
+    ((1, 16, 2, 1),    (1, 16, 2, 1, 0), (1, 16, 2),       (1, 16, 2, 1)),
+    ((8, 32, 2, 8),    (8, 32, 2, 8, 0), (8, 32, 2, 8),    (8, 32, 2, 8)),
+    ((6, 16, 2, 1, 4), (6, 16, 2, 1, 4), (6, 16, 2, 1, 4), (6, 16, 2, 1, 4)),
+    ((6, 16, 2, 1, 0), (6, 16, 2, 1, 0), (6, 16, 2),       (6, 16, 2, 1)),
+    ((6, 16, 2, 1, 1), (6, 16, 2, 1, 0), (6, 16, 2),       (6, 16, 2, 1)),
+    ([0, 0, 0],        (0, 0, 0, 1, 0),  (0, 0, 0),        (0, 0, 0, 1)),
+    ((0, 0, 0, 4),     (0, 0, 0, 4, 0),  (0, 0, 0, 4),     (0, 0, 0, 4)),
+]
+
+
+@pytest.mark.parametrize("spelling,canonical,stored,candidate", VARIANT_FORMS, ids=[str(f[0]).replace(" ", "") for f in VARIANT_FORMS])
+def test_conv_variant_forms(spelling, canonical, stored, candidate):
+    from centermask2_amd import ops
+    v = ops.Variant.of(spelling)
+    assert tuple(v) == canonical and (v.wm, v.sc, v.wn, v.splitk, v.tail) == canonical
+    assert v.stored() == stored and type(v.stored()) is tuple
+    assert ops.Variant.of(v) == v and ops.Variant.of(stored) == v and ops.Variant.of(list(canonical)) == v
+    assert ops._variant5(spelling) == candidate == v.stored(4) and type(ops._variant5(spelling)) is tuple
+
+
+@pytest.mark.parametrize("name", sorted(n for n in os.listdir(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "centermask2_amd", "tuned"))
+                                        if n.endswith(".json")))
+def test_tuned_table_round_trip(name, tmp_path):
+    """load_tuned then save_tuned writes, byte for byte, the file's admitted entries as lists under sorted keys with indent 0, and _TUNED
+    holds plain tuples in between (bench.py indexes and assigns them as such)."""
+    import json
+    from centermask2_amd import ops
+    path = os.path.join(os.path.dirname(ops.__file__), "tuned", name)
+    with open(path) as f:
+        table = json.load(f)
+    admitted = {k: v for k, v in table.items() if ops._variant_on_menu(v)}
+    saved = dict(ops._TUNED)
+    try:
+        ops._TUNED.clear()
+        assert ops.load_tuned(path) == len(admitted)
+        assert ops._TUNED == {ops._str_to_key(k): tuple(v) for k, v in admitted.items()}
+        assert all(type(v) is tuple for v in ops._TUNED.values())
+        ops.save_tuned(str(tmp_path / "saved.json"))
+    finally:
+        ops._TUNED.clear()
+        ops._TUNED.update(saved)
+    with open(str(tmp_path / "expected.json"), "w") as f:
+        json.dump({k: list(v) for k, v in sorted(admitted.items())}, f, indent=0)
+    assert (tmp_path / "saved.json").read_bytes() == (tmp_path / "expected.json").read_bytes()
+
+
 def test_bin_sextuple_fixture_from_the_reference(tmp_path):
     """tests/golden/bin/000000000139_{1..6}.bin: written from the tuple of the reference's own single_flatten_to_tuple and read back by
     its own reader steps (tests/golden/make_golden_bin.py).  wire.from_bin must parse them to the same tensors, wire.to_bin must write

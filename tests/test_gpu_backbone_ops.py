@@ -1,11 +1,15 @@
 """-m gpu: HIP kernels of the backbone/towers through the C ABI vs the oracle's torch fp32 ops (same seeded inputs).
 Tolerance: fp32 logits/features within 1e-3 ABSOLUTE (north_star) and, for single ops, also within 2e-4 * max(1, max|ref|)."""
+import ctypes
+
 import pytest
 import torch
 import torch.nn.functional as F
 
-from centermask2_amd import ops
+from centermask2_amd import _lib, ops
 from centermask2_amd.ops import View
+
+from .helpers import raw_conv, relaunch
 
 pytestmark = pytest.mark.gpu
 
@@ -21,6 +25,16 @@ def _close(got, ref, rel=2e-4):
     err = (got - ref).abs().max().item()
     bound = min(1e-3, rel * max(1.0, ref.abs().max().item()))      # never looser than north_star's absolute 1e-3
     assert err <= bound, "max abs err {} > {}".format(err, bound)
+
+
+def _problem(n, cin, h, w, cout, seed, k=3, stride=1, relu=True):
+    """x, He-scaled weights, scale in [0.5, 1.5), shift and torch's (relu of) conv * scale + shift on the CPU, from seeds seed .. seed + 3."""
+    x = _rand((n, cin, h, w), seed)
+    wt = _rand((cout, cin, k, k), seed + 1, (2.0 / (cin * k * k)) ** 0.5)
+    scale = torch.rand(cout, generator=torch.Generator().manual_seed(seed + 2)) + 0.5
+    shift = _rand((cout,), seed + 3, 0.1)
+    ref = F.conv2d(x, wt, None, stride=stride, padding=k // 2) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+    return x, wt, scale, shift, F.relu(ref) if relu else ref
 
 
 CONV_CASES = [
@@ -44,11 +58,7 @@ CONV_CASES = [
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv_igemm_matches_torch(dev, case):
     n, h, w, cin, cout, k, stride = case
-    x = _rand((n, cin, h, w), 1)
-    wt = _rand((cout, cin, k, k), 2, (2.0 / (cin * k * k)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(3)) + 0.5
-    shift = _rand((cout,), 4, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None, stride=stride, padding=k // 2) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 1, k, stride=stride)
     pc = ops.PackedConv(wt, scale, shift, dev, stride=stride)
     xv = ops.as_view(x.to(dev))
     y = ops.conv_out(xv, pc, relu=True)
@@ -215,20 +225,10 @@ def test_conv_multi_level_launch(dev):
 
 def _run_variant(dev, x, wt, scale, shift, tv, stride=1, relu=True):
     """One conv through the C ABI with the tile variant written into the descriptor (cmk_conv_desc.tune_*), as the tuner does."""
-    import ctypes
-    from centermask2_amd import _lib
     pc = ops.PackedConv(wt, scale, shift, dev, stride=stride)
-    xv = ops.as_view(x.to(dev))
     n, _, h, w = x.shape
-    ho, wo = (h, w) if stride == 1 else ((h - 1) // 2 + 1, (w - 1) // 2 + 1)
-    y = View(torch.full((n, ho, wo, wt.shape[0]), -5.0, device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], xv, pc, y, relu, None, None, False, False)
-    ws = ops._set_variant(d, 1, tv)
-    rc = _lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream())
-    torch.cuda.synchronize()
-    del ws
-    return rc, y
+    y = View(torch.full((n,) + ops._out_hw(h, w, stride) + (wt.shape[0],), -5.0, device=dev))
+    return raw_conv(ops.as_view(x.to(dev)), pc, y, tv, relu=relu)[0], y
 
 
 DIRECT_VARIANT_SHAPES = [(2, 37, 45, 64, 128), (1, 20, 70, 32, 96), (1, 9, 33, 48, 160), (1, 17, 23, 64, 192), (1, 11, 19, 32, 224)]
@@ -240,11 +240,7 @@ def test_conv_direct_tile_variants(dev, wm, sc):
     the real knob (the descriptor's tune_* fields).  The start-up tuner may pick any of them, so each must be right by itself."""
     ran = set()
     for (n, h, w, cin, cout) in DIRECT_VARIANT_SHAPES:
-        x = _rand((n, cin, h, w), 31)
-        wt = _rand((cout, cin, 3, 3), 32, (2.0 / (cin * 9)) ** 0.5)
-        scale = torch.rand(cout, generator=torch.Generator().manual_seed(33)) + 0.5
-        shift = _rand((cout,), 34, 0.1)
-        ref = F.relu(F.conv2d(x, wt, None, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+        x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 31)
         for wn in range(1, 8):
             rc, y = _run_variant(dev, x, wt, scale, shift, (wm, sc, wn))
             if rc != 0:
@@ -277,11 +273,7 @@ def test_conv_pointwise_kernel(dev, case, mt):
     """conv_pw (tune_wm 8): the 1x1 GEMM kernel with the weights fetched straight into registers, both workgroup heights; ragged pixel
     counts, Cout that is not a multiple of the 128-cout tile; equal to conv_igemm bit for bit (same K and accumulation order)."""
     n, h, w, cin, cout = case
-    x = _rand((n, cin, h, w), 61)
-    wt = _rand((cout, cin, 1, 1), 62, (2.0 / cin) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(63)) + 0.5
-    shift = _rand((cout,), 64, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 61, 1)
     rc, y = _run_variant(dev, x, wt, scale, shift, (8, 32, mt))
     assert rc == 0
     _close(y.nchw(), ref)
@@ -291,8 +283,6 @@ def test_conv_pointwise_kernel(dev, case, mt):
 
 def test_conv_pointwise_kernel_views_residual_partial_relu(dev, cmk_lib):
     """Channel views on both sides, a same-size residual, ReLU on the first channels only; then the requests the kernel refuses."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout = 2, 17, 19, 64, 288
     big = _rand((n, h, w, 160), 65).to(dev)
     wt = _rand((cout, cin, 1, 1), 66, 0.1)
@@ -303,11 +293,7 @@ def test_conv_pointwise_kernel_views_residual_partial_relu(dev, cmk_lib):
     ref[:, :100] = F.relu(ref[:, :100])
     for mt in (4, 2):
         out = torch.full((n, h, w, 400), -7.0, device=dev)
-        d = (_lib.ConvDesc * 1)()
-        ops._fill_desc(d[0], View(big, 32, cin), pc, View(out, 64, cout), False, 100, View(res, 16, cout), False, False)
-        d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 8, 32, mt
-        assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) == 0, cmk_lib.cmk_last_error()
-        torch.cuda.synchronize()
+        assert raw_conv(View(big, 32, cin), pc, View(out, 64, cout), (8, 32, mt), relu_upto=100, res=View(res, 16, cout))[0] == 0, cmk_lib.cmk_last_error()
         _close(out[..., 64:64 + cout].permute(0, 3, 1, 2), ref)
         assert float(out[..., :64].max()) == -7.0 and float(out[..., 64 + cout:].min()) == -7.0   # neighbours untouched
     # refused: a 3x3 conv, Cout <= 224, Cin % 32 != 0, a tile height that does not exist
@@ -324,27 +310,18 @@ def test_conv_pointwise_pooled_sums_and_ese_gate(dev, cmk_lib, case):
     """The aggregation conv's fused average-pool partial sums (cmk_conv_desc.pool_ws) and the eSE gate made from them: images whose pixel
     count is not a multiple of the block (records split at the image boundary), a ragged last block, Cout that is not a multiple of 128.
     Reference: torch mean over the conv output and the reference's hsigmoid(fc(mean)) (vovnet.py:247-260)."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout, mt = case
-    x = _rand((n, cin, h, w), 81)
-    wt = _rand((cout, cin, 1, 1), 82, (2.0 / cin) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(83)) + 0.5
-    shift = _rand((cout,), 84, 0.1)
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 81, 1)
     fc_w, fc_b = _rand((cout, cout), 85, 0.05), _rand((cout,), 86, 0.5)
-    ref = F.relu(F.conv2d(x, wt, None) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
     ref_gate = F.relu6(F.linear(ref.mean(dim=(2, 3)), fc_w, fc_b) + 3.0) / 6.0
     pc = ops.PackedConv(wt, scale, shift, dev)
     y = View(torch.full((n, h, w, cout), -5.0, device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], ops.as_view(x.to(dev)), pc, y, True, None, None, False, False)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 8, 32, mt
+    _, d, keep = raw_conv(ops.as_view(x.to(dev)), pc, y, (8, 32, mt), relu=True, launch=False)
     rows = cmk_lib.cmk_conv_pool_rows(ctypes.byref(d[0]))
     assert rows == 32 * mt
     pws = torch.full((2 * (-(-(n * h * w) // rows)), cout), float("nan"), device=dev)
     d[0].pool_ws = pws.data_ptr()
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) == 0, cmk_lib.cmk_last_error()
-    torch.cuda.synchronize()
+    assert relaunch(d) == 0, cmk_lib.cmk_last_error()
     _close(y.nchw(), ref)
     assert bool(torch.isfinite(pws).all())                       # every record is written
     _close(pws.sum(0) / (n * h * w), ref.mean(dim=(0, 2, 3)), rel=1e-5)
@@ -354,7 +331,7 @@ def test_conv_pointwise_pooled_sums_and_ese_gate(dev, cmk_lib, case):
     # a conv the pointwise kernel does not run: no pooled sums on offer, and asking for them anyway is an error
     d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 1, 32, 2
     assert cmk_lib.cmk_conv_pool_rows(ctypes.byref(d[0])) == 0
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) != 0
+    assert relaunch(d) != 0
 
 
 @pytest.mark.parametrize("mt", [4, 2])
@@ -364,11 +341,7 @@ def test_conv_pointwise_gather_form(dev, case, mt):
     bounds-checked loads — odd sizes (every border case of the padding), ragged pixel counts, Cout that is not a multiple of 128.  Same K
     order (tap-major) as conv_igemm's gather form: bit-identical to it."""
     n, h, w, cin, cout, stride = case
-    x = _rand((n, cin, h, w), 91)
-    wt = _rand((cout, cin, 3, 3), 92, (2.0 / (9 * cin)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(93)) + 0.5
-    shift = _rand((cout,), 94, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None, stride=stride, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 91, stride=stride)
     rc, y = _run_variant(dev, x, wt, scale, shift, (9, 32, mt), stride=stride)
     assert rc == 0
     _close(y.nchw(), ref)
@@ -382,8 +355,6 @@ def test_conv_pointwise_upsampled_residual(dev, cmk_lib, case, mt):
     """The FPN lateral with the top-down add on the pointwise kernel (tune_wm 8 with res_mode 2): residual = nearest 2x upsampling of a
     map of half the size (odd heights: the coarse map has ceil(H/2) rows), ragged last tile, Cout that is not a multiple of 128; an odd
     width is refused (conv_igemm keeps it)."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout = case
     x = _rand((n, cin, h, w), 101)
     wt = _rand((cout, cin, 1, 1), 102, (2.0 / cin) ** 0.5)
@@ -394,21 +365,14 @@ def test_conv_pointwise_upsampled_residual(dev, cmk_lib, case, mt):
     ref = F.conv2d(x, wt, shift) + up
     pc = ops.PackedConv(wt, None, shift, dev)
     y = View(torch.full((n, h, w, cout), -5.0, device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], ops.as_view(x.to(dev)), pc, y, False, None, View(res, 8, cout), True, False)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 8, 32, mt
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) == 0, cmk_lib.cmk_last_error()
-    torch.cuda.synchronize()
+    assert raw_conv(ops.as_view(x.to(dev)), pc, y, (8, 32, mt), res=View(res, 8, cout), res_upsample=True)[0] == 0, cmk_lib.cmk_last_error()
     _close(y.nchw(), ref)
     # odd width: refused
     x2 = _rand((1, 32, 6, 9), 105)
     y2 = View(torch.empty((1, 6, 9, 256), device=dev))
     pc2 = ops.PackedConv(_rand((256, 32, 1, 1), 106), None, None, dev)
     res2 = View(torch.zeros((1, 3, 5, 256), device=dev))
-    d2 = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d2[0], ops.as_view(x2.to(dev)), pc2, y2, False, None, res2, True, False)
-    d2[0].tune_wm, d2[0].tune_sc, d2[0].tune_wn = 8, 32, mt
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d2[0]), ops._stream()) != 0
+    assert raw_conv(ops.as_view(x2.to(dev)), pc2, y2, (8, 32, mt), res=res2, res_upsample=True)[0] != 0
 
 
 @pytest.mark.parametrize("case", [(1, 1, 37, 12544, 1024, 1, 1, (8, 32, 2, 8)), (1, 1, 400, 1024, 1024, 1, 1, (8, 32, 4, 2)), (6, 14, 14, 256, 256, 3, 2, (9, 32, 2, 4)),
@@ -416,11 +380,7 @@ def test_conv_pointwise_upsampled_residual(dev, cmk_lib, case, mt):
 def test_conv_pointwise_split_k(dev, case):
     """Split-K on the pointwise kernel (both the 1x1 and the gather form): raw partial sums + the reduce kernel of conv.hip."""
     n, h, w, cin, cout, k, stride, tv = case
-    x = _rand((n, cin, h, w), 111)
-    wt = _rand((cout, cin, k, k), 112, (2.0 / (cin * k * k)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(113)) + 0.5
-    shift = _rand((cout,), 114, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None, stride=stride, padding=k // 2) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 111, k, stride=stride)
     rc, y = _run_variant(dev, x, wt, scale, shift, tv, stride=stride)
     assert rc == 0
     _close(y.nchw(), ref)
@@ -435,11 +395,7 @@ def test_conv_winograd6_variant(dev, case):
     """Fused Winograd F(4x4,3x3) kernel (tune_wm 6) against torch: exact tiles, ragged edges in both directions, maps smaller than a
     tile, Cout not a multiple of 32, Cin not a multiple of 32.  fp32 rounding differences only (tolerance as for every conv here)."""
     n, h, w, cin, cout = case
-    x = _rand((n, cin, h, w), 81)
-    wt = _rand((cout, cin, 3, 3), 82, (2.0 / (cin * 9)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(83)) + 0.5
-    shift = _rand((cout,), 84, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 81)
     rc, y = _run_variant(dev, x, wt, scale, shift, (6, 16, 1))
     assert rc == 0
     _close(y.nchw(), ref)
@@ -460,11 +416,7 @@ def test_conv_winograd6_split_k(dev, case):
     workgroups with hundreds of input channels (the first conv of a stage-4 / stage-5 OSA block).  fp32 rounding differences only;
     chunk counts that do not split evenly and the shared-V form are refused."""
     n, h, w, cin, cout, sk = case
-    x = _rand((n, cin, h, w), 181)
-    wt = _rand((cout, cin, 3, 3), 182, (2.0 / (cin * 9)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(183)) + 0.5
-    shift = _rand((cout,), 184, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 181)
     rc, y = _run_variant(dev, x, wt, scale, shift, (6, 16, 1, sk))
     assert rc == 0
     _close(y.nchw(), ref)
@@ -481,11 +433,7 @@ def test_conv_winograd6_roi_pair_geometry(dev, case):
     """tune_wm 6 / tune_wn 2: two whole RoI maps (at most 16 rows x 14 columns) per workgroup — even and odd batch, the 272-channel
     mask-IoU input, maps smaller than 14x14, Cout not a multiple of 32."""
     n, h, w, cin, cout = case
-    x = _rand((n, cin, h, w), 91)
-    wt = _rand((cout, cin, 3, 3), 92, (2.0 / (cin * 9)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(93)) + 0.5
-    shift = _rand((cout,), 94, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 91)
     rc, y = _run_variant(dev, x, wt, scale, shift, (6, 16, 2))
     assert rc == 0
     _close(y.nchw(), ref)
@@ -502,18 +450,12 @@ def test_conv_winograd6_roi_pair_geometry(dev, case):
 @pytest.mark.parametrize("sc", [16, 64])
 def test_conv_winograd6_channel_views(dev, sc):
     """tune_wm 6 reading a channel slice of a wider buffer (an OSA concat buffer) and writing into a slice of another; partial ReLU."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout = 2, 23, 47, 64, 48
     big = _rand((n, h, w, 160), 5).to(dev)
     wt = _rand((cout, cin, 3, 3), 6, 0.06)
     out = torch.full((n, h, w, 96), -7.0, device=dev)
     pc = ops.PackedConv(wt, None, _rand((cout,), 8, 0.1), dev)
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], View(big, 32, cin), pc, View(out, 16, cout), False, 4, None, False, False)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 6, sc, 1
-    _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "wino6 views")
-    torch.cuda.synchronize()
+    _lib.check(raw_conv(View(big, 32, cin), pc, View(out, 16, cout), (6, sc, 1), relu_upto=4)[0], "wino6 views")
     ref = F.conv2d(big[..., 32:96].permute(0, 3, 1, 2).cpu(), wt, pc.shift.cpu(), padding=1)
     ref[:, :4] = F.relu(ref[:, :4])
     _close(out[..., 16:64].permute(0, 3, 1, 2), ref)
@@ -523,22 +465,10 @@ def test_conv_winograd6_channel_views(dev, sc):
 @pytest.mark.parametrize("case", [(2, 37, 45, 64, 128), (1, 16, 16, 256, 256), (1, 25, 40, 224, 224), (2, 14, 14, 256, 80), (1, 100, 160, 32, 5)])
 def test_conv_winograd_variant(dev, case):
     """Fused Winograd F(2x2,3x3) kernel (tune_wm 5) against torch; fp32 rounding differences only."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout = case
-    x = _rand((n, cin, h, w), 81)
-    wt = _rand((cout, cin, 3, 3), 82, (2.0 / (cin * 9)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(83)) + 0.5
-    shift = _rand((cout,), 84, 0.1)
-    ref = F.relu(F.conv2d(x, wt, None, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
-    pc = ops.PackedConv(wt, scale, shift, dev)
-    xv = ops.as_view(x.to(dev))
-    y = View(torch.full((n, h, w, cout), -5.0, device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], xv, pc, y, True, None, None, False, False)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 5, 16, 2
-    _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "wino")
-    torch.cuda.synchronize()
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 81)
+    rc, y = _run_variant(dev, x, wt, scale, shift, (5, 16, 2))
+    _lib.check(rc, "wino")
     _close(y.nchw(), ref)
 
 
@@ -557,14 +487,8 @@ GATHER_SPLITK_CASES = [
 
 @pytest.mark.parametrize("case", GATHER_SPLITK_CASES)
 def test_conv_gather_form_and_split_k(dev, case):
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout, k, stride, tv, with_res = case
-    x = _rand((n, cin, h, w), 61)
-    wt = _rand((cout, cin, k, k), 62, (2.0 / (cin * k * k)) ** 0.5)
-    scale = torch.rand(cout, generator=torch.Generator().manual_seed(63)) + 0.5
-    shift = _rand((cout,), 64, 0.1)
-    ref = F.conv2d(x, wt, None, stride=stride, padding=k // 2) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+    x, wt, scale, shift, ref = _problem(n, cin, h, w, cout, 61, k, stride=stride, relu=False)
     res = _rand(tuple(ref.shape), 65) if with_res else None
     if with_res:
         ref = ref + res
@@ -573,36 +497,23 @@ def test_conv_gather_form_and_split_k(dev, case):
     pc.w_wino = None                                   # keep the default on the direct kernels
     xv = ops.as_view(x.to(dev))
     y = View(torch.full((n, ref.shape[2], ref.shape[3], cout), -5.0, device=dev))
-    d = (_lib.ConvDesc * 1)()
-    resv = ops.as_view(res.to(dev)) if with_res else None      # the descriptor only borrows the pointer: keep the tensor alive
-    ops._fill_desc(d[0], xv, pc, y, True, None, resv, False, False)
-    ws = ops._set_variant(d, 1, tv)
-    _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "gather/split-K")
-    torch.cuda.synchronize()
-    del ws
+    _lib.check(raw_conv(xv, pc, y, tv, relu=True, res=ops.as_view(res.to(dev)) if with_res else None)[0], "gather/split-K")
     _close(y.nchw(), ref)
 
 
 def test_conv_split_k_rejects_bad_requests(dev, cmk_lib):
-    import ctypes
-    from centermask2_amd import _lib
     x = ops.as_view(_rand((1, 48, 8, 8), 1).to(dev))
     pc = ops.PackedConv(_rand((32, 48, 1, 1), 2), None, None, dev)
     y = View(torch.empty((1, 8, 8, 32), device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], x, pc, y, False, None, None, False, False)
-    ws = ops._set_variant(d, 1, (0, 0, 0, 2))          # 3 K chunks are not divisible by 2*2
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) != 0 and b"split-K" in cmk_lib.cmk_last_error()
+    rc, d, keep = raw_conv(x, pc, y, (0, 0, 0, 2))     # 3 K chunks are not divisible by 2*2
+    assert rc != 0 and b"split-K" in cmk_lib.cmk_last_error()
     d[0].splitk, d[0].splitk_ws = 2, None              # no workspace
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) != 0
-    del ws
+    assert relaunch(d) != 0
 
 
 @pytest.mark.parametrize("variant", [(0, 0, 0), (5, 16, 2), (6, 16, 1), (6, 64, 1), (1, 16, 1)])
 def test_conv_fused_groupnorm_relu_input(dev, variant):
     """conv(relu(GroupNorm(x))) with the GN apply fused into the conv's input staging (direct kernels and Winograd form 6)."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, c, cout = 2, 25, 40, 256, 80
     x = _rand((n, c, h, w), 91, 2.0) + 0.7
     gamma = torch.rand(c, generator=torch.Generator().manual_seed(92)) + 0.5
@@ -614,14 +525,11 @@ def test_conv_fused_groupnorm_relu_input(dev, variant):
     aff = ops.groupnorm_affine(xv.t, gamma.to(dev), beta.to(dev))
     pc = ops.PackedConv(wt, None, bias, dev)
     y = View(torch.empty((n, h, w, cout), device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], xv, pc, y, False, None, None, False, False, aff)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = variant
-    _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "conv+gn")
-    torch.cuda.synchronize()
+    rc, d, keep = raw_conv(xv, pc, y, variant, in_affine=aff)
+    _lib.check(rc, "conv+gn")
     _close(y.nchw(), ref)
     d[0].tune_wm = 4          # the Winograd form without the fused affine must refuse rather than ignore it
-    assert _lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) != 0
+    assert relaunch(d) != 0
 
 
 @pytest.mark.parametrize("form", [5, 6, 664])
@@ -655,6 +563,19 @@ def test_conv_with_fused_groupnorm_statistics(dev, cout, groups, form, monkeypat
         _close(sh, ref_sh, 1e-4)
 
 
+def _tower_pair(dev, shapes, c, with_affine):
+    """Seeded inputs of a tower pair launch over level shapes (N, H, W), c -> c channels: two packed 3x3 convs, two GroupNorm (gamma, beta),
+    the levels' inputs and, with_affine, the fused input affines of both towers (else None, None)."""
+    g = torch.Generator().manual_seed(77)
+    wts = [torch.randn((c, c, 3, 3), generator=g) * (2.0 / (c * 9)) ** 0.5 for _ in range(2)]
+    pca, pcb = [ops.PackedConv(w, None, torch.randn((c,), generator=g) * 0.1, dev) for w in wts]
+    gn = [((torch.rand((c,), generator=g) + 0.5).to(dev), (torch.randn((c,), generator=g) * 0.1).to(dev)) for _ in range(2)]
+    xs = [ops.as_view(torch.randn((n, c, h, w), generator=g).to(dev)) for n, h, w in shapes]
+    affs = [[((torch.rand((n, c), generator=g) + 0.5).to(dev), (torch.randn((n, c), generator=g) * 0.2).to(dev)) for n, _, _ in shapes]
+            for _ in range(2)] if with_affine else [None, None]
+    return pca, pcb, gn, xs, affs[0], affs[1]
+
+
 @pytest.mark.parametrize("sc", [16, 64])
 @pytest.mark.parametrize("with_affine", [False, True])
 def test_tower_pair_launch_equals_two_launches(dev, sc, with_affine, monkeypatch):
@@ -662,20 +583,8 @@ def test_tower_pair_launch_equals_two_launches(dev, sc, with_affine, monkeypatch
     in the F(4x4) kernels) — outputs and GroupNorm affines bit-identical to two conv_gn_multi launches, with and without the fused input
     affine of the previous GroupNorm."""
     monkeypatch.setattr(ops, "FORCE_VARIANT", (6, sc, 1))
-    g = torch.Generator().manual_seed(77)
-    shapes = [(2, 20, 36), (2, 9, 17), (2, 5, 3), (2, 3, 2), (2, 1, 1)]
-    cin = cout = 64
     groups = 32
-    wa = torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (cin * 9)) ** 0.5
-    wb = torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (cin * 9)) ** 0.5
-    pca = ops.PackedConv(wa, None, torch.randn((cout,), generator=g) * 0.1, dev)
-    pcb = ops.PackedConv(wb, None, torch.randn((cout,), generator=g) * 0.1, dev)
-    gn = [((torch.rand((cout,), generator=g) + 0.5).to(dev), (torch.randn((cout,), generator=g) * 0.1).to(dev)) for _ in range(2)]
-    xs = [ops.as_view(torch.randn((n, cin, h, w), generator=g).to(dev)) for n, h, w in shapes]
-    aff_a = aff_b = None
-    if with_affine:
-        aff_a = [((torch.rand((n, cin), generator=g) + 0.5).to(dev), (torch.randn((n, cin), generator=g) * 0.2).to(dev)) for n, _, _ in shapes]
-        aff_b = [((torch.rand((n, cin), generator=g) + 0.5).to(dev), (torch.randn((n, cin), generator=g) * 0.2).to(dev)) for n, _, _ in shapes]
+    pca, pcb, gn, xs, aff_a, aff_b = _tower_pair(dev, [(2, 20, 36), (2, 9, 17), (2, 5, 3), (2, 3, 2), (2, 1, 1)], 64, with_affine)
     pair = ops.conv_gn_multi_pair(xs, pca, gn[0], xs, pcb, gn[1], groups, 1e-5, in_affine_a=aff_a, in_affine_b=aff_b)
     assert pair is not None
     ya, affa = ops.conv_gn_multi(xs, [pca] * 5, gn[0][0], gn[0][1], groups, 1e-5, in_affine=aff_a)
@@ -698,8 +607,6 @@ def test_conv_pointwise_split_bf16_form(dev, case, form, monkeypatch):
     fp16 pieces (22-bit operands, three products), fp32 accumulation — checked against a FLOAT64 convolution at 2e-5 absolute (the fp32-MFMA
     kernel's own distance from float64 on these shapes), ragged pixel counts, cout padding, channel views via the packed conv, and the pooled
     sums of the eSE gate; refused without the split packing."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout, pool = case
     flag = "ALLOW_SPLIT_BF16" if form == 10 else "ALLOW_SPLIT_F16"
     monkeypatch.setattr(ops, flag, True)
@@ -714,17 +621,14 @@ def test_conv_pointwise_split_bf16_form(dev, case, form, monkeypatch):
     ys = {}
     for tv in ((form, 32, 4), (8, 32, 4)):
         y = View(torch.full((n, h, w, cout), -5.0, device=dev))
-        d = (_lib.ConvDesc * 1)()
-        ops._fill_desc(d[0], xv, pc, y, True, None, None, False, False)
-        d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = tv
+        _, d, keep = raw_conv(xv, pc, y, tv, relu=True, launch=False)
         pws = None
         if pool:
-            rows = cmk_rows = _lib.load().cmk_conv_pool_rows(ctypes.byref(d[0]))
+            rows = _lib.load().cmk_conv_pool_rows(ctypes.byref(d[0]))
             assert rows == 128
             pws = torch.zeros((2 * (-(-(n * h * w) // rows)), cout), dtype=torch.float32, device=dev)
             d[0].pool_ws = pws.data_ptr()
-        _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "pointwise " + str(tv))
-        torch.cuda.synchronize()
+        _lib.check(relaunch(d), "pointwise " + str(tv))
         ys[tv[0]] = (y, pws)
     err_split = float((ys[form][0].nchw().cpu().double() - ref).abs().max())
     err_f32 = float((ys[8][0].nchw().cpu().double() - ref).abs().max())
@@ -735,18 +639,13 @@ def test_conv_pointwise_split_bf16_form(dev, case, form, monkeypatch):
     # without the split packing the variant is refused, not silently replaced
     monkeypatch.setattr(ops, flag, False)
     pc2 = ops.PackedConv(wt, scale, shift, dev)
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], xv, pc2, View(torch.empty((n, h, w, cout), device=dev)), True, None, None, False, False)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = form, 32, 4
-    assert _lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) != 0
+    assert raw_conv(xv, pc2, View(torch.empty((n, h, w, cout), device=dev)), (form, 32, 4), relu=True)[0] != 0
 
 
 @pytest.mark.parametrize("form", [10, 12])
 def test_conv_split_bf16_gather_and_upsampled_residual_forms(dev, form, monkeypatch):
     """OPT-IN tune_wm 10 / 12 (three bf16 pieces / two fp16 pieces per operand) beyond the plain 1x1 conv: a 3x3 conv (stride 2 and stride 1) in the gather form — K walks 9 taps x Cin / 16 chunks, the split
     weights packed tap-major — and a 1x1 lateral with the nearest-2x upsampled residual in the epilogue (d2 FPN top-down add); against float64."""
-    import ctypes
-    from centermask2_amd import _lib
     monkeypatch.setattr(ops, "ALLOW_SPLIT_BF16" if form == 10 else "ALLOW_SPLIT_F16", True)
     for (n, h, w, cin, cout, stride) in ((2, 21, 35, 64, 128, 2), (1, 17, 23, 32, 256, 1)):
         x = _rand((n, cin, h, w), 311).abs()
@@ -757,11 +656,7 @@ def test_conv_split_bf16_gather_and_upsampled_residual_forms(dev, form, monkeypa
         assert (pc.w_split if form == 10 else pc.w_splith) is not None
         ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
         y = View(torch.full((n, ho, wo, cout), -5.0, device=dev))
-        d = (_lib.ConvDesc * 1)()
-        ops._fill_desc(d[0], ops.as_view(x.to(dev)), pc, y, True, None, None, False, False)
-        d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = form, 32, 4
-        _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "split gather form")
-        torch.cuda.synchronize()
+        _lib.check(raw_conv(ops.as_view(x.to(dev)), pc, y, (form, 32, 4), relu=True)[0], "split gather form")
         assert float((y.nchw().cpu().double() - ref).abs().max()) <= 2e-5
     # lateral + nearest-2x upsampled residual
     n, h, w, cin, cout = 2, 12, 20, 512, 256
@@ -772,11 +667,7 @@ def test_conv_split_bf16_gather_and_upsampled_residual_forms(dev, form, monkeypa
     ref = F.conv2d(x.double(), wt.double(), bias.double()) + F.interpolate(coarse.double(), scale_factor=2, mode="nearest")
     pc = ops.PackedConv(wt, None, bias, dev)
     y = View(torch.empty((n, h, w, cout), device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], ops.as_view(x.to(dev)), pc, y, False, None, ops.as_view(coarse.to(dev)), True, False)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = form, 32, 4
-    _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "split lateral + upsampled residual")
-    torch.cuda.synchronize()
+    _lib.check(raw_conv(ops.as_view(x.to(dev)), pc, y, (form, 32, 4), res=ops.as_view(coarse.to(dev)), res_upsample=True)[0], "split lateral + upsampled residual")
     assert float((y.nchw().cpu().double() - ref).abs().max()) <= 2e-5
 
 
@@ -795,7 +686,6 @@ def test_groupnorm_affine_multi_level(dev):
 
 def _gn_affine_raw(lib, xs, gamma, beta, groups, chunks, multi):
     """(workspace, [(scale, shift) per level]) of cmk_groupnorm_affine (one level) or cmk_groupnorm_affine_multi on dense NHWC tensors."""
-    import ctypes
     nl, (n, c) = len(xs), (xs[0].shape[0], xs[0].shape[3])
     dev = xs[0].device
     ws = torch.zeros((nl, n, groups, chunks, 2), dtype=torch.float64, device=dev)
@@ -861,8 +751,6 @@ def test_conv_direct_split_f16_form(dev, case, monkeypatch):
     operands), three products, fp32 accumulation: within 1e-5 of a FLOAT64 conv on unit-variance outputs (an fp32 accumulation's distance; the
     fp32 F(4x4) Winograd form sits at 1e-4); inputs spanning 1e-4 .. 1e3 in magnitude (the residual scaling); output channel views, partial
     ReLU, every geometry; refused without the packing or with another piece count."""
-    import ctypes
-    from centermask2_amd import _lib
     n, h, w, cin, cout, geo, pieces = case
     monkeypatch.setattr(ops, "ALLOW_SPLIT_BF16", True)
     monkeypatch.setattr(ops, "ALLOW_SPLIT_F16", True)
@@ -881,22 +769,18 @@ def test_conv_direct_split_f16_form(dev, case, monkeypatch):
     xv = ops.as_view(x.to(dev))
     big = torch.full((n, h, w, cout + 24), float("nan"), device=dev)         # the output is a channel slice of a wider buffer (the OSA concat)
     y = View(big, 16, cout)
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], xv, pc, y, False, relu_upto, None, False, False)
-    d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 11, pieces, geo
-    lib = _lib.load()
+    rc, d, keep = raw_conv(xv, pc, y, (11, pieces, geo), relu_upto=relu_upto)
     if pieces not in (2, 21):
-        assert lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) != 0
+        assert rc != 0
         return
-    _lib.check(lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "conv_sp3")
-    torch.cuda.synchronize()
+    _lib.check(rc, "conv_sp3")
     got = big[..., 16:16 + cout].permute(0, 3, 1, 2).double().cpu()
     assert bool(torch.isnan(big[..., :16]).all()) and bool(torch.isnan(big[..., 16 + cout:]).all())       # nothing written outside the view
     for i in range(n):                                        # per image, relative to that image's own output magnitude
         err, mag = float((got[i] - ref[i]).abs().max()), float(ref[i].abs().max())
         assert err <= 1e-5 * mag, (i, err, mag)
     d[0].w_splith = None
-    assert lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) != 0                                    # no packing: refused, not emulated
+    assert relaunch(d) != 0                                    # no packing: refused, not emulated
 
 
 @pytest.mark.parametrize("geo", [0, 1, 2, 3])

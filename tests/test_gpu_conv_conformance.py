@@ -1,7 +1,7 @@
 """-m gpu: every case of the conv conformance table (tests/conv_cases.py) through the C ABI on real buffers, one test id per family.
 
 An accepted case is launched (cmk_conv2d_nhwc for one problem, cmk_conv2d_nhwc_multi otherwise; descriptors from ops._fill_desc and
-ops._set_variant) and checked for: the output against a float64 reference at the bar the family already holds in its own tests; nothing
+ops._set_variant, through conv_cases.fill_descs) and checked for: the output against a float64 reference at the bar the family already holds in its own tests; nothing
 written outside the output view (the view lies in a NaN-filled tensor that is itself the middle images of a NaN-filled allocation with one
 guard image before and one after); input, residual, weights and epilogue vectors bit-unchanged; a second launch giving the same bits;
 cmk_conv_plan agreeing with the launch.  A refused case must return non-zero with an error text and leave the NaN-filled output and every
@@ -17,15 +17,13 @@ Observed on an MI355X (the run's error report has them per family): relative to 
 stride 2 9.2e-7, gather 9.0e-7, pw 4.5e-7, pw gather 1.3e-6, wino4r 3.5e-7, the six F(4x4) forms 5.5e-6 .. 7.8e-6; tune_wm 10 7.8e-6 and
 tune_wm 12 4.5e-6 absolute; tune_wm 11 7.5e-7 of the image's magnitude; GroupNorm scale / shift below 5.4e-7; pooled means below 1.1e-7.
 Census rows write a dense output between the guard images, feature rows a channel slice of a wider tensor."""
-import ctypes
-
 import pytest
 import torch
 
 from centermask2_amd import _lib, ops
 from centermask2_amd.ops import View
 from tests import conv_cases as cc
-from tests.helpers import close, close_abs
+from tests.helpers import close, close_abs, relaunch
 
 pytestmark = pytest.mark.gpu
 
@@ -86,11 +84,8 @@ def _all_nan(t):
 
 
 def _launch(lib, descs):
-    n = len(descs)
-    rc = lib.cmk_conv2d_nhwc(ctypes.byref(descs[0]), ops._stream()) if n == 1 else lib.cmk_conv2d_nhwc_multi(descs, n, ops._stream())
-    err = lib.cmk_last_error().decode() if rc != 0 else ""
-    torch.cuda.synchronize()
-    return rc, err
+    rc = relaunch(descs)
+    return rc, lib.cmk_last_error().decode() if rc != 0 else ""
 
 
 def _fp32_bar(diff, ref, rel, what):

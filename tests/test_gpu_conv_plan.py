@@ -1,6 +1,6 @@
 """-m gpu: the profiled launch path of ops.py (ops.PROFILE a list) records each conv under the kernel name and the executed FLOPs that the
 library's plan of the launch gives (cmk_conv_plan), and launches what the unprofiled path launches.  The literals are the answers of the
-Python mirrors this replaced (tests/golden/conv_plan_cases.json, the rows of make_conv_plan_cases.py's profile_rows)."""
+Python mirrors this replaced (the three profile rows of tests/golden/conv_plan_cases.json; DESIGN.md, "The plan golden")."""
 import pytest
 import torch
 

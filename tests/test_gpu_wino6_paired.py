@@ -1,24 +1,19 @@
 """-m gpu: the paired form of the F(4x4,3x3) Winograd kernel (tune_wm 6 / tune_sc 32, conv_wino6p_kernel: 64 couts per workgroup, halo
 loads and pass 1 shared by the two cout tiles) does the arithmetic of conv_wino6_kernel (tune_sc 16) in the same order: every output,
 GroupNorm record and split-K partial result must be bit-identical to it."""
-import ctypes
-
 import pytest
 import torch
 
 from centermask2_amd import _lib, ops
 from centermask2_amd.ops import View
 
+from .helpers import raw_conv
+from .test_gpu_backbone_ops import WINO6_CASES as MAP_CASES, _rand, _tower_pair
+
 pytestmark = pytest.mark.gpu
 
-# the F(4x4) shapes of test_gpu_backbone_ops.py (test_conv_winograd6_variant, test_conv_winograd6_roi_pair_geometry)
-MAP_CASES = [(2, 37, 45, 64, 128), (1, 16, 16, 256, 256), (1, 25, 40, 224, 224), (2, 14, 14, 256, 80), (1, 100, 160, 32, 5),
-             (1, 12, 40, 128, 32), (1, 13, 41, 48, 33), (3, 5, 3, 32, 64), (1, 50, 80, 192, 192)]
+# the F(4x4) shapes of test_gpu_backbone_ops.py (test_conv_winograd6_variant: MAP_CASES; test_conv_winograd6_roi_pair_geometry)
 ROI_CASES = [(6, 14, 14, 256, 80), (5, 14, 14, 272, 256), (3, 16, 14, 32, 64), (2, 7, 7, 64, 32), (1, 14, 14, 64, 33)]
-
-
-def _rand(shape, seed, scale=1.0):
-    return torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
 def _conv(dev, x, wt, tv, seed=0, aff=None):
@@ -28,13 +23,7 @@ def _conv(dev, x, wt, tv, seed=0, aff=None):
     scale = torch.rand(cout, generator=torch.Generator().manual_seed(seed)) + 0.5
     pc = ops.PackedConv(wt, scale, _rand((cout,), seed + 1, 0.1), dev)
     y = View(torch.full((n, h, w, cout), -5.0, device=dev))
-    d = (_lib.ConvDesc * 1)()
-    ops._fill_desc(d[0], ops.as_view(x.to(dev)), pc, y, False, cout // 2, None, False, False, aff)
-    ws = ops._set_variant(d, 1, tv)
-    rc = _lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream())
-    torch.cuda.synchronize()
-    del ws
-    return rc, y.t
+    return raw_conv(ops.as_view(x.to(dev)), pc, y, tv, relu_upto=cout // 2, in_affine=aff)[0], y.t
 
 
 def _same(dev, x, wt, tv16, tv32, seed=0, aff=None):
@@ -79,11 +68,7 @@ def test_paired_channel_views(dev):
     outs = []
     for sc in (16, 32):
         out = torch.full((n, h, w, 96), -7.0, device=dev)
-        d = (_lib.ConvDesc * 1)()
-        ops._fill_desc(d[0], View(big, 32, cin), pc, View(out, 16, cout), False, 4, None, False, False)
-        d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = 6, sc, 1
-        _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "wino6 views")
-        torch.cuda.synchronize()
+        _lib.check(raw_conv(View(big, 32, cin), pc, View(out, 16, cout), (6, sc, 1), relu_upto=4)[0], "wino6 views")
         outs.append(out)
     assert torch.equal(outs[0], outs[1])
     assert float(outs[1][..., :16].max()) == -7.0 and float(outs[1][..., 64:].min()) == -7.0
@@ -106,13 +91,7 @@ def test_paired_groupnorm_records(dev, cout, groups, with_affine):
     for sc in (16, 32):
         ys = [View(torch.full((n, h, w, cout), -5.0, device=dev)) for n, h, w in shapes]
         gws = torch.full((recs, groups, 2), -1.0, dtype=torch.float64, device=dev)
-        d = (_lib.ConvDesc * len(shapes))()
-        for i in range(len(shapes)):
-            ops._fill_desc(d[i], xs[i], pc, ys[i], False, None, None, False, False, affs[i] if with_affine else None)
-            d[i].tune_wm, d[i].tune_sc, d[i].tune_wn = 6, sc, 1
-            d[i].gn_ws, d[i].gn_groups = gws.data_ptr(), groups
-        _lib.check(lib.cmk_conv2d_nhwc_multi(d, len(shapes), ops._stream()), "wino6 gn records")
-        torch.cuda.synchronize()
+        _lib.check(raw_conv(xs, [pc] * len(shapes), ys, (6, sc, 1), in_affine=affs if with_affine else None, gn=(gws, groups))[0], "wino6 gn records")
         res.append((ys, gws))
     for y16, y32 in zip(res[0][0], res[1][0]):
         assert torch.equal(y16.t, y32.t)
@@ -131,20 +110,8 @@ def test_paired_split_k(dev, case):
 def test_paired_tower_pair_launch(dev, with_affine, monkeypatch):
     """ops.conv_gn_multi_pair (the cls and bbox towers' conv k as ONE launch of 10 problems with per-problem weights) on the paired form:
     outputs and GroupNorm affines bit-identical to the same launch on conv_wino6."""
-    g = torch.Generator().manual_seed(77)
-    shapes = [(2, 25, 41), (2, 13, 20), (2, 7, 10), (2, 4, 5), (2, 2, 3)]
-    cin = cout = 256
     groups = 32
-    wa = torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (cin * 9)) ** 0.5
-    wb = torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (cin * 9)) ** 0.5
-    pca = ops.PackedConv(wa, None, torch.randn((cout,), generator=g) * 0.1, dev)
-    pcb = ops.PackedConv(wb, None, torch.randn((cout,), generator=g) * 0.1, dev)
-    gn = [((torch.rand((cout,), generator=g) + 0.5).to(dev), (torch.randn((cout,), generator=g) * 0.1).to(dev)) for _ in range(2)]
-    xs = [ops.as_view(torch.randn((n, cin, h, w), generator=g).to(dev)) for n, h, w in shapes]
-    aff_a = aff_b = None
-    if with_affine:
-        aff_a = [((torch.rand((n, cin), generator=g) + 0.5).to(dev), (torch.randn((n, cin), generator=g) * 0.2).to(dev)) for n, _, _ in shapes]
-        aff_b = [((torch.rand((n, cin), generator=g) + 0.5).to(dev), (torch.randn((n, cin), generator=g) * 0.2).to(dev)) for n, _, _ in shapes]
+    pca, pcb, gn, xs, aff_a, aff_b = _tower_pair(dev, [(2, 25, 41), (2, 13, 20), (2, 7, 10), (2, 4, 5), (2, 2, 3)], 256, with_affine)
     res = []
     for sc in (16, 32):
         monkeypatch.setattr(ops, "FORCE_VARIANT", (6, sc, 1))

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from centermask2_amd import _lib, ops
 from centermask2_amd.ops import View
+from tests.helpers import raw_conv, relaunch
 from tests.test_gpu_backbone_ops import _close, _rand, _run_variant
 
 pytestmark = pytest.mark.gpu
@@ -94,13 +95,9 @@ def test_tail_channel_view(dev, sc, monkeypatch):
     outs = []
     for tv in ((6, sc, 2), (6, sc, 2, 1, 4)):
         out = torch.full((n, h, w, 96), -7.0, device=dev)
-        d = (_lib.ConvDesc * 1)()
-        ops._fill_desc(d[0], View(big, 0, cin), pc, View(out, 16, cout), False, 4, None, False, False)
-        ws = ops._set_variant(d, 1, tv)
-        assert (ws is not None) == (len(tv) == 5)
-        _lib.check(_lib.load().cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()), "wino6 tail views")
-        torch.cuda.synchronize()
-        del ws
+        rc, d, keep = raw_conv(View(big, 0, cin), pc, View(out, 16, cout), tv, relu_upto=4)
+        assert (keep["ws"] is not None) == (len(tv) == 5)
+        _lib.check(rc, "wino6 tail views")
         outs.append(out)
     off, on = outs
     ref = F.conv2d(big[..., :cin].permute(0, 3, 1, 2).cpu().double(), wt.double(), pc.shift.cpu().double(), padding=1)
@@ -115,49 +112,37 @@ def test_tail_refusals(dev, cmk_lib, monkeypatch):
     n, h, w, cin, cout = 4, 14, 14, 64, 64
     x = ops.as_view(_rand((n, cin, h, w), 1).to(dev))
     pc = ops.PackedConv(_rand((cout, cin, 3, 3), 2, 0.05), None, None, dev)
-    st = ops._stream()
-
-    def desc(count=1):
-        d = (_lib.ConvDesc * count)()
-        ys = [View(torch.empty((n, h, w, cout), device=dev)) for _ in range(count)]
-        for i in range(count):
-            ops._fill_desc(d[i], x, pc, ys[i], False, None, None, False, False)
-        return d, ys
-
-    d, ys = desc()
-    ws = ops._set_variant(d, 1, (6, 16, 2, 1, 2))
+    ys = [View(torch.empty((n, h, w, cout), device=dev)) for _ in range(3)]
+    _, d, keep = raw_conv(x, pc, ys[0], (6, 16, 2, 1, 2), launch=False)
+    ws = keep["ws"]
     assert ws is not None and ws.numel() == cmk_lib.cmk_conv_tail_ws_floats(ctypes.byref(d[0])) == 2 * 2 * h * w * 64
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) == 0          # the descriptor itself is fine
+    assert relaunch(d) == 0                                             # the descriptor itself is fine
     gws = torch.zeros((64, 32, 2), dtype=torch.float64, device=dev)     # ... but not with fused GroupNorm statistics
     d[0].gn_ws, d[0].gn_groups = gws.data_ptr(), 32
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) != 0
+    assert relaunch(d) != 0
     d[0].gn_ws, d[0].gn_groups = None, 0
     d[0].splitk_ws = None                                               # ... nor without its workspace
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) != 0 and b"tail" in cmk_lib.cmk_last_error()
+    assert relaunch(d) != 0 and b"tail" in cmk_lib.cmk_last_error()
     d[0].splitk_ws = ws.data_ptr()
     d[0].splitk_tail = 8                                                # ... nor more ways than chunk pairs (64 channels: 4)
     big = torch.empty((8 * 2 * h * w * 64,), device=dev)
     d[0].splitk_ws = big.data_ptr()
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) != 0 and b"tail" in cmk_lib.cmk_last_error()
+    assert relaunch(d) != 0 and b"tail" in cmk_lib.cmk_last_error()
     d[0].splitk_tail = 2
     d[0].tune_wn = 1                                                    # ... nor on the map geometry
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) != 0 and b"tail" in cmk_lib.cmk_last_error()
+    assert relaunch(d) != 0 and b"tail" in cmk_lib.cmk_last_error()
     d[0].tune_wn, d[0].tune_sc = 2, 64                                  # ... nor on the shared-V form
     assert cmk_lib.cmk_conv_tail_ws_floats(ctypes.byref(d[0])) == 0
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) != 0 and b"tail" in cmk_lib.cmk_last_error()
+    assert relaunch(d) != 0 and b"tail" in cmk_lib.cmk_last_error()
     d[0].tune_sc = 16
     d[0].splitk, d[0].splitk_tail = 2, 2                                # ... nor beside split-K
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) != 0 and b"tail" in cmk_lib.cmk_last_error()
+    assert relaunch(d) != 0 and b"tail" in cmk_lib.cmk_last_error()
     d[0].splitk = 0
-    assert cmk_lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), st) == 0
-    torch.cuda.synchronize()
+    assert relaunch(d) == 0
     # several problems in one launch
-    d2, ys2 = desc(2)
-    ws2 = ops._set_variant(d2, 2, (6, 16, 2, 1, 2))
-    d2[1].splitk_tail, d2[1].splitk_tail_tiles, d2[1].splitk_ws = 2, 1, ws2.data_ptr()
-    assert cmk_lib.cmk_conv2d_nhwc_multi(d2, 2, st) != 0
-    torch.cuda.synchronize()
-    del ws, ws2, big, ys, ys2
+    _, d2, keep2 = raw_conv([x, x], [pc, pc], ys[1:], (6, 16, 2, 1, 2), launch=False)
+    d2[1].splitk_tail, d2[1].splitk_tail_tiles, d2[1].splitk_ws = 2, 1, keep2["ws"].data_ptr()
+    assert relaunch(d2) != 0
 
 
 def test_tail_off_unless_named(dev, cmk_lib, monkeypatch):
