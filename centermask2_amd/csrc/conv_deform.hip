@@ -7,8 +7,11 @@
 //   so one workgroup covers the whole layer width (the DCN layers' Cout is the stage width, 64..224) and every sampled value
 //   feeds each output channel exactly once.
 //   K is walked tap-major: at the start of tap t the workgroup computes, once per (pixel, deformable group), the four corner
-//   pixel indices and the four bilinear weights (mask = sigmoid(logit) folded in, out-of-map corners weighted 0 and clamped to
-//   a valid address) into LDS; every 16-channel chunk of that tap then reads them back.  In NHWC a corner is a contiguous run of
+//   pixel indices and the four bilinear weights (mask = sigmoid(logit) folded in) into LDS; every 16-channel chunk of that tap
+//   then reads them back.  A corner that must not be read (it lies outside the map, its sample lies outside (-1,H) x (-1,W), or
+//   its pixel is past the last one) gets the index -1: load_A skips its load (the lane is masked off) and blends a zero quad, so
+//   nothing is multiplied by 0 and no Inf or NaN of a stand-in address can reach the output.  An in-map corner of weight 0 is
+//   read and multiplied, as the float64 restatement does.  In NHWC a corner is a contiguous run of
 //   channels, so a thread gathers its 4 channels of a pixel as four 16-byte loads and blends them with three FMAs + one mul.
 //   K order inside a 16-chunk is that of conv_igemm.hip (MFMA k-step s of lane half h uses channel 8h+s); a lane half's 8
 //   channels lie in one deformable group whenever (Cin/dg) % 8 == 0, which the host checks.
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void conv_deform_kernel(const DeformArgs a)
             const int p = item / dg, g = item - p * dg;
             const long P = pix0 + p;
             Sample s;
-            s.o[0] = s.o[1] = s.o[2] = s.o[3] = 0;
+            s.o[0] = s.o[1] = s.o[2] = s.o[3] = -1;          // -1: nothing is read for this corner
             s.w[0] = s.w[1] = s.w[2] = s.w[3] = 0.f;
             if (P < a.total_pix) {
                 const int n = (int)(P / hw);
@@ -94,13 +97,10 @@ __global__ __launch_bounds__(256, 2) void conv_deform_kernel(const DeformArgs a)
                     const int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
                     const float ly = py - fy, lx = px - fx, uy = 1.f - ly, ux = 1.f - lx;
                     const bool vy0 = y0 >= 0, vy1 = y1 <= H - 1, vx0 = x0 >= 0, vx1 = x1 <= W - 1;
-                    const int cy0 = vy0 ? y0 : 0, cy1 = vy1 ? y1 : H - 1, cx0 = vx0 ? x0 : 0, cx1 = vx1 ? x1 : W - 1;
-                    s.o[0] = base + cy0 * W + cx0; s.w[0] = (vy0 && vx0) ? uy * ux * m : 0.f;
-                    s.o[1] = base + cy0 * W + cx1; s.w[1] = (vy0 && vx1) ? uy * lx * m : 0.f;
-                    s.o[2] = base + cy1 * W + cx0; s.w[2] = (vy1 && vx0) ? ly * ux * m : 0.f;
-                    s.o[3] = base + cy1 * W + cx1; s.w[3] = (vy1 && vx1) ? ly * lx * m : 0.f;
-                } else {
-                    s.o[0] = s.o[1] = s.o[2] = s.o[3] = base;
+                    if (vy0 && vx0) { s.o[0] = base + y0 * W + x0; s.w[0] = uy * ux * m; }
+                    if (vy0 && vx1) { s.o[1] = base + y0 * W + x1; s.w[1] = uy * lx * m; }
+                    if (vy1 && vx0) { s.o[2] = base + y1 * W + x0; s.w[2] = ly * ux * m; }
+                    if (vy1 && vx1) { s.o[3] = base + y1 * W + x1; s.w[3] = ly * lx * m; }
                 }
             }
             sS[item] = s;
@@ -119,11 +119,14 @@ __global__ __launch_bounds__(256, 2) void conv_deform_kernel(const DeformArgs a)
             const int g = ch / a.cpg;
             const Sample s = sS[p * dg + g];
             const float* src = xin + ch;
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(src + (long)s.o[0] * a.x_cs);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(src + (long)s.o[1] * a.x_cs);
-            const f32x4 v2 = *reinterpret_cast<const f32x4*>(src + (long)s.o[2] * a.x_cs);
-            const f32x4 v3 = *reinterpret_cast<const f32x4*>(src + (long)s.o[3] * a.x_cs);
-            a_stage[it] = v0 * s.w[0] + v1 * s.w[1] + v2 * s.w[2] + v3 * s.w[3];
+            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            f32x4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {               // a predicated load: an unread corner is a zero quad, not a product with 0
+                v[k] = zero;
+                if (s.o[k] >= 0) v[k] = *reinterpret_cast<const f32x4*>(src + (long)s.o[k] * a.x_cs);
+            }
+            a_stage[it] = v[0] * s.w[0] + v[1] * s.w[1] + v[2] * s.w[2] + v[3] * s.w[3];
         }
     };
     auto store_A = [&](int buf) {
@@ -244,9 +247,12 @@ extern "C" int cmk_deform_conv3x3_nhwc(const float* x, int x_cs, int x_co, const
     using namespace cmk;
     if (!x || !offsets || !w || !scale || !shift || !y) return fail(CMK_EINVAL, "deform_conv: null pointer%s", "");
     if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return fail(CMK_EINVAL, "deform_conv: empty shape%s", "");
-    if ((x_cs & 3) || (x_co & 3) || x_co < 0 || x_co + Cin > x_cs || ((uintptr_t)x & 15))
+    if ((x_cs & 3) || (x_co & 3) || x_co < 0 || (long)x_co + Cin > x_cs || ((uintptr_t)x & 15))
         return fail(CMK_EINVAL, "deform_conv: input view must be 16-byte aligned (stride and offset multiples of 4) and hold Cin channels%s", "");
-    if (y_co < 0 || y_co + Cout > y_cs) return fail(CMK_EINVAL, "deform_conv: output view (%s%ld channels) does not hold Cout", "", (long)y_cs);
+    if ((uintptr_t)w & 15) return fail(CMK_EINVAL, "deform_conv: the packed weights are read as 16-byte vectors, w must be 16-byte aligned%s", "");
+    if (((uintptr_t)offsets | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)y) & 3)
+        return fail(CMK_EINVAL, "deform_conv: offsets, scale, shift and y must be 4-byte aligned%s", "");
+    if (y_co < 0 || (long)y_co + Cout > y_cs) return fail(CMK_EINVAL, "deform_conv: output view (%s%ld channels) does not hold Cout", "", (long)y_cs);
     if (x == y && x_co < y_co + Cout && y_co < x_co + Cin)
         return fail(CMK_EINVAL, "deform_conv: input and output channel slices of one buffer overlap%s", "");
     if (dg < 1 || Cin % dg) return fail(CMK_EINVAL, "deform_conv: deformable groups (%s%ld) do not divide Cin", "", (long)dg);

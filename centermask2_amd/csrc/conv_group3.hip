@@ -264,6 +264,8 @@ extern "C" int cmk_group_conv3x3_nhwc(const float* x, int x_cs, int x_co, const 
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     if ((long)N * Ho * Wo * (C >> 2) >= (1L << 31))
         return fail(CMK_EINVAL, "group_conv3x3: %s%ld output quads, the kernel indexes them in 32 bits", "", (long)N * Ho * Wo * (C >> 2));
+    if (x == y && x_co < y_co + C && y_co < x_co + C)
+        return fail(CMK_EINVAL, "group_conv3x3: input and output channel slices of one buffer overlap%s", "");
     const GroupArgs a = {x, w, scale, shift, y, x_cs, x_co, y_cs, y_co, N, H, W, Ho, Wo, C, groups, relu ? 1 : 0, stream};
     switch (cg) {
         case 4: launch_valu<4>(a, stride); break;

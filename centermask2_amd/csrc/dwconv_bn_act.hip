@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void dwconv3_bn_act_kernel(const float* __rest
                                                             float out_min, float out_max, float* __restrict__ y, int y_cs, int y_co, int N,
                                                             int H, int W, int Ho, int Wo, int C4) {
     const int WT = (Wo + T - 1) / T, HT = (Ho + R - 1) / R;
-    const int total = N * HT * WT * C4;               // < 2^31, checked on the host
+    const int total = N * HT * WT * C4;               // <= 2^31 - DW_MAX_GRID_STRIDE, checked on the host: i never wraps
     for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
         const int c4 = i % C4;
         int r = i / C4;
@@ -112,6 +112,23 @@ struct DwArgs {
     void* stream;
 };
 
+// The kernel walks its threads with a 32-bit index and a grid stride of at most 8192 workgroups x 256 (launch_dw).  The entry points
+// refuse an output of more than 2^31 - DW_MAX_GRID_STRIDE quads (a thread owns at least one), so the index that ends the loop,
+// below total + stride, stays below 2^31.  A bound, not a 64-bit index: the kernel and its registers stay as they are.
+constexpr long DW_MAX_GRID_STRIDE = 8192L * 256;
+
+// what both entry points ask of their views and shape after the null and empty-shape checks; nullptr or the reason of the refusal
+static const char* dw_view_error(const float* x, int x_cs, int x_co, const float* y, int y_cs, int y_co, int C) {
+    if (C & 3) return "C must be a multiple of 4";
+    if ((x_cs & 3) || (x_co & 3) || (y_cs & 3) || (y_co & 3) || x_co < 0 || y_co < 0)
+        return "misaligned channel offset or pixel stride (multiples of 4 floats, offsets >= 0)";
+    if ((long)x_co + C > x_cs || (long)y_co + C > y_cs) return "channel slice [co, co + C) leaves the pixel";
+    return nullptr;
+}
+
+// x == y is fine for disjoint channel slices; overlapping ones are refused: a thread would read what another has written
+static bool dw_overlap(const float* x, int x_co, const float* y, int y_co, int C) { return x == y && x_co < y_co + C && y_co < x_co + C; }
+
 static inline long dw_blocks(const DwArgs& a, int t, int r) {
     return ((long)a.N * ((a.Ho + r - 1) / r) * ((a.Wo + t - 1) / t) * a.C4 + 255) / 256;
 }
@@ -133,17 +150,16 @@ extern "C" int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, con
                                          int stride, void* stream) {
     if (!x || !w || !scale || !shift || !y) return fail(CMK_EINVAL, "dwconv_bn_act: null pointer%s", "");
     if (N < 1 || H < 1 || W < 1 || C < 1) return fail(CMK_EINVAL, "dwconv_bn_act: empty shape%s (N, H, W, C must be >= 1)", "");
-    if (C & 3) return fail(CMK_EINVAL, "dwconv_bn_act: %sC = %ld must be a multiple of 4", "", (long)C);
-    if ((x_cs & 3) || (x_co & 3) || (y_cs & 3) || (y_co & 3) || x_co < 0 || y_co < 0)
-        return fail(CMK_EINVAL, "dwconv_bn_act: misaligned channel offset or pixel stride%s (x %ld, y %ld: multiples of 4 floats)", "", (long)x_co, (long)y_co);
-    if ((long)x_co + C > x_cs || (long)y_co + C > y_cs) return fail(CMK_EINVAL, "dwconv_bn_act: channel slice%s [co, co + %ld) leaves the pixel", "", (long)C);
+    if (const char* why = dw_view_error(x, x_cs, x_co, y, y_cs, y_co, C)) return fail(CMK_EINVAL, "dwconv_bn_act: %s (C = %ld)", why, (long)C);
     if (stride != 1 && stride != 2) return fail(CMK_EINVAL, "dwconv_bn_act: %sstride %ld must be 1 or 2", "", (long)stride);
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)y) & 15)
         return fail(CMK_EINVAL, "dwconv_bn_act: pointers must be 16-byte aligned%s", "");
     if (in_max != in_max || out_min != out_min || out_max != out_max || out_min > out_max)
         return fail(CMK_EINVAL, "dwconv_bn_act: bad clamp bounds%s", "");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    if ((long)N * Ho * Wo * (C >> 2) >= (1L << 31)) return fail(CMK_EINVAL, "dwconv_bn_act: %s%ld output quads, the kernel indexes them in 32 bits", "", (long)N * Ho * Wo * (C >> 2));
+    if ((long)N * Ho * Wo * (C >> 2) > (1L << 31) - DW_MAX_GRID_STRIDE)
+        return fail(CMK_EINVAL, "dwconv_bn_act: %s%ld output quads, the kernel indexes them in 32 bits with room for one grid stride", "", (long)N * Ho * Wo * (C >> 2));
+    if (dw_overlap(x, x_co, y, y_co, C)) return fail(CMK_EINVAL, "dwconv_bn_act: input and output channel slices of one buffer overlap%s", "");
     const DwArgs a = {x, w, scale, shift, y, x_cs, x_co, y_cs, y_co, N, H, W, Ho, Wo, C >> 2, in_max, out_min, out_max, stream};
     // outputs per thread (T columns x R rows): the measured best tile while it still leaves >= 1024 workgroups (4 per CU), smaller on small maps
     if (stride == 1) {
@@ -162,11 +178,14 @@ extern "C" int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, con
 extern "C" int cmk_dwconv3x3_nhwc(const float* x, int x_cs, int x_co, const float* w, float* y, int y_cs, int y_co, int N, int H, int W,
                                   int C, int stride, void* stream) {
     if (!x || !w || !y) return fail(CMK_EINVAL, "dwconv: null pointer%s", "");
-    if ((C & 3) || (x_cs & 3) || (x_co & 3) || (y_cs & 3) || (y_co & 3) || C < 4) return fail(CMK_EINVAL, "dwconv: channels must be multiples of 4%s", "");
-    if (stride != 1 && stride != 2) return fail(CMK_EINVAL, "dwconv: stride must be 1 or 2%s", "");
-    if (N < 1 || H < 1 || W < 1) return fail(CMK_EINVAL, "dwconv: empty input%s", "");
+    if (N < 1 || H < 1 || W < 1 || C < 1) return fail(CMK_EINVAL, "dwconv: empty shape%s (N, H, W, C must be >= 1)", "");
+    if (const char* why = dw_view_error(x, x_cs, x_co, y, y_cs, y_co, C)) return fail(CMK_EINVAL, "dwconv: %s (C = %ld)", why, (long)C);
+    if (stride != 1 && stride != 2) return fail(CMK_EINVAL, "dwconv: %sstride %ld must be 1 or 2", "", (long)stride);
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15) return fail(CMK_EINVAL, "dwconv: pointers must be 16-byte aligned%s", "");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    if ((long)N * Ho * Wo * (C >> 2) >= (1L << 31)) return fail(CMK_EINVAL, "dwconv: %s%ld output quads, the kernel indexes them in 32 bits", "", (long)N * Ho * Wo * (C >> 2));
+    if ((long)N * Ho * Wo * (C >> 2) > (1L << 31) - DW_MAX_GRID_STRIDE)
+        return fail(CMK_EINVAL, "dwconv: %s%ld output quads, the kernel indexes them in 32 bits with room for one grid stride", "", (long)N * Ho * Wo * (C >> 2));
+    if (dw_overlap(x, x_co, y, y_co, C)) return fail(CMK_EINVAL, "dwconv: input and output channel slices of one buffer overlap%s", "");
     const DwArgs a = {x, w, nullptr, nullptr, y, x_cs, x_co, y_cs, y_co, N, H, W, Ho, Wo, C >> 2, INFINITY, -INFINITY, INFINITY, stream};
     if (stride == 1) launch_dw<1, 4, 1, true>(a);
     else launch_dw<2, 2, 1, true>(a);

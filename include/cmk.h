@@ -205,15 +205,24 @@ int cmk_conv_gn_records(int H, int W, int tune_wm);
  * cmk_conv_desc.w for a 3x3 conv (cmk_conv_packed_floats(Cout, Cin, 3) floats).  offsets is the raw (N,H,W,off_cs) output of the
  * offset conv: for deformable group g and tap k = 3i+j channel g*18 + 2k holds dy and g*18 + 2k + 1 holds dx; with modulated != 0
  * channel 18*dg + g*9 + k holds the mask LOGIT (the sigmoid is applied here).  Input channel c belongs to group c / (Cin/dg).  The
- * sample (h-1+i+dy, w-1+j+dx) is bilinear with corners outside the map read as 0, and 0 outside (-1,H) x (-1,W).
- * Supported: Cin % 16 == 0, dg in {1, 2, 4} with (Cin/dg) % 8 == 0, off_cs >= 18*dg (27*dg modulated). */
+ * sample (h-1+i+dy, w-1+j+dx) is bilinear with corners outside the map read as 0, and 0 outside (-1,H) x (-1,W).  "0" means not
+ * read: an Inf or NaN of x reaches an output only through a corner that lies in the map and belongs to a sample inside
+ * (-1,H) x (-1,W); such a corner counts even at weight 0 (0 * Inf = NaN), nothing else does.  The ReLU is fmaxf: relu(NaN) = 0, as in
+ * the other conv epilogues.  Offsets and mask logits must be finite.
+ * Supported: N, H, W, Cin, Cout >= 1, Cin % 16 == 0, dg in {1, 2, 4} with (Cin/dg) % 8 == 0, off_cs >= 18*dg (27*dg modulated).
+ * Views: 0 <= x_co, x_co + Cin <= x_cs, x_cs and x_co multiples of 4; 0 <= y_co, y_co + Cout <= y_cs (any stride and offset: y is
+ * written float by float); x == y is allowed when the two channel slices are disjoint and refused when they overlap.
+ * Alignment: x and w are read as 16-byte vectors and must be 16-byte aligned; offsets, scale, shift and y are read and written as single
+ * floats and need 4 bytes only.  N*H*W * max(x_cs, y_cs) and N*H*W * off_cs must stay below 2^31.
+ * Every check is made before the launch and returns CMK_EINVAL. */
 int cmk_deform_conv3x3_nhwc(const float* x, int x_cs, int x_co, const float* offsets, int off_cs, const float* w,
                             const float* scale, const float* shift, float* y, int y_cs, int y_co, int N, int H, int W,
                             int Cin, int Cout, int dg, int modulated, int relu, void* stream);
 
 /* ---- depth-wise 3x3, pad 1, stride 1|2, no bias / norm / activation (vovnet.py:110-119 'dw_conv3x3', the dw half of the
  * depth-wise VoVNet bodies V-19-slim-dw-eSE / V-19-dw-eSE vovnet.py:30-48).  x, y are NHWC channel-slice views
- * (pixel stride *_cs, offset *_co floats); w is tap-major [9][C]. ------------------------------------------------ */
+ * (pixel stride *_cs, offset *_co floats); w is tap-major [9][C].  The same front door as cmk_dwconv3x3_bn_act_nhwc below
+ * (without scale, shift and the clamps): N, H, W >= 1, C a multiple of 4, the view, overlap, alignment and size rules. */
 int cmk_dwconv3x3_nhwc(const float* x, int x_cs, int x_co, const float* w, float* y, int y_cs, int y_co,
                        int N, int H, int W, int C, int stride, void* stream);
 
@@ -221,7 +230,11 @@ int cmk_dwconv3x3_nhwc(const float* x, int x_cs, int x_co, const float* w, float
  *   y = clamp(dw3x3(min(x, in_max)) * scale[c] + shift[c], out_min, out_max),  pad 1, stride 1|2, C % 4 == 0.
  * min(x, in_max) finishes the ReLU6 of the producer (the stem / expand 1x1 run with the plain ReLU epilogue); scale/shift is the
  * folded FrozenBN; the padding is zeros of the clamped input.  in_max = +inf, out_min = -inf, out_max = +inf switch the clamps
- * off.  A NaN propagates (torch.nn.ReLU6).  x, y: NHWC channel-slice views; w tap-major [9][C]; all pointers 16-byte aligned. */
+ * off; a NaN bound or out_min > out_max is refused.  A NaN propagates (torch.nn.ReLU6).  x, y: NHWC channel-slice views; w tap-major
+ * [9][C]; all pointers 16-byte aligned.  N, H, W >= 1; *_cs and *_co multiples of 4 floats with 0 <= co and co + C <= cs; x == y is
+ * allowed for disjoint channel slices (stride 1) and refused when the slices overlap (a thread would read what another wrote).
+ * Output map ((H-1)/stride + 1, (W-1)/stride + 1); N*Ho*Wo*C/4 <= 2^31 - 2^21: the kernel walks a 32-bit index with a grid stride of
+ * up to 2^21 threads.  Every check is made before the launch and returns CMK_EINVAL. */
 int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, const float* w, const float* scale, const float* shift,
                               float in_max, float out_min, float out_max, float* y, int y_cs, int y_co,
                               int N, int H, int W, int C, int stride, void* stream);
@@ -230,7 +243,9 @@ int cmk_dwconv3x3_bn_act_nhwc(const float* x, int x_cs, int x_co, const float* w
  *   y = [relu](gconv3x3(x) * scale[c] + shift[c]),  pad 1, stride 1|2, no bias, Cin = Cout = C, `groups` >= 2 groups of Cg = C/groups,
  * Cg in {4, 8, 16, 32, 64}.  Exact fp32; a group reads only its own Cg input channels (a NaN / Inf stays inside its group); a NaN passes
  * the ReLU.  Output map ((H-1)/stride + 1, (W-1)/stride + 1).  x, y: NHWC channel-slice views; w: 9*Cg*C floats in the packing written
- * down in csrc/conv_group3.hip (ops.pack_group_weight); all pointers 16-byte aligned, offsets and strides multiples of 4 floats.
+ * down in csrc/conv_group3.hip (ops.pack_group_weight); all pointers 16-byte aligned, offsets and strides multiples of 4 floats with
+ * 0 <= co and co + C <= cs; x == y is allowed for disjoint channel slices (stride 1) and refused when the slices overlap;
+ * N*Ho*Wo*C/4 < 2^31.  Every check is made before the launch and returns CMK_EINVAL.
  * One launch, no workspace.  Additive entry: the ABI version stays 5. */
 int cmk_group_conv3x3_nhwc(const float* x, int x_cs, int x_co, const float* w, const float* scale, const float* shift,
                            float* y, int y_cs, int y_co, int N, int H, int W, int C, int groups, int stride, int relu, void* stream);
@@ -243,7 +258,9 @@ int cmk_stem_conv_nchw3(const float* x, const float* w /* [27][Cout] */, const f
  * x (N,3,H,W) NCHW fp32; w [147][Cout], k = (kh*7 + kw)*3 + ci; y (N,Hp,Wp,Cout) NHWC channel-slice view.
  * Hc = (H-1)/2 + 1, Wc likewise (conv); Hp = (Hc-1)/2 + 1, Wp likewise (pool). Pool padding never wins (-inf).
  * One launch (csrc/stem7_pool.hip): the conv map stays in LDS.  Cout must be 64.  Conv taps outside the image are zeros; a NaN
- * behaves as in torch (relu keeps it, the max returns it for every window that holds it). */
+ * behaves as in torch (relu keeps it, the max returns it for every window that holds it).  N, H, W >= 1; y_cs and y_co multiples of 4
+ * floats with 0 <= y_co and y_co + 64 <= y_cs; y 16-byte aligned, x, w, scale, shift 4-byte; 3*H*W < 2^31.  Every check is made before
+ * the launch and returns CMK_EINVAL. */
 int cmk_stem7x7_bn_relu_maxpool_nchw3(const float* x, const float* w, const float* scale, const float* shift,
                                       float* y, int y_cs, int y_co, int N, int H, int W, int Cout, void* stream);
 

@@ -2,7 +2,7 @@
 exactly the __global__ kernels of csrc/detect.hip, csrc/roi.hip, csrc/prepost.hip and csrc/keypoint.hip as the built library instantiates
 them, every (entry point, feature) cell must have a row or a reason, and every refused row must be refused on dummy aligned pointers: every
 argument check of these entry points sits before its launch.  And the library-wide census: every kernel of the built library is claimed by
-exactly one of the four conformance tables (conv, stream, tail, image) or by a named direct test module."""
+exactly one of the five conformance tables (conv, stream, tail, image, variant) or by a named direct test module."""
 import ctypes
 import glob
 import os
@@ -14,18 +14,15 @@ import pytest
 from tests import image_cases as ic
 from tests import stream_cases as sc
 from tests import tail_cases as tc
+from tests import variant_cases as vc
 
 CASES = tc.all_cases()
 TESTS = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(TESTS), "centermask2_amd", "csrc")
 TAIL_FILES = ("detect.hip", "roi.hip", "prepost.hip", "keypoint.hip")
 
-# kernels outside the four tables: the source file of csrc/ that defines them -> the direct test module that launches them
+# kernels outside the five tables: the source file of csrc/ that defines them -> the direct test module that launches them
 DIRECT = {
-    "conv_group3.hip": "test_gpu_resnext.py",
-    "dwconv_bn_act.hip": "test_gpu_mobilenet.py",
-    "conv_deform.hip": "test_gpu_deform_conv.py",
-    "stem7_pool.hip": "test_gpu_resnet.py",
     "visualize.hip": "test_gpu_visualize.py",
     "conv.hip": "test_gpu_conv_conformance.py",      # the split-K reduction behind the conv table's splitk rows (no conv_*_kernel<> instantiation)
 }
@@ -125,7 +122,8 @@ def test_refused_rows_are_refused_before_any_launch(cmk_lib, entry):
 def test_every_kernel_of_the_library_is_claimed_exactly_once(cmk_lib):
     """Every __global__ kernel of csrc/ that the built library holds belongs to the conv table (the conv_*_kernel<...> instantiations that
     tests/test_cpu_conv_conformance.py counts), to the stream table, to the tail table, to the image table (rle.hip, mask_iou.hip and resize.hip,
-    claimed per instantiation) or to a direct test module named in DIRECT.  A new kernel that nobody claims fails here by name; no count is
+    claimed per instantiation), to the variant table (conv_deform.hip, dwconv_bn_act.hip, conv_group3.hip and stem7_pool.hip, per instantiation)
+    or to a direct test module named in DIRECT.  A new kernel that nobody claims fails here by name; no count is
     written down."""
     from tests import test_cpu_conv_conformance as conv
     sources = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
@@ -137,6 +135,7 @@ def test_every_kernel_of_the_library_is_claimed_exactly_once(cmk_lib):
     stream = {k for c in sc.all_cases() if c["answer"] == "accept" for k in c["kernels"]}
     tail = {k for c in CASES if c["answer"] == "accept" for k in c["kernels"]}
     image = {k for c in ic.all_cases() if c["answer"] == "accept" for k in c["kernels"]}
+    variant = {k for c in vc.all_cases() if c["answer"] == "accept" for k in c["kernels"]}
     for k in kernels:
         if k in conv_kernels:
             claims[k].append("tests/conv_cases.py")
@@ -146,6 +145,8 @@ def test_every_kernel_of_the_library_is_claimed_exactly_once(cmk_lib):
             claims[k].append("tests/tail_cases.py")
         if k in image:
             claims[k].append("tests/image_cases.py")
+        if k in variant:
+            claims[k].append("tests/variant_cases.py")
         for f, module in DIRECT.items():
             if base(k) in source_kernels([f]):
                 claims[k].append("tests/" + module)
@@ -153,7 +154,8 @@ def test_every_kernel_of_the_library_is_claimed_exactly_once(cmk_lib):
     twice = sorted((k, v) for k, v in claims.items() if len(v) > 1)
     assert not unclaimed, "kernels that no table and no direct test module claims: {}".format(unclaimed)
     assert not twice, "kernels claimed more than once: {}".format(twice)
-    assert conv_kernels <= kernels and stream <= kernels and tail <= kernels and image <= kernels
+    assert conv_kernels <= kernels and stream <= kernels and tail <= kernels and image <= kernels and variant <= kernels
+    assert set(DIRECT) == {"visualize.hip", "conv.hip"}
     assert not set(DIRECT) & set(ic.FILES), "a file of the image table is claimed per instantiation, not per file"
     for f, module in DIRECT.items():
         assert source_kernels([f]), "DIRECT names a file without kernels: " + f
