@@ -26,6 +26,18 @@
 //              vis_track_gather_kernel — mask mode: the packed words and areas of the next table, row by row from the new instances or
 //                                        the old table, into the other half of the ping-pong pair.
 //              The counters (n_tracks, next_id, dropped) stay on the device; nothing is read back.
+//   contours : the exact outlines of the packed masks as loops of lattice vertices (DESIGN §3 "Contours"), two phases around one host read:
+//              vis_contour_count_kernel   — a thread per 64 vertices of a lattice row: corner and saddle bits from four shifted row windows,
+//                                           their popcounts scanned over 1024 such words in the same pass;
+//              vis_contour_offsets_kernel — ONE workgroup scans the block totals of all masks: record numbers, offsets, totals per mask;
+//              vis_contour_emit_kernel    — the corner records (x, y, out direction, mask) in lattice row-major order = canonical order;
+//              vis_contour_link_kernel    — a wave per record: a horizontal edge ends at record i ^ 1, a vertical one is followed 64 rows
+//                                           per ballot to the next corner of its column;
+//              vis_contour_jump_kernel    — pointer jumping, one launch per round between ping-pong buffers: the smallest record of every
+//                                           loop (its start) and the steps to it;
+//              vis_contour_lens_kernel, vis_contour_blocks_kernel, vis_contour_place_kernel — the loop lengths scanned in three launches:
+//                                           where every loop goes; vis_contour_write_kernel puts every vertex there.
+//              No kernel waits for another workgroup; every loop's trip count is bounded by an argument.
 // Every store is an ordinary vector store, the atomics are vector atomics.
 #include "cmk_common.hpp"
 
@@ -501,6 +513,309 @@ inline int vis_check_width(const char* what, const char* name, int v) {
     return CMK_EINVAL;
 }
 
+// ---- contours: exact outlines of the packed masks ---------------------------------------------------------------------------------
+// A lattice row y in [0, H] of a mask is LW = ceil((W + 1) / 64) words of 64 vertices; entry e = y * LW + k is word k of row y, NE =
+// (H + 1) * LW entries per mask.  Of the 2x2 pixels around vertex (x, y), bit x - 64 k of ne/nwb is pixel (y - 1, x) / (y - 1, x - 1), of
+// se/sw pixel (y, x) / (y, x - 1).  A vertex with one or three of them set is a corner (one record), one with the two diagonal ones set a
+// saddle (two records).  Records are numbered in lattice row-major order, the two of a saddle with the pass whose horizontal edge lies to
+// the left first: the corners of a lattice row then pair up (2m, 2m + 1) into its horizontal segments, and the number of a record is its
+// canonical (y, x) rank.  Directions: 0 +x, 1 +y, 2 -x, 3 -y (y down, foreground on the right).
+constexpr int VC_BLOCK = 1024;       // records or entries per workgroup of the scans
+constexpr long VC_LINK_GRID = 1L << 22;       // workgroups of the link kernel at most: 2^32 threads in x are never reached
+
+// columns x0 .. x0 + 63 of row y as 64 bits; columns outside [0, W) and rows outside [0, H) read as zero
+__device__ inline unsigned long long vis_contour_row64(const unsigned long long* __restrict__ w, int nw, int H, int W, int y, long x0) {
+    if (y < 0 || y >= H || x0 >= W || x0 <= -64) return 0ull;
+    unsigned long long v = vis_bits64(w, (long)y * W + x0, nw);
+    if (x0 < 0) v &= ~0ull << (int)(-x0);
+    const long n = (long)W - x0;
+    if (n < 64) v &= (1ull << n) - 1ull;
+    return v;
+}
+
+struct VisContourBits {
+    unsigned long long ne, nwb, se, sw, corner, saddle;
+};
+
+__device__ inline VisContourBits vis_contour_bits(const unsigned long long* __restrict__ w, int nw, int H, int W, int y, int k) {
+    VisContourBits b;
+    const long x0 = (long)k * 64;
+    b.ne = vis_contour_row64(w, nw, H, W, y - 1, x0), b.nwb = vis_contour_row64(w, nw, H, W, y - 1, x0 - 1);
+    b.se = vis_contour_row64(w, nw, H, W, y, x0), b.sw = vis_contour_row64(w, nw, H, W, y, x0 - 1);
+    b.corner = b.ne ^ b.nwb ^ b.se ^ b.sw;
+    b.saddle = (b.ne ^ b.nwb) & (b.se ^ b.sw) & (b.ne ^ b.se);
+    return b;
+}
+
+// records in front of vertex bit j of an entry
+__device__ inline int vis_contour_rank(const VisContourBits& b, int j) {
+    const unsigned long long below = (1ull << j) - 1ull;
+    return __popcll(b.corner & below) + 2 * __popcll(b.saddle & below);
+}
+
+__device__ inline int vis_contour_pix(const unsigned long long* __restrict__ w, int H, int W, int y, int x) {
+    if (x < 0 || x >= W || y < 0 || y >= H) return 0;
+    const long p = (long)y * W + x;
+    return (int)((w[p >> 6] >> (p & 63)) & 1ull);
+}
+
+// exclusive scan of one value per thread over the VC_BLOCK threads of a workgroup; total: their sum
+__device__ inline long long vis_contour_block_scan(long long v, long long* wsum, long long& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();                                                 // the readers of the scan before this one are done with wsum
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    long long before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < VC_BLOCK / 64; ++k) {
+        const long long s = wsum[k];
+        before += k < wave ? s : 0;
+        total += s;
+    }
+    return before + inc - v;
+}
+
+// grid = (NB = ceil(NE / VC_BLOCK), R), one pass over the words: inc[r][e] = records of the entries of e's block up to and with e,
+// grp[r][block] = records of the block
+__global__ __launch_bounds__(VC_BLOCK) void vis_contour_count_kernel(const unsigned long long* __restrict__ words, int nw, int H, int W, int LW, long NE,
+                                                                    int32_t* __restrict__ inc, long long* __restrict__ grp) {
+    __shared__ long long wsum[VC_BLOCK / 64];
+    const long e = (long)blockIdx.x * VC_BLOCK + threadIdx.x;
+    const int r = blockIdx.y;
+    long long v = 0;
+    if (e < NE) {
+        const int y = (int)(e / LW), k = (int)(e - (long)y * LW);
+        const VisContourBits b = vis_contour_bits(words + (long)r * nw, nw, H, W, y, k);
+        v = __popcll(b.corner) + 2 * __popcll(b.saddle);
+    }
+    long long total;
+    const long long ex = vis_contour_block_scan(v, wsum, total);
+    if (e < NE) inc[(long)r * NE + e] = (int32_t)(ex + v);           // at most 128 * VC_BLOCK
+    if (threadIdx.x == 0) grp[(long)r * gridDim.x + blockIdx.x] = total;
+}
+
+// grid = 1: grp (R * NB block totals, masks in order) -> their exclusive prefix sums in place: the number of the first record of every
+// block among the records of all masks; off[r] = that of mask r, off[R] = all, n_corners[r] = off[r + 1] - off[r] (-1 beyond int32)
+__global__ __launch_bounds__(VC_BLOCK) void vis_contour_offsets_kernel(long long* __restrict__ grp, int R, int NB, long long* __restrict__ off,
+                                                                      int32_t* __restrict__ n_corners) {
+    __shared__ long long wsum[VC_BLOCK / 64];
+    const long n = (long)R * NB;
+    long long carry = 0;
+    for (long base = 0; base < n; base += VC_BLOCK) {
+        const long g = base + threadIdx.x;
+        const long long v = g < n ? grp[g] : 0;
+        long long total;
+        const long long ex = carry + vis_contour_block_scan(v, wsum, total);
+        if (g < n) grp[g] = ex;
+        carry += total;
+    }
+    __syncthreads();                                                 // the prefix sums are in memory for every thread of the workgroup
+    for (int r = threadIdx.x; r < R; r += VC_BLOCK) {
+        const long long a = grp[(long)r * NB], b = r + 1 < R ? grp[(long)(r + 1) * NB] : carry;
+        off[r] = a;
+        n_corners[r] = b - a > 0x7fffffffLL ? -1 : (int32_t)(b - a);
+    }
+    if (threadIdx.x == 0) off[R] = carry;
+}
+
+// the number of the first record of entry e among the records of all masks; count: the records of the entry
+__device__ inline long long vis_contour_first(const int32_t* __restrict__ inc, const long long* __restrict__ grp, long e, int& count) {
+    const int here = inc[e], prev = (e & (VC_BLOCK - 1)) ? inc[e - 1] : 0;
+    count = here - prev;
+    return grp[e / VC_BLOCK] + prev;
+}
+
+// grid = (ceil(NE / 256), R), a thread per entry; an entry without a corner reads two counts and no row.  rec[i] = (x, y, out direction,
+// mask) for the corners of the entry in order of x, at most 64 trips
+__global__ __launch_bounds__(256) void vis_contour_emit_kernel(const unsigned long long* __restrict__ words, int nw, int H, int W, int LW, long NE,
+                                                              int NB, const int32_t* __restrict__ inc, const long long* __restrict__ grp, int T,
+                                                              int4* __restrict__ rec) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    const int r = blockIdx.y;
+    int count;
+    long long i = vis_contour_first(inc + (long)r * NE, grp + (long)r * NB, e, count);
+    if (count <= 0) return;
+    const int y = (int)(e / LW), k = (int)(e - (long)y * LW);
+    const VisContourBits b = vis_contour_bits(words + (long)r * nw, nw, H, W, y, k);
+    unsigned long long any = b.corner | b.saddle;
+    for (int t = 0; t < 64 && any; ++t) {
+        const int j = __builtin_ctzll(any);
+        any &= any - 1ull;
+        const bool sad = (b.saddle >> j) & 1ull;
+        if (i < 0 || i + (sad ? 1 : 0) >= (long long)T) return;      // never outside the T records the host sized, whatever ws holds
+        const int NWp = (int)((b.nwb >> j) & 1ull), NEp = (int)((b.ne >> j) & 1ull), SWp = (int)((b.sw >> j) & 1ull), SEp = (int)((b.se >> j) & 1ull);
+        const int x = k * 64 + j;
+        if (sad) {
+            rec[i] = make_int4(x, y, NWp ? 2 : 1, r);
+            rec[i + 1] = make_int4(x, y, NWp ? 0 : 3, r);
+            i += 2;
+        } else {
+            rec[i] = make_int4(x, y, (SEp && !NEp) ? 0 : ((SWp && !SEp) ? 1 : ((NWp && !SWp) ? 2 : 3)), r);
+            i += 1;
+        }
+    }
+}
+
+// one record of the link kernel, by one wave: everything is wave-uniform but the row a lane tests
+__device__ inline void vis_contour_link_one(const unsigned long long* __restrict__ words, int nw, int R, int H, int W, int LW, long NE, int NB,
+                                            const int32_t* __restrict__ inc, const long long* __restrict__ grp, int T, const int4* __restrict__ rec,
+                                            int32_t* __restrict__ succ, long i, int lane) {
+    const int4 q = rec[i];
+    const int x = q.x, y = q.y, d = q.z, r = q.w;
+    long long s = i;
+    if (r >= 0 && r < R && x >= 0 && x <= W && y >= 0 && y <= H) {   // a record nobody wrote links to itself and reads nothing
+        if (d == 0 || d == 2) {
+            s = i ^ 1;
+        } else if (d == 1 || d == 3) {
+            const unsigned long long* w = words + (long)r * nw;
+            int yy = d == 1 ? H : 0;
+            const int trips = cdiv(H, 64) + 1;
+            for (int t = 0; t < trips; ++t) {
+                bool stop;
+                int cand;
+                if (d == 1) {                                        // down while the row below the vertex still has (set, unset)
+                    cand = y + 1 + t * 64 + lane;
+                    stop = cand >= H || !(vis_contour_pix(w, H, W, cand, x - 1) && !vis_contour_pix(w, H, W, cand, x));
+                } else {                                             // up while the row above the vertex still has (unset, set)
+                    cand = y - 1 - t * 64 - lane;
+                    stop = cand <= 0 || !(!vis_contour_pix(w, H, W, cand - 1, x - 1) && vis_contour_pix(w, H, W, cand - 1, x));
+                }
+                const unsigned long long hit = __ballot(stop);
+                if (hit) {
+                    yy = __shfl(cand, __builtin_ctzll(hit), 64);
+                    break;
+                }
+            }
+            yy = min(max(yy, 0), H);
+            const int k = x >> 6, j = x & 63;
+            const VisContourBits b = vis_contour_bits(w, nw, H, W, yy, k);
+            int count;
+            s = vis_contour_first(inc + (long)r * NE, grp + (long)r * NB, (long)yy * LW + k, count) + vis_contour_rank(b, j) +
+                ((((b.saddle >> j) & 1ull) && d == 3) ? 1 : 0);
+        }
+    }
+    if (lane == 0) succ[i] = (s < 0 || s >= (long long)T) ? (int32_t)i : (int32_t)s;
+}
+
+// grid = min(ceil(T / 4), VC_LINK_GRID), a wave per record, striding: succ[i] = the record the out edge of record i ends at.  A
+// horizontal edge ends at record i ^ 1.  A vertical one is followed along its column to the next corner, 64 lattice rows per trip (lane = row, the first lane whose row ends
+// the edge wins the ballot), at most ceil(H / 64) + 1 trips; that corner's number is the first of its entry + its rank (+ 1 for the pass
+// of a saddle that arrives going up: the walk turns right).
+__global__ __launch_bounds__(256) void vis_contour_link_kernel(const unsigned long long* __restrict__ words, int nw, int R, int H, int W, int LW, long NE,
+                                                              int NB, const int32_t* __restrict__ inc, const long long* __restrict__ grp, int T,
+                                                              const int4* __restrict__ rec, int32_t* __restrict__ succ) {
+    const int lane = threadIdx.x & 63;
+    for (long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6); i < T; i += (long)gridDim.x * 4)       // wave-uniform
+        vis_contour_link_one(words, nw, R, H, W, LW, NE, NB, inc, grp, T, rec, succ, i, lane);
+}
+
+// grid = ceil(T / 256), round k of the pointer jumping with hop = 2^k: lab[i] = the smallest record number among the 2 hop records from i
+// along the loop, dist[i] = the steps from i to its first occurrence, s[i] = the record 2 hop steps on.  first: lab = i, dist = 0.
+__global__ __launch_bounds__(256) void vis_contour_jump_kernel(const int32_t* __restrict__ s_in, const int32_t* __restrict__ lab_in,
+                                                              const int32_t* __restrict__ dist_in, int32_t* __restrict__ s_out,
+                                                              int32_t* __restrict__ lab_out, int32_t* __restrict__ dist_out, int T, int hop, int first) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= T) return;
+    int j = s_in[i];
+    if (j < 0 || j >= T) j = (int)i;
+    int li = first ? (int)i : lab_in[i], di = first ? 0 : dist_in[i];
+    const int lj = first ? j : lab_in[j], dj = first ? 0 : dist_in[j];
+    if (lj < li) li = lj, di = hop + dj;                             // an equal label is the same record met again: the earlier one stays
+    int sj = s_in[j];
+    if (sj < 0 || sj >= T) sj = j;
+    s_out[i] = sj, lab_out[i] = li, dist_out[i] = di;
+}
+
+// the vertices of the loop that starts at record i, 0 for a record that starts none
+__device__ inline int vis_contour_loop_len(const int32_t* __restrict__ succ, const int32_t* __restrict__ lab, const int32_t* __restrict__ dist, int T,
+                                           long i) {
+    if (i >= T || lab[i] != (int)i) return 0;
+    const int s = succ[i];
+    return s >= 0 && s < T ? 1 + dist[s] : 1;
+}
+
+// grid = ceil(T / VC_BLOCK): bsum[b] = vertices of the loops that start in block b
+__global__ __launch_bounds__(VC_BLOCK) void vis_contour_lens_kernel(const int32_t* __restrict__ succ, const int32_t* __restrict__ lab,
+                                                                   const int32_t* __restrict__ dist, int T, int32_t* __restrict__ bsum) {
+    __shared__ long long wsum[VC_BLOCK / 64];
+    const long i = (long)blockIdx.x * VC_BLOCK + threadIdx.x;
+    long long total;
+    vis_contour_block_scan(vis_contour_loop_len(succ, lab, dist, T, i), wsum, total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = (int32_t)(total > 0x7fffffffLL ? 0x7fffffffLL : total);
+}
+
+// grid = 1: bsum -> its exclusive prefix sums in place
+__global__ __launch_bounds__(VC_BLOCK) void vis_contour_blocks_kernel(int32_t* __restrict__ bsum, int nb) {
+    __shared__ long long wsum[VC_BLOCK / 64];
+    long long carry = 0;
+    for (int base = 0; base < nb; base += VC_BLOCK) {
+        const int b = base + threadIdx.x;
+        const long long v = b < nb ? bsum[b] : 0;
+        long long total;
+        const long long ex = carry + vis_contour_block_scan(v, wsum, total);
+        if (b < nb) bsum[b] = (int32_t)(ex > 0x7fffffffLL ? 0x7fffffffLL : ex);
+        carry += total;
+    }
+}
+
+// grid = ceil(T / VC_BLOCK): lo[i] = the output position of the loop that starts at record i: the vertices of all loops that start earlier
+__global__ __launch_bounds__(VC_BLOCK) void vis_contour_place_kernel(const int32_t* __restrict__ succ, const int32_t* __restrict__ lab,
+                                                                    const int32_t* __restrict__ dist, int T, const int32_t* __restrict__ bsum,
+                                                                    int32_t* __restrict__ lo) {
+    __shared__ long long wsum[VC_BLOCK / 64];
+    const long i = (long)blockIdx.x * VC_BLOCK + threadIdx.x;
+    long long total;
+    const long long ex = bsum[blockIdx.x] + vis_contour_block_scan(vis_contour_loop_len(succ, lab, dist, T, i), wsum, total);
+    if (i < T) lo[i] = (int32_t)(ex > 0x7fffffffLL ? 0x7fffffffLL : ex);
+}
+
+// grid = ceil(T / 256): record i goes to the position of its loop + its rank in the walk from the loop's start
+__global__ __launch_bounds__(256) void vis_contour_write_kernel(const int4* __restrict__ rec, const int32_t* __restrict__ succ,
+                                                               const int32_t* __restrict__ lab, const int32_t* __restrict__ dist,
+                                                               const int32_t* __restrict__ lo, int T, int32_t* __restrict__ xy,
+                                                               int32_t* __restrict__ head) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= T) return;
+    int l = lab[i];
+    if (l < 0 || l >= T) l = (int)i;
+    const int d = dist[i];
+    const int len = vis_contour_loop_len(succ, lab, dist, T, l);
+    const long long pos = (long long)lo[l] + (d == 0 ? 0 : len - d);
+    if (pos < 0 || pos >= (long long)T) return;
+    const int4 q = rec[i];
+    xy[2 * pos] = q.x, xy[2 * pos + 1] = q.y;
+    head[pos] = d == 0 ? 1 : 0;
+}
+
+inline long vis_contour_lw(int W) { return ((long)W + 1 + 63) / 64; }
+inline long vis_contour_entries(int H, int W) { return ((long)H + 1) * vis_contour_lw(W); }
+inline long vis_contour_groups(int H, int W) { return (vis_contour_entries(H, W) + VC_BLOCK - 1) / VC_BLOCK; }
+// [off R + 1 int64 | grp R * NB int64 | inc R * NE int32]
+inline int64_t vis_contour_ws_bytes(int R, int H, int W) {
+    return 8 * ((int64_t)R + 1) + 8 * (int64_t)R * vis_contour_groups(H, W) + 4 * (int64_t)R * vis_contour_entries(H, W);
+}
+inline int64_t vis_contour_blocks(int64_t T) { return (T + VC_BLOCK - 1) / VC_BLOCK; }
+// [rec 16 T | succ, 2 x (s, lab, dist), lo: 8 x 4 T | bsum 4 nb]
+inline int64_t vis_contour_trace_bytes(int64_t T) { return T <= 0 ? 0 : 48 * T + 4 * vis_contour_blocks(T); }
+
+// shared argument check of the two phases; the messages name the entry
+inline int vis_contour_check(const char* what, int R, int H, int W, const void* ws, int64_t ws_bytes, bool any_null) {
+    if (int rc = vis_check(what, H, W, R)) return rc;
+    if (any_null) return fail(CMK_EINVAL, "%s: null pointer", what);
+    if ((uintptr_t)ws & 7) return fail(CMK_EINVAL, "%s: workspace is not 8-byte aligned", what);
+    if (ws_bytes < vis_contour_ws_bytes(R, H, W))
+        return fail(CMK_EINVAL, "%s: workspace of %ld bytes, need %ld", what, (long)ws_bytes, (long)vis_contour_ws_bytes(R, H, W));
+    return CMK_OK;
+}
+
 }  // namespace cmk
 
 using namespace cmk;
@@ -623,4 +938,95 @@ extern "C" int cmk_vis_keypoints(uint8_t* image, int H, int W, const float* keyp
     hipLaunchKernelGGL(vis_kp_colour_kernel, dim3(stream_grid(HW)), dim3(256), 0, st, image, (long)HW, (const int32_t*)winner, records, num_segments,
                        num_keypoints, keypoint_color);
     return check_launch("vis_keypoints");
+}
+
+extern "C" int64_t cmk_vis_contour_ws_bytes(int R, int H, int W) {
+    if (R < 0 || R > 65535 || H < 1 || W < 1 || (int64_t)H * W >= 0x7fffffffLL) return 0;
+    return vis_contour_ws_bytes(R, H, W);
+}
+
+extern "C" int64_t cmk_vis_contour_trace_ws_bytes(int total) { return vis_contour_trace_bytes(total); }
+
+extern "C" int cmk_vis_contour_count(const uint64_t* words, int R, int H, int W, void* ws, int64_t ws_bytes, int32_t* n_corners, void* stream) {
+    const char* what = "vis_contour_count";
+    if (R == 0) return CMK_OK;
+    if (int rc = vis_contour_check(what, R, H, W, ws, ws_bytes, !words || !ws || !n_corners)) return rc;
+    const int nw = (int)(((int64_t)H * W + 63) / 64);
+    const int64_t in_bytes = (int64_t)R * nw * 8, need = vis_contour_ws_bytes(R, H, W);
+    if (vis_overlap(ws, need, words, in_bytes) || vis_overlap(n_corners, 4 * (int64_t)R, words, in_bytes) ||
+        vis_overlap(n_corners, 4 * (int64_t)R, ws, need))
+        return fail(CMK_EINVAL, "%s: the workspace or n_corners overlaps the words or each other", what);
+    hipStream_t st = (hipStream_t)stream;
+    const int LW = (int)vis_contour_lw(W), NB = (int)vis_contour_groups(H, W);
+    const long NE = vis_contour_entries(H, W);
+    long long* off = (long long*)ws;
+    long long* grp = off + R + 1;
+    int32_t* inc = (int32_t*)(grp + (long)R * NB);
+    hipLaunchKernelGGL(vis_contour_count_kernel, dim3(NB, R), dim3(VC_BLOCK), 0, st, (const unsigned long long*)words, nw, H, W, LW, NE, inc, grp);
+    hipLaunchKernelGGL(vis_contour_offsets_kernel, dim3(1), dim3(VC_BLOCK), 0, st, grp, R, NB, off, n_corners);
+    return check_launch(what);
+}
+
+extern "C" int cmk_vis_contour_trace(const uint64_t* words, int R, int H, int W, const void* ws, int64_t ws_bytes, const int32_t* n_corners,
+                                     void* scratch, int64_t scratch_bytes, int32_t* xy, int32_t* head, void* stream) {
+    const char* what = "vis_contour_trace";
+    if (R == 0) return CMK_OK;
+    if (int rc = vis_contour_check(what, R, H, W, ws, ws_bytes, !words || !ws || !n_corners)) return rc;
+    int64_t T = 0;
+    int32_t longest = 0;
+    for (int r = 0; r < R; ++r) {
+        const int32_t n = n_corners[r];                              // host memory: the totals the caller read back
+        if (n < 0 || (n & 1)) return fail(CMK_EINVAL, "%s: n_corners[%ld] = %ld is negative or odd", what, r, n);
+        T += n;
+        longest = n > longest ? n : longest;
+    }
+    if (T > 0x7fffffffLL) return fail(CMK_EINVAL, "%s: the corners of all masks, %ld, do not fit int32", what, (long)T);
+    if (T == 0) return CMK_OK;
+    if (!scratch || !xy || !head) return fail(CMK_EINVAL, "%s: null pointer", what);
+    if ((uintptr_t)scratch & 15) return fail(CMK_EINVAL, "%s: scratch is not 16-byte aligned", what);
+    if (scratch_bytes < vis_contour_trace_bytes(T))
+        return fail(CMK_EINVAL, "%s: scratch of %ld bytes, need %ld", what, (long)scratch_bytes, (long)vis_contour_trace_bytes(T));
+    const int nw = (int)(((int64_t)H * W + 63) / 64);
+    const int64_t in_bytes = (int64_t)R * nw * 8, ws_need = vis_contour_ws_bytes(R, H, W), sc_need = vis_contour_trace_bytes(T);
+    const void* outs[3] = {xy, head, scratch};
+    const int64_t out_bytes[3] = {8 * T, 4 * T, sc_need};
+    for (int a = 0; a < 3; ++a) {
+        if (vis_overlap(outs[a], out_bytes[a], words, in_bytes) || vis_overlap(outs[a], out_bytes[a], ws, ws_need))
+            return fail(CMK_EINVAL, "%s: xy, head or scratch overlaps the words or the workspace; the trace is out of place", what);
+        for (int b = a + 1; b < 3; ++b)
+            if (vis_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b])) return fail(CMK_EINVAL, "%s: xy, head and scratch overlap each other", what);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int LW = (int)vis_contour_lw(W), NB = (int)vis_contour_groups(H, W);
+    const long NE = vis_contour_entries(H, W);
+    const long long* grp = (const long long*)ws + R + 1;
+    const int32_t* inc = (const int32_t*)(grp + (long)R * NB);
+    const int Ti = (int)T, nb = (int)vis_contour_blocks(T);
+    int4* rec = (int4*)scratch;
+    int32_t* succ = (int32_t*)(rec + T);
+    int32_t* buf[2][3] = {{succ + T, succ + 2 * T, succ + 3 * T}, {succ + 4 * T, succ + 5 * T, succ + 6 * T}};
+    int32_t* lo = succ + 7 * T;
+    int32_t* bsum = succ + 8 * T;
+    const dim3 per_record((unsigned)((T + 255) / 256));
+    const unsigned long long* w = (const unsigned long long*)words;
+    hipLaunchKernelGGL(vis_contour_emit_kernel, dim3((unsigned)((NE + 255) / 256), R), dim3(256), 0, st, w, nw, H, W, LW, NE, NB, inc, grp, Ti, rec);
+    const int64_t link_grid = (T + 3) / 4 < VC_LINK_GRID ? (T + 3) / 4 : VC_LINK_GRID;
+    hipLaunchKernelGGL(vis_contour_link_kernel, dim3((unsigned)link_grid), dim3(256), 0, st, w, nw, R, H, W, LW, NE, NB, inc, grp, Ti,
+                       (const int4*)rec, succ);
+    // after round k a record has seen 2^(k+1) records of its loop, and no loop is longer than the corners of its mask
+    int cur = 0;
+    for (int k = 0; (1LL << k) < longest; ++k) {
+        const int32_t* const* in = k ? buf[cur ^ 1] : nullptr;
+        hipLaunchKernelGGL(vis_contour_jump_kernel, per_record, dim3(256), 0, st, k ? in[0] : (const int32_t*)succ, k ? in[1] : nullptr,
+                           k ? in[2] : nullptr, buf[cur][0], buf[cur][1], buf[cur][2], Ti, (int)(1LL << k), k ? 0 : 1);
+        cur ^= 1;
+    }
+    const int32_t* lab = buf[cur ^ 1][1];
+    const int32_t* dist = buf[cur ^ 1][2];
+    hipLaunchKernelGGL(vis_contour_lens_kernel, dim3(nb), dim3(VC_BLOCK), 0, st, (const int32_t*)succ, lab, dist, Ti, bsum);
+    hipLaunchKernelGGL(vis_contour_blocks_kernel, dim3(1), dim3(VC_BLOCK), 0, st, bsum, nb);
+    hipLaunchKernelGGL(vis_contour_place_kernel, dim3(nb), dim3(VC_BLOCK), 0, st, (const int32_t*)succ, lab, dist, Ti, (const int32_t*)bsum, lo);
+    hipLaunchKernelGGL(vis_contour_write_kernel, per_record, dim3(256), 0, st, (const int4*)rec, (const int32_t*)succ, lab, dist, (const int32_t*)lo,
+                       Ti, xy, head);
+    return check_launch(what);
 }

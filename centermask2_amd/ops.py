@@ -1649,6 +1649,79 @@ def mask_boundary(masks: torch.Tensor, dilation: Optional[int] = None) -> torch.
     return mask_unpack_bits(bwords, h, w)
 
 
+def _contour_count(words: torch.Tensor, h: int, w: int):
+    """Count phase of mask_contours_bits -> (ws, ws_bytes, n_corners on the device).  Launches only."""
+    lib = _lib.load()
+    r = int(words.shape[0])
+    ws_bytes = lib.cmk_vis_contour_ws_bytes(r, int(h), int(w))
+    if ws_bytes <= 0:
+        raise _lib.CmkError("mask_contours_bits: {} masks of {}x{} are outside what the contour kernels take (include/cmk.h)".format(r, h, w))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=words.device)
+    n_dev = torch.empty((r,), dtype=torch.int32, device=words.device)
+    check(lib.cmk_vis_contour_count(words.data_ptr(), r, int(h), int(w), ws.data_ptr(), ws_bytes, n_dev.data_ptr(), _stream()),
+          "cmk_vis_contour_count")
+    return ws, ws_bytes, n_dev
+
+
+def _contour_trace(words: torch.Tensor, h: int, w: int, ws: torch.Tensor, ws_bytes: int, n_host) -> torch.Tensor:
+    """Trace phase of mask_contours_bits: n_host the totals as a contiguous int32 NumPy array, their sum T > 0 -> int32 (3 T,) on the
+    device, [xy 2 T | head T].  Launches only."""
+    lib = _lib.load()
+    total = int(n_host.astype("int64").sum())
+    scratch_bytes = lib.cmk_vis_contour_trace_ws_bytes(total)
+    scratch = torch.empty((scratch_bytes,), dtype=torch.uint8, device=words.device)
+    out = torch.empty((3 * total,), dtype=torch.int32, device=words.device)
+    p = out.data_ptr()
+    check(lib.cmk_vis_contour_trace(words.data_ptr(), int(words.shape[0]), int(h), int(w), ws.data_ptr(), ws_bytes, n_host.ctypes.data,
+                                    scratch.data_ptr(), scratch_bytes, p, p + 8 * total, _stream()), "cmk_vis_contour_trace")
+    return out
+
+
+def _contour_split(host, n_host):
+    """[xy 2 T | head T] on the host and the totals per mask -> per mask the list of its loops, (k,2) int32 arrays."""
+    import numpy as np
+    total = int(n_host.astype("int64").sum())
+    xy, head = host[:2 * total].reshape(total, 2), host[2 * total:]
+    starts = np.flatnonzero(head)
+    out, off = [], 0
+    for n in n_host.tolist():
+        cuts = starts[np.searchsorted(starts, off):np.searchsorted(starts, off + n)]
+        out.append([xy[a:b].copy() for a, b in zip(cuts, list(cuts[1:]) + [off + n])])
+        off += n
+    return out
+
+
+def mask_contours_bits(words: torch.Tensor, h: int, w: int):
+    """Packed masks (R, mask_words(h,w)) int64 on the GPU -> a list of R lists of np.int32 arrays (k,2): the closed loops of lattice
+    vertices (x, y) that outline each mask exactly (include/cmk.h, DESIGN §3 "Contours": foreground 4-connected and on the right of the
+    walk, right turn at a saddle, corners only, a loop starts at its smallest (y, x) vertex, loops sorted by start, outer boundaries
+    with a positive doubled area and holes with a negative one).  No bitmap is touched.  Two host synchronisations: the corner totals
+    after the count phase, which size every buffer exactly, then one download of vertices and loop heads."""
+    import numpy as np
+    words = _need_words(words, h, w, "mask_contours_bits")
+    r = int(words.shape[0])
+    if r == 0:
+        return []
+    ws, ws_bytes, n_dev = _contour_count(words, h, w)
+    n_host = np.ascontiguousarray(n_dev.cpu().numpy(), dtype=np.int32)  # synchronisation 1
+    if (n_host < 0).any() or int(n_host.astype("int64").sum()) > 2 ** 31 - 1:
+        raise _lib.CmkError("mask_contours_bits: the corners of the masks do not fit int32")
+    if int(n_host.sum()) == 0:
+        return [[] for _ in range(r)]
+    host = _contour_trace(words, h, w, ws, ws_bytes, n_host).cpu().numpy()   # synchronisation 2
+    return _contour_split(host, n_host)
+
+
+def mask_contours(masks: torch.Tensor):
+    """(R,H,W) bool bitmasks on the GPU -> their contours as mask_contours_bits gives them, packed first (mask_pack_bits); the bitmaps
+    are not downloaded.  wire.mask_contours_host is the host path, wire.contours_to_polygons turns the result into COCO polygons."""
+    masks = _need_bitmasks(masks, "mask_contours")
+    if masks.shape[0] == 0:
+        return []
+    words, _ = mask_pack_bits(masks)
+    return mask_contours_bits(words, int(masks.shape[1]), int(masks.shape[2]))
+
+
 def mask_boundary_intersections(det_masks: torch.Tensor, gt_counts, h: int, w: int, dilation: int):
     """mask_intersections and the same for the boundaries of the masks (Boundary IoU): -> (inter (N,M), det_areas (N,), gt_areas (M,),
     inter_b (N,M), det_areas_b (N,), gt_areas_b (M,)), int32 CPU tensors.  The detections are packed and the ground truths decoded once,

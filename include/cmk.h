@@ -576,6 +576,34 @@ int cmk_vis_track_gather(const int32_t* src, const int32_t* counters, const uint
                          const uint64_t* new_words, const int32_t* new_areas, int n, int rows, int max_tracks, int H, int W,
                          uint64_t* out_words, int32_t* out_areas, void* stream);
 
+/* ---- mask contours: the exact outlines of packed masks as closed loops of int32 lattice vertices (x, y), 0 <= x <= W, 0 <= y <= H
+ * (the reference's visualizer.py:35-37 reaches polygons through detectron2's GenericMask.mask_to_polygons; the rule here is this
+ * package's own, DESIGN §3 "Contours").  Pixel (row r, column c) is the square [c, c+1] x [r, r+1], outside the image is background,
+ * foreground is 4-connected.  Every unit edge between a set and an unset pixel is walked once with the foreground on the right (a set
+ * pixel's top edge runs +x, its right edge +y, with y down); at a saddle vertex (the two set pixels of the 2x2 diagonal) the walk turns
+ * right.  Only corners are emitted.  A loop starts at its smallest vertex in (y, x) order, the loops of a mask are sorted by that start.
+ * Outer boundaries have a positive doubled area sum(x_i*y_{i+1} - x_{i+1}*y_i), holes a negative one.
+ * Two phases around one host read of the corner totals, as the RLE entries.  words: R packed masks as cmk_mask_pack_bits writes them.
+ * ws: cmk_vis_contour_ws_bytes(R, H, W) bytes, 8-byte aligned (0 for arguments the launches refuse): R+1 int64 corner offsets, one int64
+ * per (mask, 1024 words of its vertex lattice), then one int32 per (mask, lattice row, 64 vertices of it).  Refused by both phases before any launch: null pointers, H or W < 1,
+ * H*W >= 2^31 - 1, R outside [0, 65535], a workspace too small, outputs that overlap the inputs.  R == 0 is CMK_OK with no launch.
+ * Nothing is allocated or synchronised. */
+int64_t cmk_vis_contour_ws_bytes(int R, int H, int W);
+/* visualizer.py:35-37, count phase: n_corners[r] (device, R int32) = vertices of all loops of mask r, always even (-1 where they do not
+ * fit int32); ws keeps the scanned offsets for the trace phase. */
+int cmk_vis_contour_count(const uint64_t* words, int R, int H, int W, void* ws, int64_t ws_bytes, int32_t* n_corners, void* stream);
+/* Scratch bytes of the trace phase for `total` corners (0 for a negative total): corner records, successor links and the ping-pong
+ * buffers of the loop ranking. */
+int64_t cmk_vis_contour_trace_ws_bytes(int total);
+/* visualizer.py:35-37, trace phase, after cmk_vis_contour_count on the same words and ws.  n_corners: the R totals the count phase
+ * wrote, read back by the caller and passed here in HOST memory; with T their sum and off[r] the sum of n_corners[0..r), xy (device,
+ * 2*T int32) gets the vertices of mask r at off[r] as x, y pairs, loop after loop in canonical order, and head (device, T int32) is 1 at
+ * the first vertex of every loop, else 0.  scratch: cmk_vis_contour_trace_ws_bytes(T) bytes on the device, 16-byte aligned.  Also
+ * refused: an n_corners that is negative or odd, a T that does not fit int32, a scratch too small.  T == 0 launches nothing.  No kernel
+ * writes outside [0, T) whatever the device totals are. */
+int cmk_vis_contour_trace(const uint64_t* words, int R, int H, int W, const void* ws, int64_t ws_bytes, const int32_t* n_corners,
+                          void* scratch, int64_t scratch_bytes, int32_t* xy, int32_t* head, void* stream);
+
 /* ---- multi-GPU result exchange (the reference's analogue: comm.gather in evaluation/coco_evaluation.py:155-156) ----------
  * One fixed-stride float record per image, written straight into the all-gather send buffer:
  * [box 4K | score K | mask_score K | loc 2K | class K (as float) | mask K*hw*hw | count], K*(9 + hw*hw) + 1 floats.

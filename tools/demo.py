@@ -2,10 +2,13 @@
 detectron2's matplotlib renderer and without an imaging library).
 
     python tools/demo.py CONFIG IMAGE OUT.png [--weights FILE] [--min-size N --max-size N] [--score-threshold T]
+                         [--json OUT.json [--segmentation rle|polygon]]
 
 CONFIG is a yaml of centermask2_amd/configs (a bare file name is looked up there); IMAGE is a binary P6 `.ppm` or a `.npy` holding an
 (h,w,3) uint8 array in the config's INPUT.FORMAT channel order (a .ppm is RGB on disk and is converted).  Without --weights and without
-MODEL.WEIGHTS a VoVNet config gets the seeded synthetic weights, which detect arbitrary things: good for trying the tools, nothing else."""
+MODEL.WEIGHTS a VoVNet config gets the seeded synthetic weights, which detect arbitrary things: good for trying the tools, nothing else.
+--json also writes the detections as COCO results (wire.instances_to_coco_json, image_id 0), their masks as compressed RLE or as the
+polygons of their outer boundaries, traced on the device (holes are not represented in polygons)."""
 import argparse
 import os
 import sys
@@ -23,6 +26,8 @@ def main():
     ap.add_argument("--score-threshold", type=float, default=None, help="draw only detections at or above this score")
     ap.add_argument("--min-size", type=int, default=None, help="INPUT.MIN_SIZE_TEST")
     ap.add_argument("--max-size", type=int, default=None, help="INPUT.MAX_SIZE_TEST")
+    ap.add_argument("--json", default=None, help="also write the detections as COCO results to this file")
+    ap.add_argument("--segmentation", choices=("rle", "polygon"), default="rle", help="form of the masks in --json")
     a = ap.parse_args()
 
     import numpy as np
@@ -57,6 +62,12 @@ def main():
     out = Visualizer(class_names=names, input_format=fmt).draw(image, inst)
     write_png(a.out, out, input_format=fmt)
     print("{} detections drawn into {}".format(len(inst), a.out))
+    if a.json:
+        import json
+        from centermask2_amd import wire
+        with open(a.json, "w") as f:
+            json.dump(wire.instances_to_coco_json(inst, 0, segmentation=a.segmentation), f)
+        print("{} COCO results ({}) written to {}".format(len(inst), a.segmentation, a.json))
 
 
 if __name__ == "__main__":
