@@ -3,13 +3,12 @@ must be exactly the __global__ kernels of csrc/resize.hip, csrc/rle.hip and csrc
 (entry, feature) cell must have a row or a reason, the geometry a row exists for must be what the restated launch code makes of its
 arguments, no accepted row may grow into a workload, and every refused row must be refused with CMK_EINVAL on dummy aligned pointers:
 every argument check of these entries sits before its launch."""
-import ctypes
 import os
 
 import pytest
 
+from tests import conformance as C
 from tests import image_cases as ic
-from tests.test_cpu_tail_conformance import base, library_kernels, source_kernels
 
 CASES = ic.all_cases()
 ACCEPTED = [c for c in CASES if c["answer"] == "accept"]
@@ -18,35 +17,18 @@ ROW_KEYS = {"id", "entry", "feature", "answer", "why", "data", "null", "host_onl
 
 def test_census_equals_the_kernels_of_the_three_files(cmk_lib):
     """No count is written down: a new kernel or instantiation without a row, or a row naming a kernel that is gone, fails here by name."""
-    names = source_kernels(ic.FILES)
-    assert names, "no __global__ kernel found in the sources"
-    kernels = library_kernels(names)
-    assert {base(k) for k in kernels} == names, "kernels of the sources the library lacks: {}".format(sorted(names - {base(k) for k in kernels}))
-    named = {k for c in ACCEPTED for k in c["kernels"]}
-    assert named == kernels, "kernels no accepted row launches: {}; rows naming kernels the library lacks: {}".format(sorted(kernels - named), sorted(named - kernels))
-    census = {k for c in CASES if c["feature"] == "census" for k in c["kernels"]}
-    assert census == kernels, "kernels without a census row: {}".format(sorted(kernels - census))
+    C.assert_census(CASES, ic.FILES)
     for e in ic.ENTRIES:
         assert all(hasattr(cmk_lib, name) for name in e.split("+")), e
 
 
 def test_every_cell_has_a_row_or_a_reason():
-    assert {c["entry"] for c in CASES} == set(ic.ENTRIES) and {c["feature"] for c in CASES} == set(ic.FEATURES)
-    cells = {(c["entry"], c["feature"]) for c in CASES}
-    assert set(ic.N_A) <= {(e, f) for e in ic.ENTRIES for f in ic.FEATURES}
-    for e in ic.ENTRIES:
-        for f in ic.FEATURES:
-            assert ((e, f) in cells) != ((e, f) in ic.N_A), (e, f, "a cell has a row or a reason, not both and not neither")
-    assert all(isinstance(v, str) and v.strip() for v in list(ic.N_A.values()) + list(ic.PRECONDITIONS.values()) + list(ic.NO_ROW.values()))
-    assert set(ic.PRECONDITIONS) <= set(ic.ENTRIES)
-    assert len({c["id"] for c in CASES}) == len(CASES)                   # ids name rows
+    C.assert_cells(CASES, ic, nullable=ic.NULLABLE)
+    assert all(isinstance(v, str) and v.strip() for v in ic.NO_ROW.values())
     for c in CASES:
-        assert c["answer"] in ("accept", "refuse") and (c["answer"] == "refuse") == (c["feature"] == "refuse"), c["id"]
         assert c["why"].strip(), c["id"]
-        assert not c["kernels"] or c["answer"] == "accept", c["id"]
         if c["answer"] == "accept" and not c["kernels"]:                 # accepted and launching nothing: a count of zero
             assert min(c.get(k, 1) for k in ("r", "m", "n")) == 0 and "touches nothing" in c["why"], c["id"]
-        assert not c["host_only"] or c["answer"] == "refuse", c["id"]
         assert c["null"] is None or c["null"] in ic.NULLABLE[c["entry"]], c["id"]
         assert set(c) - ROW_KEYS == set(ic.DEFAULTS[c["entry"]]), c["id"]
     for e in ic.ENTRIES:                                                 # every pointer of every entry has its NULL row
@@ -126,13 +108,4 @@ def test_ksize_and_workspace_formulas(cmk_lib):
 
 @pytest.mark.parametrize("entry", ic.ENTRIES)
 def test_refused_rows_are_refused_before_any_launch(cmk_lib, entry):
-    buf = (ctypes.c_float * 96)()
-    ptr = (ctypes.addressof(buf) + 15) // 16 * 16
-    rows = [c for c in CASES if c["entry"] == entry and c["answer"] == "refuse"]
-    assert rows
-    for c in rows:
-        rc = ic.call(cmk_lib, c, ic.dummy_pointers(c, ptr))
-        err = cmk_lib.cmk_last_error().decode()
-        # CMK_EINVAL is the argument checks' code; a call that got as far as its launch returns CMK_ELAUNCH here (there is no device)
-        assert rc == ic.CMK_EINVAL, (c["id"], "declared refuse, but the call went on to its launch" if rc else "declared refuse, accepted", rc, err)
-        assert err.strip(), (c["id"], "refused without an error text")
+    C.assert_refused_before_launch(cmk_lib, ic, entry, einval=ic.CMK_EINVAL)

@@ -3,46 +3,28 @@ must be exactly the __global__ kernels of csrc/conv_deform.hip, csrc/dwconv_bn_a
 built library instantiates them, every (entry point, feature) cell must have a row or a reason, no accepted row may be out of proportion,
 and every refused row must be refused with CMK_EINVAL on dummy aligned pointers: every argument check of these entry points sits before its
 launch.  And the per-corner float64 restatement of the deformable conv (tests/deform_ref.py) equals the grid_sample one where both apply."""
-import ctypes
-
 import pytest
 import torch
 
+from tests import conformance as C
 from tests import variant_cases as vc
 from tests.deform_ref import deform_conv3x3_ref, deform_conv3x3_ref_corners, make_offsets
-from tests.test_cpu_tail_conformance import base, library_kernels, source_kernels
 
 CASES = vc.all_cases()
-FILES = ("conv_deform.hip", "dwconv_bn_act.hip", "conv_group3.hip", "stem7_pool.hip")
 MB = 1 << 20
 
 
 def test_census_equals_the_kernels_of_the_four_files(cmk_lib):
     """No count is written down: a new kernel or instantiation without a row, or a row naming a kernel that is gone, fails here by name."""
-    names = source_kernels(FILES)
-    assert names, "no __global__ kernel found in the sources"
-    kernels = library_kernels(names)
-    assert {base(k) for k in kernels} == names, "kernels of the sources the library lacks: {}".format(sorted(names - {base(k) for k in kernels}))
-    named = {k for c in CASES if c["answer"] == "accept" for k in c["kernels"]}
-    assert named == kernels, "kernels no accepted row launches: {}; rows naming kernels the library lacks: {}".format(sorted(kernels - named), sorted(named - kernels))
-    census = {k for c in CASES if c["feature"] == "census" for k in c["kernels"]}
-    assert census == kernels, "kernels without a census row: {}".format(sorted(kernels - census))
+    C.assert_census(CASES, C.TABLES["tests/variant_cases.py"][1])
     assert all(hasattr(cmk_lib, e) for e in vc.ENTRIES)
 
 
 def test_every_cell_has_a_row_or_a_reason():
-    assert {c["entry"] for c in CASES} == set(vc.ENTRIES) and {c["feature"] for c in CASES} == set(vc.FEATURES)
-    cells = {(c["entry"], c["feature"]) for c in CASES}
-    for e in vc.ENTRIES:
-        for f in vc.FEATURES:
-            assert ((e, f) in cells) != ((e, f) in vc.N_A), (e, f, "a cell has a row or a reason, not both and not neither")
-    assert all(isinstance(v, str) and v.strip() for v in list(vc.N_A.values()) + list(vc.PRECONDITIONS.values()))
-    assert set(vc.PRECONDITIONS) <= set(vc.ENTRIES) and set(vc.DEFAULTS) == set(vc.POINTERS) == set(vc.NULLABLE) == set(vc.ENTRIES)
-    assert len({c["id"] for c in CASES}) == len(CASES)                   # ids name rows
+    C.assert_cells(CASES, vc, nullable=vc.POINTERS)
+    assert set(vc.DEFAULTS) == set(vc.POINTERS) == set(vc.NULLABLE) == set(vc.ENTRIES)
     for c in CASES:
-        assert c["answer"] in ("accept", "refuse") and (c["answer"] == "refuse") == (c["feature"] == "refuse"), c["id"]
         assert bool(c["kernels"]) == (c["answer"] == "accept"), c["id"]
-        assert not c["host_only"] or c["answer"] == "refuse", c["id"]
         assert c["null"] is None or c["null"] in vc.NULLABLE[c["entry"]], c["id"]
         assert c["why"].strip() or c["feature"] in ("n1", "odd_n", "offsets_edge", "offsets_far", "offsets_int", "poison"), (c["id"], "a row says which edge it puts")
         if c["same_buffer"] and c["answer"] == "accept":
@@ -110,20 +92,7 @@ def test_the_rows_keep_the_limits_that_protect_the_machine():
 
 @pytest.mark.parametrize("entry", vc.ENTRIES)
 def test_refused_rows_are_refused_before_any_launch(cmk_lib, entry):
-    buf = (ctypes.c_float * 256)()
-    ptr = (ctypes.addressof(buf) + 15) // 16 * 16
-    rows = [c for c in CASES if c["entry"] == entry and c["answer"] == "refuse"]
-    assert rows
-    failed = []
-    for c in rows:
-        rc = vc.call(cmk_lib, c, vc.dummy_pointers(c, ptr))
-        err = cmk_lib.cmk_last_error().decode()
-        # CMK_EINVAL is the argument checks' code; a call that got as far as its launch returns CMK_ELAUNCH here (there is no device)
-        if rc != vc.CMK_EINVAL:
-            failed.append("{}: {}".format(c["id"], "declared refuse, but the call went on to its launch ({}: {})".format(rc, err.strip()) if rc else "declared refuse, accepted"))
-        elif not err.strip():
-            failed.append(c["id"] + ": refused without an error text")
-    assert not failed, "\n".join(["{} of {} refused rows".format(len(failed), len(rows))] + failed)
+    C.assert_refused_before_launch(cmk_lib, vc, entry, einval=vc.CMK_EINVAL)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@ import torch
 
 from centermask2_amd import _lib, ops
 from centermask2_amd.ops import View
+from tests import conformance as C
 from tests import conv_cases as cc
 from tests.helpers import close, close_abs, relaunch
 
@@ -75,10 +76,6 @@ def _read_only(c, b):
     return ro
 
 
-def _same_bits(a, b):
-    return a.dtype == b.dtype and torch.equal(a.view(torch.int32 if a.element_size() == 4 else torch.int16), b.view(torch.int32 if b.element_size() == 4 else torch.int16))
-
-
 def _all_nan(t):
     return t is None or bool(torch.isnan(t).all())
 
@@ -125,7 +122,7 @@ def _check_outside(c, b, before):
         left, right = ya[1:n + 1, :, :, :y_co], ya[1:n + 1, :, :, y_co + c["cout"]:]
         if c["same_buffer"]:
             old = before["same{}".format(i)]
-            assert _same_bits(left.contiguous(), old[..., :y_co].contiguous()) and _same_bits(right.contiguous(), old[..., y_co + c["cout"]:].contiguous()), \
+            assert C.same_bits(left.contiguous(), old[..., :y_co].contiguous()) and C.same_bits(right.contiguous(), old[..., y_co + c["cout"]:].contiguous()), \
                 (c["id"], i, "channels outside the output view changed")
         else:
             assert _all_nan(left) and _all_nan(right), (c["id"], i, "written outside the output view")
@@ -187,7 +184,7 @@ def _run_case(c, seed, dev, lib, what, skipped):
                 assert _all_nan(b["ya"][i]), (c["id"], "the output was written before the refusal")
         assert _all_nan(keep["ws"]) and _all_nan(keep["pool"]) and _all_nan(keep["gn"]), (c["id"], "a workspace was written before the refusal")
         for k, v in ro.items():
-            assert _same_bits(v, before[k]), (c["id"], k, "changed by a refused launch")
+            assert C.same_bits(v, before[k]), (c["id"], k, "changed by a refused launch")
         return "refused"
     assert rc == 0, (c["id"], "declared accept, refused", err)
     ref = cc.reference(c, t)
@@ -195,7 +192,7 @@ def _run_case(c, seed, dev, lib, what, skipped):
     _check_outside(c, b, before)
     _check_records(c, b, keep, ref, t, dev, what)
     for k, v in ro.items():
-        assert _same_bits(v, before[k]), (c["id"], k, "an input of the launch changed")
+        assert C.same_bits(v, before[k]), (c["id"], k, "an input of the launch changed")
     # determinism: the same launch into a NaN output again
     (_, _), (_, y_co) = cc.views_of(c)
     first = [b["yv"][i].t[..., y_co:y_co + c["cout"]].clone() for i in range(n)]
@@ -208,9 +205,9 @@ def _run_case(c, seed, dev, lib, what, skipped):
     rc2, err2 = _launch(lib, descs)
     assert rc2 == 0, (c["id"], err2)
     for i in range(n):
-        assert _same_bits(b["yv"][i].t[..., y_co:y_co + c["cout"]].contiguous(), first[i].contiguous()), (c["id"], i, "a second launch gave other bits")
+        assert C.same_bits(b["yv"][i].t[..., y_co:y_co + c["cout"]].contiguous(), first[i].contiguous()), (c["id"], i, "a second launch gave other bits")
     if first_pool is not None:
-        assert _same_bits(keep["pool"], first_pool), (c["id"], "a second launch gave other pooled sums")
+        assert C.same_bits(keep["pool"], first_pool), (c["id"], "a second launch gave other pooled sums")
     return "launched"
 
 
@@ -223,15 +220,10 @@ def test_conv_conformance(dev, cmk_lib, family, monkeypatch):
     monkeypatch.setattr(ops, "ALLOW_SPLIT_F16", True)
     monkeypatch.setattr(ops, "FORCE_VARIANT", None)
     mine = [(i, c) for i, c in enumerate(CASES) if c["family"] == family]
-    done = {"launched": 0, "refused": 0, "skipped": 0}
+    seed = {c["id"]: i for i, c in mine}
     skipped = []
-    failed = []
-    for i, c in mine:
-        try:                                      # a case that misses its check does not hide the ones after it (a device error is no AssertionError and ends the test)
-            done[_run_case(c, i, dev, cmk_lib, "conformance " + family, skipped)] += 1
-        except AssertionError as e:
-            failed.append("{}: {}".format(c["id"], str(e).splitlines()[0] if str(e) else "assert"))
-    assert not failed, "\n".join(["{} of {} cases failed".format(len(failed), len(mine))] + failed)
+    how = C.run_rows([c for _, c in mine], lambda c: _run_case(c, seed[c["id"]], dev, cmk_lib, "conformance " + family, skipped))
+    done = {k: how.count(k) for k in ("launched", "refused", "skipped")}
     if skipped:
         print("skipped (the device's LDS limit refuses the paired form):", skipped)
     # nothing skips silently: every declared case ran, and was answered as declared

@@ -20,6 +20,7 @@ import torch
 
 from centermask2_amd import ops, wire
 from tests import boundary_ref as BR
+from tests import conformance as C
 from tests import image_cases as ic
 from tests import resize_ref as RR
 from tests import tta_ref as TR
@@ -69,72 +70,25 @@ def _eq(got, ref, what):
         assert np.array_equal(got, ref), what + ": {} of {} values differ".format(int((got != ref).sum()), ref.size)
 
 
-class Buf:
-    """A device buffer in the middle of a larger allocation of filler bytes: `guard` bytes before it (plus the row's byte offset) and
-    after it.  arr: what it holds before the call (an input); None: filler, an output or workspace."""
+class Bufs(C.Bufs):
+    """The row's buffers from NumPy arrays: on the device they are bytes, on the host they come back in the array's own dtype."""
+    TORCH = {"f4": torch.float32, "u1": torch.uint8, "i4": torch.int32, "i8": torch.int64, "u8": torch.int64}
 
-    def __init__(self, dev, arr=None, dtype=None, shape=None, off=0, guard=256):
-        if arr is not None:
-            arr = np.ascontiguousarray(arr)
-            dtype, shape = arr.dtype, arr.shape
-        self.dtype, self.shape = np.dtype(dtype), tuple(shape)
-        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
-        self.fill = 0xFF if self.dtype.kind == "f" else 0x5A
-        assert guard % 256 == 0 and 0 <= off < 16
-        self.lo = guard + off
-        self.alloc = torch.empty(2 * guard + 16 + self.nbytes, dtype=torch.uint8, device=dev)
-        assert self.alloc.data_ptr() % 64 == 0
-        self.init = None if arr is None else torch.from_numpy(arr.reshape(-1).view(np.uint8).copy()).to(dev)
-        self.reset()
-
-    def mid(self):
-        return self.alloc[self.lo:self.lo + self.nbytes]
-
-    def reset(self, guard_fill=None):
-        self.guard_fill = self.fill if guard_fill is None else guard_fill
-        self.alloc.fill_(self.guard_fill)
-        if self.init is None:
-            self.mid().fill_(self.fill)
-        else:
-            self.mid().copy_(self.init)
-
-    def ptr(self):
-        return self.alloc.data_ptr() + self.lo
-
-    def get(self):
-        return self.mid().cpu().numpy().view(self.dtype).reshape(self.shape)
-
-    def guards_untouched(self):
-        return bool((self.alloc[:self.lo] == self.guard_fill).all()) and bool((self.alloc[self.lo + self.nbytes:] == self.guard_fill).all())
-
-    def untouched(self):
-        return self.guards_untouched() and (bool((self.mid() == self.fill).all()) if self.init is None else torch.equal(self.mid(), self.init))
-
-
-def _is_filler(a):
-    a = np.ascontiguousarray(a)
-    return bool((a.reshape(-1).view(np.uint8) == (0xFF if a.dtype.kind == "f" else 0x5A)).all())
-
-
-class Bufs:
     def __init__(self, dev):
-        self.dev, self.p, self.ins, self.outs = dev, {}, {}, {}
-        self.steps = None          # the calls of an accepted row when it is more than one (the RLE pair: count, then encode)
-        self.between = None        # check after the first of them, before the second is allowed to run
-        self.extra = None          # further launches of a row: the entry against its siblings, bit for bit
-        self.regard = None         # name of an input whose guards hold another byte on the repeated call
+        super().__init__(dev)
+        self.np = {}               # output name -> its NumPy dtype
 
     def put(self, name, arr, **kw):
-        b = Buf(self.dev, arr=arr, **kw)
-        self.ins[name] = b
-        self.p[name] = b.ptr()
-        return b
+        arr = np.ascontiguousarray(arr)
+        as_torch = self.TORCH[arr.dtype.str[1:]]
+        return super().put(name, torch.from_numpy(arr.view(np.int64) if arr.dtype == np.uint64 else arr).view(as_torch), guard=kw.pop("guard", 256), **kw)
 
     def out(self, name, dtype, shape, **kw):
-        b = Buf(self.dev, dtype=dtype, shape=shape, **kw)
-        self.outs[name] = b
-        self.p[name] = b.ptr()
-        return b
+        self.np[name] = np.dtype(dtype)
+        return super().out(name, shape, self.TORCH[self.np[name].str[1:]], guard=256, **kw)
+
+    def host(self, got):
+        return {name: t.numpy().view(self.np[name]) for name, t in got.items()}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -319,7 +273,7 @@ def _build_timg(c, g, dev, B):
             assert not np.isnan(ref["box"]).any() and np.isnan(ref["loc"]).sum() == 2 and np.isnan(ref["score"]).sum() == 1, what + ": fmin / fmax drop the NaN of a box"
         for name, key in (("cand_box", "box"), ("cand_score", "score"), ("cand_cls", "cls"), ("cand_loc", "loc")):
             _eq(got[name][:m], ref[key].astype(got[name].dtype), what + " " + name)
-            assert _is_filler(got[name][m:]), what + ": {} written past the compacted total".format(name)
+            assert C.is_filler(got[name][m:]), what + ": {} written past the compacted total".format(name)
     return check
 
 
@@ -376,7 +330,7 @@ def _build_tred(c, g, dev, B):
         if g["scores"]:
             _eq(got["out_scores"], ref_s, what + " scores")
         else:
-            assert _is_filler(got["out_scores"]), what + ": out_scores was not handed in"
+            assert C.is_filler(got["out_scores"]), what + ": out_scores was not handed in"
         key = (a, k, s, g["count"], tuple(g["flips"]), g["scores"], c["data"])
         bits = got["out_masks"].view(np.uint32)
         assert np.array_equal(_SEEN.setdefault(key, bits), bits), what + ": other bits than the first row on the same data gave"
@@ -439,7 +393,7 @@ def _build_rle(c, g, dev, B):
         assert got["n_runs"].tolist() == n_runs.tolist(), c["id"] + ": n_runs"
         assert got["ws"][:8 * (r + 1)].view(np.int64).tolist() == off.tolist(), c["id"] + ": the run offsets in the workspace"
         for name in ("starts", "counts", "bytes", "lens"):
-            assert _is_filler(got[name]), (c["id"], name, "written by the count phase")
+            assert C.is_filler(got[name]), (c["id"], name, "written by the count phase")
     B.between = between
 
     def check(got):
@@ -511,7 +465,7 @@ def _build_dec(c, g, dev, B):
         if g["bitmasks"]:
             _eq(got["bitmasks"], masks, c["id"] + " bitmasks")
         else:
-            assert _is_filler(got["bitmasks"]), c["id"] + ": bitmasks was not handed in"
+            assert C.is_filler(got["bitmasks"]), c["id"] + ": bitmasks was not handed in"
     return check
 
 
@@ -576,73 +530,24 @@ BUILD = {ic.RH: _build_rh, ic.RV: _build_rv, ic.RVP: _build_rv, ic.RVF: _build_r
          ic.RLE: _build_rle, ic.PACK: _build_pack, ic.UNPACK: _build_pack, ic.DEC: _build_dec, ic.INTER: _build_inter, ic.BND: _build_bnd}
 
 
-def _run_row(c, dev, lib):
+def _conform(c, dev, lib):
     B = Bufs(dev)
     check = BUILD[c["entry"]](c, _sane(c), dev, B)
-    before = {k: b.alloc.clone() for k, b in B.ins.items()}
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    between, extra = B.between, B.extra
+    B.between = between and (lambda got: between(B.host(got)))
+    B.extra = extra and (lambda first: extra(lib, stream, first))
 
     def launch(row):
         rc = ic.call(lib, row, B.p, stream)
         err = lib.cmk_last_error().decode() if rc != 0 else ""
         torch.cuda.synchronize()
         return rc, err
-
-    def snapshot():
-        return {name: b.get() for name, b in B.outs.items()}
-
-    def inputs_unchanged(why):
-        for k, b in B.ins.items():
-            assert torch.equal(b.alloc, before[k]), (c["id"], k, why)
-
-    def run():
-        for i, row in enumerate(B.steps or [c]):
-            rc, err = launch(row)
-            assert rc == 0, (c["id"], "declared accept, refused", rc, err)
-            if i == 0 and B.steps:
-                B.between(snapshot())
-
-    if c["answer"] == "refuse" or not c["kernels"]:
-        rc, err = launch(c)
-        if c["answer"] == "refuse":
-            assert rc == ic.CMK_EINVAL and err.strip(), (c["id"], "declared refuse: the argument checks' code is CMK_EINVAL, a launch that failed gives another", rc, err)
-        else:
-            assert rc == 0, (c["id"], "a count of 0 is CMK_OK", rc, err)
-        for name, b in B.outs.items():
-            assert b.untouched(), (c["id"], name, "written by a call that launches nothing")
-        inputs_unchanged("changed by a call that launches nothing")
-        return False
-    run()
-    for name, b in B.outs.items():
-        assert b.guards_untouched(), (c["id"], name, "written into a guard")
-    inputs_unchanged("an input of the call changed")
-    first_dev = {name: b.mid().clone() for name, b in B.outs.items()}
-    check(snapshot())
-    if B.extra:
-        B.extra(lib, stream, first_dev)
-    for b in B.outs.values():                                  # the same call again into fresh buffers
-        b.reset()
-    if B.regard:                                               # ... with another byte around the source: what the kernel read lay inside it
-        B.ins[B.regard].reset(guard_fill=0xC3)
-    run()
-    for name, b in B.outs.items():
-        assert torch.equal(b.mid(), first_dev[name]) and b.guards_untouched(), (c["id"], name, "a second call gave other bits")
-    return True
+    return C.run_row(c, B, launch, lambda got: check(B.host(got)), einval=ic.CMK_EINVAL, launches=bool(c["kernels"]))
 
 
 @pytest.mark.parametrize("entry", ic.ENTRIES)
 def test_image_conformance(dev, cmk_lib, entry):
-    """Every row of one entry.  Everything is exact; nothing to measure."""
-    mine = [c for c in CASES if c["entry"] == entry and not c["host_only"]]
-    failed, launched, quiet = [], 0, 0
-    for c in mine:
-        try:                                      # a row that misses its check does not hide the ones after it (a device error is no AssertionError and ends the test)
-            if _run_row(c, dev, cmk_lib):
-                launched += 1
-            else:
-                quiet += 1
-        except AssertionError as err:
-            failed.append("{}: {}".format(c["id"], str(err).splitlines()[0] if str(err) else "assert"))
-    assert not failed, "\n".join(["{} of {} rows failed".format(len(failed), len(mine))] + failed)
-    assert launched == sum(bool(c["kernels"]) for c in mine) and launched > 0
-    assert quiet == sum(not c["kernels"] for c in mine) and quiet > 0
+    """Every row of one entry.  Everything is exact; nothing to measure.  A row with a count of 0 is accepted and launches nothing: the
+    rows are counted by their kernels."""
+    C.run_entry(entry, [c for c in CASES if c["entry"] == entry and not c["host_only"]], lambda c: _conform(c, dev, cmk_lib), count="kernels", report=False)

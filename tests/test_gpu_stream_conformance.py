@@ -15,21 +15,19 @@ test_fused_stem_matches_float64_torch: another summation order and the MFMA's ac
 orders of magnitude more).  GroupNorm: close(got, ref64, 2e-5) as test_groupnorm_relu; the *_affine entry points through x * scale + shift.
 
 Observed values: the docstring of test_stream_conformance and DESIGN.md §3 "Stream conformance table"."""
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 from centermask2_amd import ops, synthetic as S
 from centermask2_amd._lib import CmkError
+from tests import conformance as C
 from tests import stream_cases as sc
 from tests.helpers import close
 
 pytestmark = pytest.mark.gpu
 
-NAN, INF = float("nan"), float("inf")
-PAD = 1024            # floats (doubles) of NaN before and after a second_trip output: whole guard images would triple tens of MB
+NAN, INF = C.NAN, C.INF
 CASES = sc.all_cases()
 INDEX = {c["id"]: i for i, c in enumerate(CASES)}
 _HOST = {}            # row id -> the host tensors and references of a stem or gate row (the bars and the rows share them)
@@ -86,10 +84,6 @@ def _wide(x, view):
     t = torch.full(tuple(x.shape[:-1]) + (cs,), NAN)
     t[..., co:co + x.shape[-1]] = x
     return t
-
-
-def _dist(a, ref):
-    return float((a.double() - ref).abs().max()) / max(1.0, float(ref.abs().max()))
 
 
 def _pool3_out(h):
@@ -195,100 +189,33 @@ def _gn_params(c, ch):
 # ---------------------------------------------------------------------------------------------------------------
 # a row on the device
 # ---------------------------------------------------------------------------------------------------------------
-class Out:
-    """An output or workspace: `alloc` is NaN everywhere but `region(alloc)`, which the call must write; init: the content of the region of
-    an in-place operand before the call (None: NaN)."""
-
-    def __init__(self, alloc, region, init=None):
-        self.alloc, self.region, self.init = alloc, region, init
-        self.reset()
-
-    def reset(self):
-        if self.init is None:
-            self.region(self.alloc).fill_(NAN)
-        else:
-            self.region(self.alloc).copy_(self.init)
-
-    def outside_is_nan(self):
-        t = self.alloc.clone()
-        self.region(t).fill_(NAN)
-        return bool(torch.isnan(t).all())
-
-
-def _guarded(c, n, rest, dev, dtype=torch.float32):
-    """(alloc, middle): n images of shape `rest` between NaN guards — one guard image each side, or PAD elements for a second_trip row."""
-    if c["feature"] == "second_trip":
-        numel = n * math.prod(rest)
-        alloc = torch.full((numel + 2 * PAD,), NAN, dtype=dtype, device=dev)
-        return alloc, (lambda a: a[PAD:PAD + numel].view((n,) + tuple(rest)))
-    alloc = torch.full((n + 2,) + tuple(rest), NAN, dtype=dtype, device=dev)
-    return alloc, (lambda a: a[1:n + 1])
-
-
-def _sliced(mid, view, ch):
-    if view is None:
-        return mid
-    return lambda a: mid(a)[..., view[1]:view[1] + ch]
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int64)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
-def _finite_parts(got, ref, what, nan_is_zero=False):
-    """NaN and Inf sit where the reference has them (nan_is_zero: the fused ReLU's documented relu(NaN) = 0); returns the finite rest."""
-    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
-    ref_nan = torch.isnan(ref)
-    if nan_is_zero:
-        assert not bool(torch.isnan(got).any()) and bool((got[ref_nan] == 0).all()), what + ": relu(NaN) must be 0"
-    else:
-        assert torch.equal(torch.isnan(got), ref_nan), what + ": NaN elsewhere than in the float64 result ({} vs {})".format(int(torch.isnan(got).sum()), int(ref_nan.sum()))
-    for inf in (INF, -INF):
-        assert torch.equal(got == inf, ref == inf), what + ": {} elsewhere than in the float64 result".format(inf)
-    ok = torch.isfinite(ref)
-    return got[ok], ref[ok]
-
-
-def _exact(got, ref, what):
-    g, r = _finite_parts(got, ref, what)
-    assert torch.equal(g, r), what + ": not equal, max abs err {:.3e}".format(float((g.double() - r.double()).abs().max()) if g.numel() else 0.0)
-    return 0.0
-
-
 def _build(c, dev, bars):
-    """(pointers, outs {name: Out}, read-only inputs {name: tensor}, check(got {name: cpu region}) -> distance on record)."""
+    """(the row's buffers, check(got {name: the output on the host}) -> distance on record)."""
     e = c["entry"]
     g = _sane(c)
     n, h, w, ch, hw = g["n"], g["h"], g["w"], g["c"], g["h"] * g["w"]
     accept = c["answer"] == "accept"
     what = c["id"]
-    p, outs, ro = {}, {}, {}
+    B = C.Bufs(dev)
+    p = B.p
 
     def put(name, t):
-        ro[name] = t.to(dev)
-        p[name] = ro[name].data_ptr()
-        return ro[name]
+        return B.put(name, t, guard=256)
 
-    def out(name, alloc_mid, view=None, init=None):
-        alloc, mid = alloc_mid
-        outs[name] = Out(alloc, _sliced(mid, view, ch), None if init is None else init.to(dev))
-        p[name] = mid(alloc).data_ptr()
-        return outs[name]
+    def out(name, rest, view=None, init=None, dtype=torch.float32, images=n):
+        """`images` maps of shape `rest` between guards (conformance.map_guard); view: the call owns a channel slice of the last dimension."""
+        return B.out(name, (images,) + tuple(rest), dtype, init=init, guard=C.map_guard(c, rest, 8 if dtype == torch.float64 else 4),
+                     window=None if view is None else (view[1], ch))
 
     if e == sc.STEM:
         hst = _stem_host(c)
         for k, v in (("x", hst["x"]), ("w", hst["w27"]), ("scale", hst["scale"]), ("shift", hst["shift"])):
             put(k, v)
         ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        out("y", _guarded(c, n, (ho, wo, ch), dev))
+        out("y", (ho, wo, ch))
 
         def check(got):
-            a, r = _finite_parts(got["y"].double(), hst["ref64"], what, nan_is_zero=True)
-            d = float((a - r).abs().max()) / max(1.0, float(r.abs().max()))
+            d = C.dist(*C.finite_parts(got["y"].double(), hst["ref64"], what, nan_is_zero=True))
             assert d <= bars["stem"], "{}: {:.3e} from float64 > bar {:.3e}".format(what, d, bars["stem"])
             return d
     elif e in (sc.POOL3, sc.POOL1):
@@ -306,7 +233,7 @@ def _build(c, dev, bars):
             ho, wo = _pool3_out(h), _pool3_out(w)
         else:
             ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        out("y", _guarded(c, n, (ho, wo, (g["y_view"] or (ch, 0))[0]), dev), g["y_view"])
+        out("y", (ho, wo, (g["y_view"] or (ch, 0))[0]), g["y_view"])
 
         def check(got):
             xc = x.permute(0, 3, 1, 2)
@@ -318,17 +245,17 @@ def _build(c, dev, bars):
                 assert bool((ref <= 0).all()) and bool((ref < 0).any())
             if c["poison"]:
                 assert bool((ref[1, 0, 0] == -INF).all()) and bool(torch.isnan(ref[2]).any()) and bool((ref[0] == INF).any())
-            return _exact(got["y"], ref.contiguous(), what)
+            return C.exact(got["y"], ref.contiguous(), what)
     elif e == sc.UPADD:
         y0, coarse = _data(c, (n, h, w, ch)), torch.randn((n, max(1, g["hc"]), max(1, g["wc"]), ch), generator=_gen(c, 1))
         if c["poison"]:
             coarse[0, 0, 0, 1] = NAN
         put("coarse", coarse)
-        out("y", _guarded(c, n, (h, w, ch), dev), init=y0)
+        out("y", (h, w, ch), init=y0)
 
         def check(got):
             up = coarse.repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :h, :w]
-            return _exact(got["y"], y0 + up, what)
+            return C.exact(got["y"], y0 + up, what)
     elif e in (sc.GATE, sc.POOLED):
         hst = _gate_host(c)
         put("fc_w", hst["fw"])
@@ -336,10 +263,10 @@ def _build(c, dev, bars):
         if e == sc.GATE:
             put("x", _wide(hst["x"], g["x_view"]))
             chunks = g["chunks"]
-            out("ws", _guarded(c, n, (chunks, ch), dev))
+            out("ws", (chunks, ch))
         else:
             put("pool_ws", hst["rec"])
-        out("gate", _guarded(c, n, (ch,), dev))
+        out("gate", (ch,))
 
         def check(got):
             ref = hst["ref64"]
@@ -347,8 +274,7 @@ def _build(c, dev, bars):
                 assert bool((ref == 0).any()) and bool((ref == 1).any()) and bool(((ref > 0) & (ref < 1)).any()), what + ": the gates must saturate both ways and lie between"
             else:
                 assert bool(torch.isnan(ref[2]).all()) and not bool(torch.isnan(ref[:2]).any())
-            a, r = _finite_parts(got["gate"].double(), ref, what)
-            d = float((a - r).abs().max()) / max(1.0, float(r.abs().max()))
+            d = C.dist(*C.finite_parts(got["gate"].double(), ref, what))
             assert d <= bars["gate"], "{}: {:.3e} from float64 > bar {:.3e}".format(what, d, bars["gate"])
             if e == sc.GATE:
                 per = -(-hw // chunks)
@@ -370,17 +296,17 @@ def _build(c, dev, bars):
         else:
             p["identity"] = None
         if c["same_buffer"]:
-            out("y", _guarded(c, n, (h, w, ch), dev), init=x)
+            out("y", (h, w, ch), init=x)
             p["x"] = p["y"]
         else:
             put("x", _wide(x, g["x_view"]))
-            out("y", _guarded(c, n, (h, w, (g["y_view"] or (ch, 0))[0]), dev), g["y_view"])
+            out("y", (h, w, (g["y_view"] or (ch, 0))[0]), g["y_view"])
 
         def check(got):
             prod = x.double() * gate.double()[:, None, None, :]
             ref = prod + (idn.double() if idn is not None else 0.0)
             bound = 2.0 ** -23 * (prod.abs() + (idn.double().abs() if idn is not None else 0.0))
-            a, r = _finite_parts(got["y"].double(), ref, what)
+            a, r = C.finite_parts(got["y"].double(), ref, what)
             err = (a - r).abs()
             b = bound[torch.isfinite(ref)]
             assert bool((err <= b).all()), "{}: {:.3e} over the rounding bound".format(what, float((err - b).max()))
@@ -390,13 +316,13 @@ def _build(c, dev, bars):
         gamma, beta = _gn_params(c, ch)
         put("gamma", gamma)
         put("beta", beta)
-        out("ws", _guarded(c, n, (g["groups"], g["chunks"], 2), dev, torch.float64))
+        out("ws", (g["groups"], g["chunks"], 2), dtype=torch.float64)
         if e == sc.AFFINE:
             put("x", x)
-            out("out_scale", _guarded(c, n, (ch,), dev))
-            out("out_shift", _guarded(c, n, (ch,), dev))
+            out("out_scale", (ch,))
+            out("out_shift", (ch,))
         else:
-            out("x", _guarded(c, n, (h, w, ch), dev), init=x)
+            out("x", (h, w, ch), init=x)
 
         def check(got):
             if e == sc.AFFINE:
@@ -429,12 +355,10 @@ def _build(c, dev, bars):
         p["out_scale"], p["out_shift"] = [], []
         for k in range(nlev):
             for name in ("out_scale", "out_shift"):
-                alloc, mid = _guarded(c, n, (ch,), dev)
-                outs["{}{}".format(name, k)] = Out(alloc, mid)
-                p[name].append(mid(alloc).data_ptr())
+                p[name].append(out("{}{}".format(name, k), (ch,)).ptr())
         if e == sc.MULTI:
-            p["xs"] = [put("x{}".format(k), x).data_ptr() for k, x in enumerate(xs)]
-            out("ws", _guarded(c, nlev * n, (groups, g["chunks"], 2), dev, torch.float64))
+            p["xs"] = [put("x{}".format(k), x).ptr() for k, x in enumerate(xs)]
+            out("ws", (groups, g["chunks"], 2), dtype=torch.float64, images=nlev * n)
         elif not accept:
             put("ws", torch.full((64, groups, 2), NAN, dtype=torch.float64))        # (a refused geometry need not cut into records)
         else:
@@ -466,63 +390,28 @@ def _build(c, dev, bars):
             return worst
     else:
         raise KeyError(e)
-    return p, outs, ro, check
+    return B, check
 
 
-def _run_row(c, dev, lib, bars):
-    p, outs, ro, check = _build(c, dev, bars)
-    before = {k: v.clone() for k, v in ro.items()}
+def _conform(c, dev, lib, bars):
+    B, check = _build(c, dev, bars)
 
-    def launch():
-        rc = sc.call(lib, c, p, ops._stream())
+    def launch(row):
+        rc = sc.call(lib, row, B.p, ops._stream())
         err = lib.cmk_last_error().decode() if rc != 0 else ""
         torch.cuda.synchronize()
         return rc, err
-
-    rc, err = launch()
-    if c["answer"] == "refuse":
-        assert rc != 0 and err.strip(), (c["id"], "declared refuse, launched", rc)
-        for name, o in outs.items():
-            if o.init is None:
-                assert bool(torch.isnan(o.alloc).all()), (c["id"], name, "written before the refusal")
-            else:
-                assert o.outside_is_nan() and _same_bits(o.region(o.alloc), o.init), (c["id"], name, "an in-place operand changed before the refusal")
-        for k, v in ro.items():
-            assert _same_bits(v, before[k]), (c["id"], k, "changed by a refused call")
-        return None
-    assert rc == 0, (c["id"], "declared accept, refused", err)
-    for name, o in outs.items():
-        assert o.outside_is_nan(), (c["id"], name, "written outside the output view or into a guard")
-    for k, v in ro.items():
-        assert _same_bits(v, before[k]), (c["id"], k, "an input of the call changed")
-    first = {name: o.region(o.alloc).clone() for name, o in outs.items()}
-    d = check({name: t.cpu() for name, t in first.items()})
-    for o in outs.values():
-        o.reset()
-    rc2, err2 = launch()
-    assert rc2 == 0, (c["id"], err2)
-    for name, o in outs.items():
-        assert _same_bits(o.region(o.alloc), first[name]), (c["id"], name, "a second call gave other bits")
-    return d
+    return C.run_row(c, B, launch, check)
 
 
 @pytest.fixture(scope="module")
 def bars():
     """{"stem", "gate"}: 4x the largest normalised distance of torch's own fp32 CPU result from the float64 one over the accepted finite
     rows of the table — from the references alone, before any kernel runs."""
-    out = {}
-    for name, entries, host in (("stem", (sc.STEM,), _stem_host), ("gate", (sc.GATE, sc.POOLED), _gate_host)):
-        worst = 0.0
-        for c in CASES:
-            if c["entry"] in entries and c["answer"] == "accept" and not c["poison"]:
-                hst = host(c)
-                d = _dist(hst["ref32"], hst["ref64"])
-                worst = max(worst, d)
-                print("{}: torch fp32 vs float64 {:.3e}".format(c["id"], d))
-        assert worst > 0.0
-        out[name] = 4.0 * worst
-        print("{}: largest fp32 distance {:.3e}, bar {:.3e}".format(name, worst, 4.0 * worst))
-    return out
+    def distance(host):
+        return lambda c: C.dist(host(c)["ref32"], host(c)["ref64"])
+    return {name: C.fp32_bar(name, [c for c in CASES if c["entry"] in entries and c["answer"] == "accept" and not c["poison"]], distance(host))
+            for name, entries, host in (("stem", (sc.STEM,), _stem_host), ("gate", (sc.GATE, sc.POOLED), _gate_host))}
 
 
 @pytest.mark.parametrize("entry", sc.ENTRIES)
@@ -533,23 +422,7 @@ def test_stream_conformance(dev, cmk_lib, bars, entry):
     in one chunk: the fp32 partial sums) and 5.96e-08 (cmk_ese_gate_pooled) from float64.  cmk_ese_scale uses at most 0.946 of its rounding
     bound.  The GroupNorm entry points are at most 1.54e-07 (relu), 1.44e-07 (plain), 1.45e-07 (affine), 1.39e-07 (multi) and 1.09e-07 (tiles)
     of max(1, max|ref|) from float64 against the bar of 2e-5.  The pools, the subsample and the upsample + add are bit-equal."""
-    mine = [c for c in CASES if c["entry"] == entry and not c["host_only"]]
-    failed, launched, refused, worst = [], 0, 0, 0.0
-    for c in mine:
-        try:                                      # a row that misses its check does not hide the ones after it (a device error is no AssertionError and ends the test)
-            d = _run_row(c, dev, cmk_lib, bars)
-            if d is None:
-                refused += 1
-            else:
-                launched += 1
-                worst = max(worst, d)
-                print("{}: {:.3e}".format(c["id"], d))
-        except AssertionError as err:
-            failed.append("{}: {}".format(c["id"], str(err).splitlines()[0] if str(err) else "assert"))
-    print("{}: largest distance on record {:.3e}".format(entry, worst))
-    assert not failed, "\n".join(["{} of {} rows failed".format(len(failed), len(mine))] + failed)
-    assert launched == sum(c["answer"] == "accept" for c in mine) and launched > 0
-    assert refused == sum(c["answer"] == "refuse" for c in mine) and refused > 0
+    C.run_entry(entry, [c for c in CASES if c["entry"] == entry and not c["host_only"]], lambda c: _conform(c, dev, cmk_lib, bars))
 
 
 def test_wrong_inputs_are_refused(dev):

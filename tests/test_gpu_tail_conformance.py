@@ -25,14 +25,14 @@ import torch
 import torch.nn.functional as F
 
 from oracle import centermask_oracle as O
+from tests import conformance as C
 from tests import keypoint_ref as KR
 from tests import tail_cases as tc
 from tests.helpers import close, close_abs
 
 pytestmark = pytest.mark.gpu
 
-NAN, INF = float("nan"), float("inf")
-SENTINEL = {torch.int32: 0x5A5A5A5A, torch.int64: 0x5A5A5A5A5A5A5A5A, torch.uint8: 0x5A}
+NAN, INF = C.NAN, C.INF
 CASES = tc.all_cases()
 INDEX = {c["id"]: i for i, c in enumerate(CASES)}
 IMG_SIZES = [(128, 160), (96, 128), (64, 160)]       # the images of the RoIAlign rows inside their 128 x 160 padded batch
@@ -73,92 +73,9 @@ def _valid(counts, topk):
     return (torch.arange(topk)[None, :] < torch.tensor(counts)[:, None]).reshape(-1)
 
 
-def _bits(t):
-    t = t.contiguous()
-    return t.view({1: torch.uint8, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
-def _filler(t):
-    """t filled with the guard value of its dtype: NaN, or the integer sentinel."""
-    return t.fill_(NAN) if t.is_floating_point() else t.fill_(SENTINEL[t.dtype])
-
-
-def _is_filler(t):
-    return bool(torch.isnan(t).all()) if t.is_floating_point() else bool((t == SENTINEL[t.dtype]).all())
-
-
-class Buf:
-    """A device buffer in the middle of a larger allocation of filler: `guard` leading-dimension units before and after it.  init: what
-    the buffer holds before the call (an input, or an in-place operand); None: filler, an output or workspace."""
-
-    def __init__(self, shape, dtype, dev, init=None):
-        shape = tuple(shape)
-        unit = max(1, math.prod(shape[1:]))
-        self.guard = max(2, -(-64 // unit))
-        self.n = shape[0]
-        self.alloc = _filler(torch.empty((self.n + 2 * self.guard,) + shape[1:], dtype=dtype, device=dev))
-        self.init = None if init is None else init.to(dev)
-        self.reset()
-
-    def mid(self):
-        return self.alloc[self.guard:self.guard + self.n]
-
-    def reset(self):
-        if self.init is None:
-            _filler(self.mid())
-        else:
-            self.mid().copy_(self.init)
-
-    def ptr(self):
-        return self.mid().data_ptr()
-
-    def guards_untouched(self):
-        return _is_filler(self.alloc[:self.guard]) and _is_filler(self.alloc[self.guard + self.n:])
-
-
-def _finite_parts(got, ref, what):
-    """NaN and Inf sit where the reference has them; returns the finite rest."""
-    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
-    assert torch.equal(torch.isnan(got), torch.isnan(ref)), what + ": NaN elsewhere than in the reference ({} vs {})".format(int(torch.isnan(got).sum()), int(torch.isnan(ref).sum()))
-    for inf in (INF, -INF):
-        assert torch.equal(got == inf, ref == inf), what + ": {} elsewhere than in the reference".format(inf)
-    ok = torch.isfinite(ref)
-    return got[ok], ref[ok]
-
-
-def _exact(got, ref, what):
-    g, r = _finite_parts(got, ref, what)
-    assert torch.equal(g, r), what + ": not equal, max abs err {:.3e}".format(float((g.double() - r.double()).abs().max()) if g.numel() else 0.0)
-
-
-def _rel(err, ref):
-    return err / max(1.0, float(ref.abs().max())) if ref.numel() else 0.0
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # the rows of each entry point: _build_X(c, g, dev, B) -> check(got); B.put / B.out register the buffers
 # ---------------------------------------------------------------------------------------------------------------
-class Bufs:
-    def __init__(self, dev):
-        self.dev, self.p, self.ins, self.outs = dev, {}, {}, {}
-
-    def put(self, name, t, key=None):
-        b = Buf(t.shape, t.dtype, self.dev, init=t)
-        self.ins[name] = b
-        self.p[key or name] = b.ptr()
-        return b
-
-    def out(self, name, shape, dtype=torch.float32, init=None):
-        b = Buf(shape, dtype, self.dev, init=init)
-        self.outs[name] = b
-        self.p[name] = b.ptr()
-        return b
-
-
 def _select_host(c, g):
     n, C = g["n"], g["c"]
     gen = _gen(c)
@@ -176,7 +93,7 @@ def _select_host(c, g):
 
 
 def _build_select(c, g, dev, B):
-    n, C, cap, lv = g["n"], g["c"], g["cap"], g["levels"]
+    n, nc, cap, lv = g["n"], g["c"], g["cap"], g["levels"]
     logits, reg, ctr = _select_host(c, g)
     B.p["logits"] = [B.put("logits{}".format(i), t.permute(0, 2, 3, 1).contiguous()).ptr() for i, t in enumerate(logits)]
     B.p["regctr"] = [B.put("regctr{}".format(i), torch.cat([r, k], 1).permute(0, 2, 3, 1).contiguous()).ptr() for i, (r, k) in enumerate(zip(reg, ctr))]
@@ -195,8 +112,8 @@ def _build_select(c, g, dev, B):
         for i, (o, r, k) in enumerate(zip(logits, reg, ctr)):
             s = 8 << i
             per_level.append(O.fcos_single_level(O.compute_locations_per_level(o.shape[2], o.shape[3], s), o, r * s, k, 0.05, bool(g["with_ctr"])))
-            p32 = o.permute(0, 2, 3, 1).reshape(n, -1, C).sigmoid()
-            p64 = o.double().permute(0, 2, 3, 1).reshape(n, -1, C).sigmoid()
+            p32 = o.permute(0, 2, 3, 1).reshape(n, -1, nc).sigmoid()
+            p64 = o.double().permute(0, 2, 3, 1).reshape(n, -1, nc).sigmoid()
             if g["with_ctr"]:
                 p32 = p32 * k.permute(0, 2, 3, 1).reshape(n, -1, 1).sigmoid()
                 p64 = p64 * k.double().permute(0, 2, 3, 1).reshape(n, -1, 1).sigmoid()
@@ -223,9 +140,9 @@ def _build_select(c, g, dev, B):
             assert torch.equal(cls[i, :w].long(), cand["classes"][:w]), what + ": classes"
             assert torch.equal(loc[i, :w], cand["locations"][:w]), what + ": locations"
             for a, b, name in ((box[i, :w], cand["boxes"][:w], "cand boxes"), (score[i, :w], cand["scores"][:w], "cand scores")):
-                a, b = _finite_parts(a, b, what + " " + name)
-                worst = max(worst, _rel(close(a, b, 1e-6, "tail " + name), b))
-            assert _is_filler(box[i, w:]) and _is_filler(score[i, w:]) and _is_filler(cls[i, w:]) and _is_filler(loc[i, w:]), what + ": written past the candidates"
+                a, b = C.finite_parts(a, b, what + " " + name)
+                worst = max(worst, C.rel(close(a, b, 1e-6, "tail " + name), b))
+            assert C.is_filler(box[i, w:]) and C.is_filler(score[i, w:]) and C.is_filler(cls[i, w:]) and C.is_filler(loc[i, w:]), what + ": written past the candidates"
             per_block = torch.cat([F.pad(mk[i].long(), (0, -mk.shape[1] % 4096)).view(-1, 4096).sum(1) for mk in masks])
             offsets.append(torch.cumsum(per_block, 0) - per_block)
         assert torch.equal(got["block_counts"].long(), torch.cat(offsets)), what + ": the workspace must hold the exclusive scan of the block counts"
@@ -287,7 +204,7 @@ def _build_nms(c, g, dev, B):
     gen = torch.Generator().manual_seed(77) if c["data"] == "per_class" else _gen(c)
     cnts = [min(v, cap) for v in g["counts"]]
     box, score = torch.full((n, cap, 4), NAN), torch.full((n, cap), NAN)
-    cls, loc = torch.full((n, cap), SENTINEL[torch.int32], dtype=torch.int32), torch.full((n, cap, 2), NAN)
+    cls, loc = torch.full((n, cap), C.SENTINEL[torch.int32], dtype=torch.int32), torch.full((n, cap, 2), NAN)
     for i, m in enumerate(cnts):
         kind = c["data"] if c["data"] != "mixed" else ("grid", "grid", "fallback")[i]
         if m:
@@ -327,8 +244,8 @@ def _build_nms(c, g, dev, B):
             tail = slice(i * topk + kk, (i + 1) * topk)
             assert int(got["out_count"][i]) == kk, (what, i, int(got["out_count"][i]), kk)
             assert torch.equal(got["out_idx"][sl].long(), keep), what + ": kept indices, image {}".format(i)
-            assert _same_bits(got["out_box"][sl], b[keep]) and _same_bits(got["out_score"][sl], s[keep]), what + ": boxes / scores are copies"
-            assert torch.equal(got["out_cls"][sl], k[keep]) and _same_bits(got["out_loc"][sl], loc[i, :m][keep]), what + ": classes / locations"
+            assert C.same_bits(got["out_box"][sl], b[keep]) and C.same_bits(got["out_score"][sl], s[keep]), what + ": boxes / scores are copies"
+            assert torch.equal(got["out_cls"][sl], k[keep]) and C.same_bits(got["out_loc"][sl], loc[i, :m][keep]), what + ": classes / locations"
             for name in ("out_box", "out_score", "out_cls", "out_loc"):
                 assert bool((got[name][tail] == 0).all()), what + ": the unused tail of {} must hold zeros".format(name)
             assert bool((got["out_idx"][tail] == -1).all()), what + ": the unused tail of out_idx must hold -1"
@@ -338,7 +255,7 @@ def _build_nms(c, g, dev, B):
             # "attempt = (cnt > 2 * NEED ? 0 : 1)"); the bin cut of the prefix ("hist12[k0[i] >> 20]", "the bin where the count reaches
             # NEED"); the full sort ends in (k0, v0), the prefix sort in (k1, v1) ("after 4 passes the sorted order is back in the buffer
             # the passes started from"); the fall-back ("if (s_nkept >= topk || sorted_cnt >= cnt) break")
-            key = (~_bits(s)).long() & 0xFFFFFFFF
+            key = (~C.bits(s)).long() & 0xFFFFFFFF
             order = torch.sort(key, stable=True)[1]
             assert torch.equal(order, torch.sort(s, descending=True, stable=True)[1]), what + ": the key order is torch's descending order"
             path, scnt = "full", m
@@ -413,9 +330,9 @@ def _build_roi(c, g, dev, B):
         assert torch.equal(levels[valid], want_lv), what + ": levels differ from the oracle's fp32 rule"
         assert bool((levels[~valid] == -1).all()), what + ": slots past counts must get level -1"
         assert bool((y[~valid][..., :ch] == 0).all()), what + ": slots past counts must be zero"
-        assert _is_filler(y[..., ch:]), what + ": channels >= C of the output buffer must be untouched"
-        a, b = _finite_parts(y[valid][..., :ch].permute(0, 3, 1, 2), want, what)
-        return _rel(close(a, b, 1e-5, "tail roi_align features"), b)
+        assert C.is_filler(y[..., ch:]), what + ": channels >= C of the output buffer must be untouched"
+        a, b = C.finite_parts(y[valid][..., :ch].permute(0, 3, 1, 2), want, what)
+        return C.rel(close(a, b, 1e-5, "tail roi_align features"), b)
     return check
 
 
@@ -442,9 +359,9 @@ def _build_sam(c, g, dev, B):
         if c["data"] == "nonfinite":
             bad = torch.isnan(ref).flatten(1).any(1)
             assert bad.tolist() == [i == 1 for i in range(len(rows))], what + ": the NaN must stay inside its RoI in the reference"
-        assert _same_bits(got["x"][~valid], x[~valid]), what + ": slots at or beyond counts[n] must not be written"
-        a, b = _finite_parts(got["x"][valid].double().permute(0, 3, 1, 2), ref, what)
-        return _rel(close(a, b, 2e-6, "tail spatial attention"), b)
+        assert C.same_bits(got["x"][~valid], x[~valid]), what + ": slots at or beyond counts[n] must not be written"
+        a, b = C.finite_parts(got["x"][valid].double().permute(0, 3, 1, 2), ref, what)
+        return C.rel(close(a, b, 2e-6, "tail spatial attention"), b)
     return check
 
 
@@ -474,15 +391,15 @@ def _build_predict(c, g, dev, B):
         if c["data"] == "nonfinite":
             assert int(torch.isnan(ref).sum()) == 1 and bool(torch.isnan(ref[1]).any())
         masks = got["masks"]
-        a, b = _finite_parts(masks[valid].double(), torch.sigmoid(ref), what + " masks")
+        a, b = C.finite_parts(masks[valid].double(), torch.sigmoid(ref), what + " masks")
         worst = close_abs(a, b, 2e-6, "tail mask_predict masks")
         assert bool((masks[~valid] == 0).all()), what + ": slots past counts must be exactly 0"
         if g["logits"]:
-            a, b = _finite_parts(got["logits_opt"][valid].double(), ref, what + " logits")
-            worst = max(worst, _rel(close(a, b, 1e-5, "tail mask_predict logits"), b))
+            a, b = C.finite_parts(got["logits_opt"][valid].double(), ref, what + " logits")
+            worst = max(worst, C.rel(close(a, b, 1e-5, "tail mask_predict logits"), b))
             assert bool((got["logits_opt"][~valid] == 0).all()), what + ": slots past counts must be exactly 0"
         else:
-            assert _is_filler(got["logits_opt"]), what + ": logits_opt was not handed in"
+            assert C.is_filler(got["logits_opt"]), what + ": logits_opt was not handed in"
         return worst
     return check
 
@@ -501,9 +418,9 @@ def _build_pool(c, g, dev, B):
     def check(got):
         what = c["id"]
         y = got["y"]
-        _exact(y[..., y_co], F.max_pool2d(masks[:, None], 2)[:, 0], what)
+        C.exact(y[..., y_co], F.max_pool2d(masks[:, None], 2)[:, 0], what)
         assert bool((y[..., y_co + 1:] == 0).all()), what + ": the pad channels must be zeroed"
-        assert _same_bits(y[..., :y_co], y0[..., :y_co]), what + ": the feature channels must be untouched"
+        assert C.same_bits(y[..., :y_co], y0[..., :y_co]), what + ": the feature channels must be untouched"
         if c["data"] == "nonfinite":
             assert bool(torch.isnan(y[0, 0, 0, y_co])) and bool((y[..., y_co] == INF).any())
         return 0.0
@@ -526,7 +443,7 @@ def _build_iou(c, g, dev, B):
     B.out("out", (r,))
 
     def check(got):
-        _exact(got["out"], scores * iou[torch.arange(r), cls], c["id"])
+        C.exact(got["out"], scores * iou[torch.arange(r), cls], c["id"])
         return 0.0
     return check
 
@@ -570,7 +487,7 @@ def _build_paste(c, g, dev, B):
     def check(got):
         what = c["id"]
         if c["r"] == 0:
-            assert _is_filler(got["out"]), what + ": R = 0 must touch nothing"
+            assert C.is_filler(got["out"]), what + ": R = 0 must touch nothing"
             return 0.0
         v = _paste_values(masks, boxes, h, w)
         nan = torch.isnan(v)
@@ -613,7 +530,7 @@ def _build_pack(c, g, dev, B):
         if kp:
             parts.append(t["kps"].reshape(n, -1))
         want = torch.cat(parts + [t["counts"].float()[:, None]], 1)
-        assert _same_bits(got["rec"], want), c["id"] + ": the record is not the torch assembly bit for bit"
+        assert C.same_bits(got["rec"], want), c["id"] + ": the record is not the torch assembly bit for bit"
         return 0.0
     return check
 
@@ -630,7 +547,7 @@ def _build_prep(c, g, dev, B):
         what = c["id"]
         mean, std = (torch.tensor(v, dtype=torch.float32).double().view(3, 1, 1) for v in (tc.PREP_MEAN, tc.PREP_STD))
         dst = got["dst"]
-        a, b = _finite_parts(dst[:, :h, :w].double(), (src.double() - mean) / std, what)
+        a, b = C.finite_parts(dst[:, :h, :w].double(), (src.double() - mean) / std, what)
         pad = torch.ones((3, hp, wp), dtype=torch.bool)
         pad[:, :h, :w] = False
         assert bool((dst[pad] == 0).all()), what + ": the padding must be exactly zero"
@@ -730,15 +647,15 @@ def _build_kpd(c, g, dev, B):
         gaps = [rf["gap"] > 1e-4 * max(1.0, abs(rf["value"])) for ref in refs.values() for rf in ref]
         assert c["data"] == "zeros" or sum(gaps) >= len(gaps) // 2, what + ": fewer than half of the positions are unique maxima: choose another seed"
         assert bool((out[~valid] == 0).all()), what + ": slots past counts must be zeros"
-        assert _is_filler(ws[~valid]), what + ": the workspace of a slot past counts must not be written"
+        assert C.is_filler(ws[~valid]), what + ": the workspace of a slot past counts must not be written"
         exact = total = 0
         worst = 0.0
         for ri, ref in refs.items():
             box = boxes.view(-1, 4)[ri]
             used = _kp_bands(box)
             rec = ws[ri, :, :32].reshape(K, 8, 4)
-            assert bool((rec[:, used:, 0] == -INF).all()) and bool((_bits(rec[:, used:, 1:3]) == -1).all()), what + ": RoI {}: the bands past the box's rows must be empty records".format(ri)
-            assert bool((_bits(rec[:, :used, 1]) >= 0).all()), what + ": RoI {}: a band with rows left an empty record".format(ri)
+            assert bool((rec[:, used:, 0] == -INF).all()) and bool((C.bits(rec[:, used:, 1:3]) == -1).all()), what + ": RoI {}: the bands past the box's rows must be empty records".format(ri)
+            assert bool((C.bits(rec[:, :used, 1]) >= 0).all()), what + ": RoI {}: a band with rows left an empty record".format(ri)
             x0, y0, w, h, wc, hc = KR.box_geometry(box)
             for k, rf in enumerate(ref):
                 x, y, score = (float(v) for v in out[ri, k])
@@ -775,42 +692,18 @@ BUILD = {tc.SELECT: _build_select, tc.NMS: _build_nms, tc.ROI: _build_roi, tc.SA
          tc.IOU: _build_iou, tc.PASTE: _build_paste, tc.PACK: _build_pack, tc.PACK_KP: _build_pack, tc.PREP: _build_prep, tc.KPD: _build_kpd}
 
 
-def _run_row(c, dev, lib):
-    B = Bufs(dev)
+def _conform(c, dev, lib):
+    B = C.Bufs(dev)
     check = BUILD[c["entry"]](c, _sane(c), dev, B)
-    before = {k: b.alloc.clone() for k, b in B.ins.items()}
+    if c["wrapper"]:
+        B.again = [dict(c, wrapper=False)]        # the wrapper's row also as the _pool call
 
     def launch(row):
         rc = tc.call(lib, row, B.p, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         err = lib.cmk_last_error().decode() if rc != 0 else ""
         torch.cuda.synchronize()
         return rc, err
-
-    def inputs_unchanged(why):
-        for k, b in B.ins.items():
-            assert _same_bits(b.alloc, before[k]), (c["id"], k, why)
-
-    rc, err = launch(c)
-    if c["answer"] == "refuse":
-        assert rc == tc.CMK_EINVAL and err.strip(), (c["id"], "declared refuse: the argument checks' code is CMK_EINVAL, a launch that failed gives another", rc, err)
-        for name, b in B.outs.items():
-            assert b.guards_untouched() and (_is_filler(b.mid()) if b.init is None else _same_bits(b.mid(), b.init)), (c["id"], name, "written before the refusal")
-        inputs_unchanged("changed by a refused call")
-        return None
-    assert rc == 0, (c["id"], "declared accept, refused", err)
-    for name, b in B.outs.items():
-        assert b.guards_untouched(), (c["id"], name, "written into a guard")
-    inputs_unchanged("an input of the call changed")
-    first = {name: b.mid().clone() for name, b in B.outs.items()}
-    d = check({name: t.cpu() for name, t in first.items()})
-    for row in [c] + ([dict(c, wrapper=False)] if c["wrapper"] else []):       # the same call again; the wrapper's row also as the _pool call
-        for b in B.outs.values():
-            b.reset()
-        rc2, err2 = launch(row)
-        assert rc2 == 0, (c["id"], err2)
-        for name, b in B.outs.items():
-            assert _same_bits(b.mid(), first[name]), (c["id"], name, "a second call gave other bits")
-    return d
+    return C.run_row(c, B, launch, check, einval=tc.CMK_EINVAL)
 
 
 @pytest.fixture(scope="module")
@@ -819,19 +712,15 @@ def bars():
     and its larger maximum put a correct kernel past it (the fp32 source position of a 1300 px wide bicubic resize alone moves the maximum by
     1e-5).  So the bar is the larger of 1e-5 and the project's recipe: 4x the largest distance of torch's own fp32 CPU result from the float64
     one over the table's accepted rows, from the references alone, before any kernel runs."""
-    worst = 0.0
-    for c in CASES:
-        if c["entry"] == tc.KPD and c["answer"] == "accept":
-            _, boxes, _, _, refs = _kpd_host(c, _sane(c))
-            d = 0.0
-            for ri, (clean, ref) in refs.items():
-                s64 = torch.tensor([rf["xys"][2] for rf in ref], dtype=torch.float64)
-                d = max(d, float(((_kp_scores32(clean, boxes.view(-1, 4)[ri]).double() - s64).abs() / s64).max()))
-            print("{}: torch fp32 keypoint scores vs float64 {:.3e}".format(c["id"], d))
-            worst = max(worst, d)
-    assert worst > 0.0
-    _BARS["kp_score"] = max(1e-5, 4.0 * worst)
-    print("keypoint scores: largest fp32 distance {:.3e}, bar {:.3e}".format(worst, _BARS["kp_score"]))
+    def distance(c):
+        _, boxes, _, _, refs = _kpd_host(c, _sane(c))
+        d = 0.0
+        for ri, (clean, ref) in refs.items():
+            s64 = torch.tensor([rf["xys"][2] for rf in ref], dtype=torch.float64)
+            d = max(d, float(((_kp_scores32(clean, boxes.view(-1, 4)[ri]).double() - s64).abs() / s64).max()))
+        return d
+    _BARS["kp_score"] = C.fp32_bar("keypoint scores", [c for c in CASES if c["entry"] == tc.KPD and c["answer"] == "accept"], distance,
+                                   what="torch fp32 keypoint scores", floor=1e-5)
     return _BARS
 
 
@@ -843,20 +732,4 @@ def test_tail_conformance(dev, cmk_lib, bars, entry):
     absolute).  Keypoint scores: at most 1.75e-06 relative at S <= 7 and 1.07e-05 at S = 16 (the 1300 x 7 box), where torch's own fp32 CPU
     operators are 9.30e-06 from float64, so the bar came out max(1e-5, 4 x 9.30e-06) = 3.72e-05.  The NMS keep lists and copies, levels,
     pooled masks, mask-IoU scores, records and paste bits are exact."""
-    mine = [c for c in CASES if c["entry"] == entry and not c["host_only"]]
-    failed, launched, refused, worst = [], 0, 0, 0.0
-    for c in mine:
-        try:                                      # a row that misses its check does not hide the ones after it (a device error is no AssertionError and ends the test)
-            d = _run_row(c, dev, cmk_lib)
-            if d is None:
-                refused += 1
-            else:
-                launched += 1
-                worst = max(worst, d)
-                print("{}: {:.3e}".format(c["id"], d))
-        except AssertionError as err:
-            failed.append("{}: {}".format(c["id"], str(err).splitlines()[0] if str(err) else "assert"))
-    print("{}: largest distance on record {:.3e}".format(entry, worst))
-    assert not failed, "\n".join(["{} of {} rows failed".format(len(failed), len(mine))] + failed)
-    assert launched == sum(c["answer"] == "accept" for c in mine) and launched > 0
-    assert refused == sum(c["answer"] == "refuse" for c in mine) and refused > 0
+    C.run_entry(entry, [c for c in CASES if c["entry"] == entry and not c["host_only"]], lambda c: _conform(c, dev, cmk_lib))

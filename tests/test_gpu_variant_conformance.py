@@ -23,20 +23,18 @@ thread of the loop's second trip and for the last image; every other image must 
 with the sentinel intact outside it.
 
 Observed values: the docstring of test_variant_conformance and DESIGN.md "Variant-conv conformance table"."""
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 from centermask2_amd import ops
+from tests import conformance as C
 from tests import variant_cases as vc
 from tests.deform_ref import deform_conv3x3_ref_corners, make_offsets
 
 pytestmark = pytest.mark.gpu
 
-NAN, INF = float("nan"), float("inf")
-PAD = 1024            # floats of NaN before and after a second_trip output: whole guard images would not tell more
+NAN, INF = C.NAN, C.INF
 CASES = vc.all_cases()
 INDEX = {c["id"]: i for i, c in enumerate(CASES)}
 _HOST = {}            # row id -> the host tensors and references of a row (the bars and the rows share them)
@@ -161,82 +159,26 @@ def _host(c):
     return out
 
 
-def _dist(a, ref):
-    return float((a.double() - ref).abs().max()) / max(1.0, float(ref.abs().max()))
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # a row on the device
 # ---------------------------------------------------------------------------------------------------------------
-class Out:
-    """The output: `alloc` is NaN everywhere but `region(alloc)`, which the call must write, and `keep(alloc)` (a same_buffer row: the input
-    slice of the same tensor), which it must not."""
-
-    def __init__(self, alloc, region, keep=None, kept=None):
-        self.alloc, self.region, self.keep, self.kept = alloc, region, keep, kept
-        self.reset()
-
-    def reset(self):
-        self.region(self.alloc).fill_(NAN)
-
-    def outside_is_nan(self):
-        t = self.alloc.clone()
-        self.region(t).fill_(NAN)
-        if self.keep is not None:
-            if not _same_bits(self.keep(t), self.kept):
-                return False
-            self.keep(t).fill_(NAN)
-        return bool(torch.isnan(t).all())
-
-
-def _guarded(c, n, rest, dev):
-    """(alloc, middle): n images of shape `rest` between NaN guards — one guard image each side, or PAD floats for a second_trip row."""
-    if c["feature"] == "second_trip":
-        numel = n * math.prod(rest)
-        alloc = torch.full((numel + 2 * PAD,), NAN, device=dev)
-        return alloc, (lambda a: a[PAD:PAD + numel].view((n,) + tuple(rest)))
-    alloc = torch.full((n + 2,) + tuple(rest), NAN, device=dev)
-    return alloc, (lambda a: a[1:n + 1])
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
-def _finite_parts(got, ref, what, nan_is_zero=False):
-    """NaN and Inf sit where the reference has them (nan_is_zero: the fused ReLU's documented relu(NaN) = 0); returns the finite rest."""
-    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
-    ref_nan = torch.isnan(ref)
-    if nan_is_zero:
-        assert not bool(torch.isnan(got).any()), what + ": {} NaN behind the ReLU, the float64 result has {}".format(int(torch.isnan(got).sum()), int(ref_nan.sum()))
-        assert bool((got[ref_nan] == 0).all()), what + ": relu(NaN) must be 0"
-    else:
-        assert torch.equal(torch.isnan(got), ref_nan), what + ": NaN elsewhere than in the float64 result ({} vs {})".format(int(torch.isnan(got).sum()), int(ref_nan.sum()))
-    for inf in (INF, -INF):
-        assert torch.equal(got == inf, ref == inf), what + ": {} elsewhere than in the float64 result".format(inf)
-    ok = torch.isfinite(ref)
-    return got[ok], ref[ok]
-
-
 def _ceil4(v):
     return -(-v // 4) * 4
 
 
 def _build(c, dev, bars):
-    """(pointers, Out, read-only inputs {name: tensor}, check(cpu region) -> normalised distance)."""
+    """(the row's buffers, the output "y" among them, check(the output view on the host) -> normalised distance)."""
     e = c["entry"]
     accept = c["answer"] == "accept"
     what = c["id"]
-    p, ro = {}, {}
+    B = C.Bufs(dev)
 
     def put(name, t):
-        ro[name] = t.to(dev)
-        p[name] = ro[name].data_ptr()
-        return ro[name]
+        return B.put(name, t, guard=256)
+
+    def out(rest, **kw):
+        """The output: c["n"] maps of shape `rest` between guards (conformance.map_guard)."""
+        return B.out("y", (max(1, c["n"]),) + tuple(rest), guard=C.map_guard(c, rest), **kw)
 
     if not accept:
         # a refused geometry (N = 0, C = 6, a slice that leaves its pixel): buffers large enough for whatever the row says, contents arbitrary
@@ -250,21 +192,18 @@ def _build(c, dev, bars):
         ho, wo = ((h - 1) // 2 // 2 + 1, (w - 1) // 2 // 2 + 1) if e == vc.STEM7 else ((h - 1) // s + 1, (w - 1) // s + 1)
         g = torch.Generator().manual_seed(1)
         if c["same_buffer"]:
-            alloc, mid = _guarded(c, n, (h, w, max(x_cs, y_cs)), dev)
-            out = Out(alloc, mid)
-            p["x"] = p["y"] = mid(alloc).data_ptr()
+            out((h, w, max(x_cs, y_cs)))
+            B.p["x"] = B.p["y"]
         else:
             put("x", torch.randn((n, 3, h, w) if e == vc.STEM7 else (n, h, w, x_cs), generator=g))
-            alloc, mid = _guarded(c, n, (ho, wo, y_cs), dev)
-            out = Out(alloc, mid)
-            p["y"] = mid(alloc).data_ptr()
+            out((ho, wo, y_cs))
         put("w", torch.randn((1 << 19,), generator=g))
         if "scale" in vc.POINTERS[e]:
             put("scale", torch.ones(1024))
             put("shift", torch.zeros(1024))
         if e == vc.DEFORM:
             put("offsets", torch.zeros((n, h, w, max(c["off_cs"] or 0, 27 * max(1, c["dg"])) + 8)))
-        return p, out, ro, None
+        return B, None
 
     hst = _host(c)
     n, h, w, ch = c["n"], c["h"], c["w"], c["c"]
@@ -282,16 +221,11 @@ def _build(c, dev, bars):
     if c["same_buffer"]:
         x_cs, x_co = c["x_view"]
         assert x_cs == y_cs and (ho, wo) == (h, w)
-        alloc, mid = _guarded(c, n, (h, w, y_cs), dev)
-        xdev = hst["x"].to(dev)
-        mid(alloc)[..., x_co:x_co + xc] = xdev
-        out = Out(alloc, lambda a: mid(a)[..., y_co:y_co + ch], keep=lambda a: mid(a)[..., x_co:x_co + xc], kept=xdev)
-        p["x"] = p["y"] = mid(alloc).data_ptr()
+        out((h, w, y_cs), window=(y_co, ch), keep=(x_co, xc, hst["x"]))        # the input slice of the same tensor: the call must keep it
+        B.p["x"] = B.p["y"]
     else:
         put("x", hst["x"] if e == vc.STEM7 else wide(hst["x"], c["x_view"]))
-        alloc, mid = _guarded(c, n, (ho, wo, y_cs), dev)
-        out = Out(alloc, (lambda a: mid(a)[..., y_co:y_co + ch]) if c["y_view"] else mid)
-        p["y"] = mid(alloc).data_ptr()
+        out((ho, wo, y_cs), window=(y_co, ch) if c["y_view"] else None)
     put("w", hst["w"])
     if "scale" in vc.POINTERS[e]:
         put("scale", hst["scale"])
@@ -311,14 +245,14 @@ def _build(c, dev, bars):
         if c["poison"]:
             bad = ~torch.isfinite(ref)
             assert bool(bad.any()) and not bool(bad.all()), what + ": the float64 result holds non-finite and finite outputs"
-        a, r = _finite_parts(got.double(), ref, what, nan_is_zero=(e == vc.DEFORM and bool(c["relu"])))
+        a, r = C.finite_parts(got.double(), ref, what, nan_is_zero=(e == vc.DEFORM and bool(c["relu"])))
         m = max(1.0, float(r.abs().max())) if r.numel() else 1.0
         err = float((a - r).abs().max()) if r.numel() else 0.0
         bar = {vc.DEFORM: min(1e-3, 2e-4 * m), vc.DWACT: 1e-5 * m, vc.DW: 1e-5 * m, vc.GROUP: bars["group"] * m, vc.STEM7: bars["stem"] * m}[e]
         assert err <= bar, "{}: max abs err {:.3e} from float64 > bar {:.3e}".format(what, err, bar)
         return err / m
 
-    return p, out, ro, check
+    return B, check
 
 
 def _launch(c, p, lib):
@@ -328,34 +262,21 @@ def _launch(c, p, lib):
     return rc, err
 
 
-def _run_row(c, dev, lib, bars):
-    p, out, ro, check = _build(c, dev, bars)
-    before = {k: v.clone() for k, v in ro.items()}
-    rc, err = _launch(c, p, lib)
-    if c["answer"] == "refuse":
-        assert rc != 0 and err.strip(), (c["id"], "declared refuse, launched", rc)
-        assert bool(torch.isnan(out.alloc).all()), (c["id"], "written before the refusal")
-        for k, v in ro.items():
-            assert _same_bits(v, before[k]), (c["id"], k, "changed by a refused call")
-        return None
-    assert rc == 0, (c["id"], "declared accept, refused", err)
-    assert out.outside_is_nan(), (c["id"], "written outside the output view or into a guard")
-    for k, v in ro.items():
-        assert _same_bits(v, before[k]), (c["id"], k, "an input of the call changed")
-    first = out.region(out.alloc).clone()
-    d = check(first.cpu())
-    out.reset()
-    rc2, err2 = _launch(c, p, lib)
-    assert rc2 == 0, (c["id"], err2)
-    assert _same_bits(out.region(out.alloc), first), (c["id"], "a second call gave other bits")
+def _conform(c, dev, lib, bars):
+    B, check = _build(c, dev, bars)
+
+    def dense_call(first):
+        """A row with views also as a dense call, bit-equal."""
+        dense = dict(c, x_view=None, y_view=None, off_cs=None)
+        B3, _ = _build(dense, dev, bars)
+        rc3, err3 = _launch(dense, B3.p, lib)
+        assert rc3 == 0, (c["id"], "the dense call", err3)
+        assert torch.equal(B3.outs["y"].region(), first["y"]), (c["id"], "the dense call gave other bits than the view call")
+    if (c["x_view"] or c["y_view"] or c["off_cs"]) and not c["same_buffer"]:
+        B.extra = dense_call
+    d = C.run_row(c, B, lambda row: _launch(row, B.p, lib), check and (lambda got: check(got["y"])))
     if c["feature"] == "second_trip":
         _HOST.pop(c["id"], None)                  # hundreds of MB that nothing reads again
-    if (c["x_view"] or c["y_view"] or c["off_cs"]) and not c["same_buffer"]:
-        dense = dict(c, x_view=None, y_view=None, off_cs=None)
-        p3, out3, _, _ = _build(dense, dev, bars)
-        rc3, err3 = _launch(dense, p3, lib)
-        assert rc3 == 0, (c["id"], "the dense call", err3)
-        assert _same_bits(out3.region(out3.alloc), first), (c["id"], "the dense call gave other bits than the view call")
     return d
 
 
@@ -363,19 +284,8 @@ def _run_row(c, dev, lib, bars):
 def bars():
     """{"group", "stem"}: 4x the largest normalised distance of torch's own fp32 CPU result from the float64 one over the accepted finite
     rows of the table — from the references alone, before any kernel runs."""
-    out = {}
-    for name, entry in (("group", vc.GROUP), ("stem", vc.STEM7)):
-        worst = 0.0
-        for c in CASES:
-            if c["entry"] == entry and c["answer"] == "accept" and not c["poison"]:
-                hst = _host(c)
-                d = _dist(hst["ref32"], hst["ref64"])
-                worst = max(worst, d)
-                print("{}: torch fp32 vs float64 {:.3e}".format(c["id"], d))
-        assert worst > 0.0
-        out[name] = 4.0 * worst
-        print("{}: largest fp32 distance {:.3e}, bar {:.3e}".format(name, worst, 4.0 * worst))
-    return out
+    return {name: C.fp32_bar(name, [c for c in CASES if c["entry"] == entry and c["answer"] == "accept" and not c["poison"]],
+                             lambda c: C.dist(_host(c)["ref32"], _host(c)["ref64"])) for name, entry in (("group", vc.GROUP), ("stem", vc.STEM7))}
 
 
 @pytest.mark.parametrize("entry", vc.ENTRIES)
@@ -386,20 +296,4 @@ def test_variant_conformance(dev, cmk_lib, bars, entry):
     max(1, max|ref|) from float64 (Cout 128, Cin 32) against its bar of 2e-4, the fused depth-wise kernel 3.92e-07 and the plain one 1.34e-07
     against 1e-5.  On the library before the deformable kernel stopped multiplying stand-in loads by 0, the four poison rows fail: 19, 29 and
     30 non-finite pixels of 30 in the image with an Inf at (0,0) where float64 has 4, 9 and 6."""
-    mine = [c for c in CASES if c["entry"] == entry and not c["host_only"]]
-    failed, launched, refused, worst = [], 0, 0, 0.0
-    for c in mine:
-        try:                                      # a row that misses its check does not hide the ones after it (a device error is no AssertionError and ends the test)
-            d = _run_row(c, dev, cmk_lib, bars)
-            if d is None:
-                refused += 1
-            else:
-                launched += 1
-                worst = max(worst, d)
-                print("{}: {:.3e}".format(c["id"], d))
-        except AssertionError as err:
-            failed.append("{}: {}".format(c["id"], str(err).splitlines()[0] if str(err) else "assert"))
-    print("{}: largest distance on record {:.3e}".format(entry, worst))
-    assert not failed, "\n".join(["{} of {} rows failed".format(len(failed), len(mine))] + failed)
-    assert launched == sum(c["answer"] == "accept" for c in mine) and launched > 0
-    assert refused == sum(c["answer"] == "refuse" for c in mine) and refused > 0
+    C.run_entry(entry, [c for c in CASES if c["entry"] == entry and not c["host_only"]], lambda c: _conform(c, dev, cmk_lib, bars))
