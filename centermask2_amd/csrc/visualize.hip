@@ -875,7 +875,9 @@ extern "C" int cmk_vis_track_assign(const double* iou, const int32_t* inter, con
         if ((iou != nullptr) == (inter != nullptr)) return fail(CMK_EINVAL, "%s: exactly one of the iou and inter tables must be given", what);
         if (inter && (!old_areas || !new_areas)) return fail(CMK_EINVAL, "%s: null pointer (the inter table needs both area arrays)", what);
     }
-    if (old_boxes == out_boxes || old_classes == out_classes || old_ids == out_ids || old_ttl == out_ttl)
+    const int64_t cap = max_tracks;                                  // a thread reads old row t after another wrote out row t: byte ranges, not pointers
+    if (vis_overlap(out_boxes, 16 * cap, old_boxes, 16 * cap) || vis_overlap(out_classes, 8 * cap, old_classes, 8 * cap) ||
+        vis_overlap(out_ids, 4 * cap, old_ids, 4 * cap) || vis_overlap(out_ttl, 4 * cap, old_ttl, 4 * cap))
         return fail(CMK_EINVAL, "%s: the new table overlaps the old one; the update is out of place", what);
     hipLaunchKernelGGL(vis_track_assign_kernel, dim3(1), dim3(VT_MAX), 0, (hipStream_t)stream, (n && rows) ? iou : nullptr, inter, old_areas, new_areas,
                        rows, old_boxes, (const long long*)old_classes, old_ids, old_ttl, new_boxes, (const long long*)new_classes, n, max_tracks, ttl,

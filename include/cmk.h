@@ -518,7 +518,9 @@ int cmk_vis_record_ints(void);
  * the 41-glyph font (P = clamp(floor(score * 100 + 0.5), 0, 100) in float64, NaN -> 0; at most 32 glyphs), its plate rect clamped into the
  * image, and col = palette[k mod 64] (k the original index, or the class with color_by_class), edge = col*154 >> 8,
  * text = col + ((255 - col)*179 >> 8).  names: num_names rows of 32 glyph indices with name_lens; a class outside [0, num_names) is
- * named "C<id>".  palette: 64 x 3 bytes.  boxes (n,4), scores (n), classes (n) int64, order (n) int64.  n == 0: CMK_OK, no launch. */
+ * named "C<id>".  palette: 64 x 3 bytes.  boxes (n,4), scores (n), classes (n) int64, order (n) int64.  n == 0: CMK_OK, no launch.
+ * Nothing outside the inputs is read whatever they hold: an order[j] outside [0, n) stands for j, a name length is clamped into [0, 32],
+ * a glyph byte above 40 is glyph 40. */
 int cmk_vis_prepare(const float* boxes, const float* scores, const int64_t* classes, const int64_t* order, const uint8_t* names,
                     const int32_t* name_lens, int num_names, const uint8_t* palette, int n, int H, int W, int font_scale, int color_by_class,
                     int32_t* records, void* stream);
@@ -534,7 +536,8 @@ int cmk_vis_compose(const uint8_t* image_in, uint8_t* image_out, int H, int W, c
  * order: the skeleton's segments (num_segments pairs of keypoint indices; both ends visible; pixels within line_width / 2 of the segment,
  * exact in int64; colour col), then the visible points as discs of radius max(2, line_width + 1) in keypoint_color (bytes 0..2).  The
  * latest primitive wins a pixel: winner, (H,W) int32 scratch, takes the atomic maximum of the sequence numbers, a second pass colours.
- * num_keypoints in [1, 1024], num_segments in [0, 4096].  n == 0: CMK_OK, no launch. */
+ * A segment with an index outside [0, num_keypoints) is not drawn.  num_keypoints in [1, 1024], num_segments in [0, 4096].
+ * n == 0: CMK_OK, no launch. */
 int cmk_vis_keypoints(uint8_t* image, int H, int W, const float* keypoints, const int32_t* records, int n, int num_keypoints,
                       const int32_t* skeleton, int num_segments, float threshold, int line_width, int keypoint_color, int32_t* winner,
                       void* stream);
@@ -563,7 +566,8 @@ int cmk_vis_track_iou_boxes(const float* old_boxes, int rows, const float* new_b
  * order of j.  Every other old row misses: ttl - 1, and survives iff that is > 0.  The new table: the n new instances in order with
  * ttl = `ttl`, then the survivors in old order while they fit in max_tracks; the rest add to `dropped`.  src[slot] = j for a new row,
  * n + i for a survivor (the map cmk_vis_track_gather follows); track_ids[j] is the id of new instance j.  Always launches (n == 0 ages the
- * table).  ttl in [1, 255], threshold in [0, 1]; an out table that is an old table is refused. */
+ * table).  A NaN value counts as 0; counters[0] is clamped into [0, rows].  ttl in [1, 255], threshold in [0, 1].  Out of place: an out
+ * array overlapping its old array (max_tracks rows of each) is refused. */
 int cmk_vis_track_assign(const double* iou, const int32_t* inter, const int32_t* old_areas, const int32_t* new_areas, int rows,
                          const float* old_boxes, const int64_t* old_classes, const int32_t* old_ids, const int32_t* old_ttl,
                          const float* new_boxes, const int64_t* new_classes, int n, int max_tracks, int ttl, double threshold,
@@ -571,7 +575,9 @@ int cmk_vis_track_assign(const double* iou, const int32_t* inter, const int32_t*
                          int32_t* counters, void* stream);
 /* Mask mode, after cmk_vis_track_assign on the same src and counters: out row s < n_tracks gets the ceil(H*W/64) words and the area of
  * new instance src[s], or of old row src[s] - n.  rows: how many out rows can be live (n_tracks <= rows is the caller's bound; the grid).
- * Out of place: out_words overlapping old_words or new_words is refused, as is H*W >= 2^31 - 1.  rows == 0: CMK_OK, no launch. */
+ * Out of place: out_words overlapping old_words or new_words is refused, as is H*W >= 2^31 - 1.  rows == 0: CMK_OK, no launch.
+ * A src[s] that names neither (negative, or n + max_tracks and above) leaves out row s unwritten; rows at and beyond
+ * min(n_tracks, max_tracks, rows) are never written. */
 int cmk_vis_track_gather(const int32_t* src, const int32_t* counters, const uint64_t* old_words, const int32_t* old_areas,
                          const uint64_t* new_words, const int32_t* new_areas, int n, int rows, int max_tracks, int H, int W,
                          uint64_t* out_words, int32_t* out_areas, void* stream);

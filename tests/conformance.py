@@ -1,4 +1,4 @@
-"""The conformance harness: what the five kernel conformance tables (tests/*_cases.py) and their CPU and GPU test modules share.
+"""The conformance harness: what the six kernel conformance tables (tests/*_cases.py) and their CPU and GPU test modules share.
 
 The protocol of a row, stated once (run_row).  Every buffer handed to the call is the middle of a larger allocation of filler bytes (Buf).
 A refused row returns the table's refusal code with an error text and leaves every buffer untouched.  An accepted row writes nothing
@@ -16,7 +16,7 @@ import subprocess
 import numpy as np
 import torch
 
-from tests import conv_cases, image_cases, stream_cases, tail_cases, variant_cases
+from tests import conv_cases, image_cases, stream_cases, tail_cases, variant_cases, vis_cases
 
 NAN, INF = float("nan"), float("inf")
 SENTINEL = {torch.uint8: 0x5A, torch.int32: 0x5A5A5A5A, torch.int64: 0x5A5A5A5A5A5A5A5A}      # the integer filler, by dtype
@@ -24,13 +24,14 @@ PAD = 1024            # elements of filler before and after a second_trip output
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "centermask2_amd", "csrc")
 
 # cases file -> (its module, the files of csrc/ whose kernels it claims per instantiation).  The conv table claims the conv_*_kernel<>
-# instantiations of the library instead (tests/test_cpu_conv_conformance.py counts them); a sixth table is one more line
+# instantiations of the library instead (tests/test_cpu_conv_conformance.py counts them); a further table is one more line
 TABLES = {
     "tests/conv_cases.py": (conv_cases, ()),
     "tests/stream_cases.py": (stream_cases, ("elementwise.hip", "groupnorm.hip")),
     "tests/tail_cases.py": (tail_cases, ("detect.hip", "roi.hip", "prepost.hip", "keypoint.hip")),
     "tests/image_cases.py": (image_cases, image_cases.FILES),
     "tests/variant_cases.py": (variant_cases, ("conv_deform.hip", "dwconv_bn_act.hip", "conv_group3.hip", "stem7_pool.hip")),
+    "tests/vis_cases.py": (vis_cases, ("visualize.hip",)),
 }
 
 

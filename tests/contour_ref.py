@@ -51,6 +51,19 @@ def contours(mask):
     return loops
 
 
+def checkerboard(side, parity):
+    """side x side, pixel (r, c) set iff (r + c) % 2 == parity."""
+    ys, xs = np.mgrid[0:side, 0:side]
+    return (ys + xs) % 2 == parity
+
+
+def unit_squares(mask):
+    """Built, not traced: the contours of a mask whose set pixels touch only diagonally (a checkerboard, single pixels), where the right
+    turn at every saddle closes one unit square per set pixel, in row-major order of the pixels.  -> (pixels, 4, 2) int32 of (x, y)."""
+    ys, xs = np.nonzero(np.asarray(mask).astype(bool))                # row-major
+    return np.stack([np.stack([xs, ys], 1), np.stack([xs + 1, ys], 1), np.stack([xs + 1, ys + 1], 1), np.stack([xs, ys + 1], 1)], 1).astype(np.int32)
+
+
 def as_lists(loops):
     """Loops as (k,2) arrays or lists of pairs -> lists of (x, y) int tuples, for comparison with contours()."""
     return [[(int(x), int(y)) for x, y in np.asarray(lp).reshape(-1, 2)] for lp in loops]

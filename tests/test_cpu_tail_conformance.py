@@ -2,7 +2,7 @@
 exactly the __global__ kernels of csrc/detect.hip, csrc/roi.hip, csrc/prepost.hip and csrc/keypoint.hip as the built library instantiates
 them, every (entry point, feature) cell must have a row or a reason, and every refused row must be refused on dummy aligned pointers: every
 argument check of these entry points sits before its launch.  And the library-wide census: every kernel of the built library is claimed by
-exactly one of the five conformance tables (conv, stream, tail, image, variant) or by a named direct test module."""
+exactly one of the six conformance tables (conv, stream, tail, image, variant, vis) or by a named direct test module."""
 import glob
 import os
 
@@ -15,9 +15,8 @@ from tests import tail_cases as tc
 CASES = tc.all_cases()
 TESTS = os.path.dirname(os.path.abspath(__file__))
 
-# kernels outside the five tables: the source file of csrc/ that defines them -> the direct test module that launches them
+# kernels outside the six tables: the source file of csrc/ that defines them -> the direct test module that launches them
 DIRECT = {
-    "visualize.hip": "test_gpu_visualize.py",
     "conv.hip": "test_gpu_conv_conformance.py",      # the split-K reduction behind the conv table's splitk rows (no conv_*_kernel<> instantiation)
 }
 
@@ -63,8 +62,8 @@ def test_refused_rows_are_refused_before_any_launch(cmk_lib, entry):
 def test_every_kernel_of_the_library_is_claimed_exactly_once(cmk_lib):
     """Every __global__ kernel of csrc/ that the built library holds belongs to the conv table (the conv_*_kernel<...> instantiations that
     tests/test_cpu_conv_conformance.py counts), to the stream table, to the tail table, to the image table (rle.hip, mask_iou.hip and resize.hip,
-    claimed per instantiation), to the variant table (conv_deform.hip, dwconv_bn_act.hip, conv_group3.hip and stem7_pool.hip, per instantiation)
-    or to a direct test module named in DIRECT.  A new kernel that nobody claims fails here by name; no count is
+    claimed per instantiation), to the variant table (conv_deform.hip, dwconv_bn_act.hip, conv_group3.hip and stem7_pool.hip, per instantiation),
+    to the vis table (visualize.hip) or to a direct test module named in DIRECT.  A new kernel that nobody claims fails here by name; no count is
     written down."""
     from tests import conv_cases, test_cpu_conv_conformance as conv
     sources = sorted(os.path.basename(f) for f in glob.glob(os.path.join(C.CSRC, "*.hip")) + glob.glob(os.path.join(C.CSRC, "*.hpp")))
@@ -82,7 +81,7 @@ def test_every_kernel_of_the_library_is_claimed_exactly_once(cmk_lib):
     assert not unclaimed, "kernels that no table and no direct test module claims: {}".format(unclaimed)
     assert not twice, "kernels claimed more than once: {}".format(twice)
     assert all(claimed <= kernels for claimed in tables.values())
-    assert set(DIRECT) == {"visualize.hip", "conv.hip"}
+    assert set(DIRECT) == {"conv.hip"}
     assert not set(DIRECT) & set(ic.FILES), "a file of the image table is claimed per instantiation, not per file"
     for f, module in DIRECT.items():
         assert C.source_kernels([f]), "DIRECT names a file without kernels: " + f

@@ -114,6 +114,41 @@ def test_nan_box():
     assert np.isnan(tr.arrays()["boxes"][2, 1])
 
 
+@pytest.mark.parametrize("match,size,cap,ttl", [("box", (480, 640), 64, 8), ("box", (480, 640), 12, 2), ("mask", (37, 53), 64, 3), ("mask", (5, 7), 11, 8)])
+def test_assign_tables_is_the_tracker_on_tables(match, size, cap, ttl):
+    """video_ref.assign_tables (the rule on tables in plain loops, what the conformance rows of cmk_vis_track_assign are held to) against
+    RefTracker.update over the frames of video_ref.sequence: the same table, src, ids and counters, frame for frame.  The table handed
+    in is the ungated one (box_iou or the intersection counts of every pair): the class gate is assign_tables' own."""
+    tr = V.RefTracker(match=match, ttl=ttl, max_tracks=cap)
+    counters = np.array([0, 0, 0, 77], dtype=np.int32)
+    old = dict(boxes=np.zeros((0, 4), np.float32), classes=np.zeros(0, np.int64), ids=np.zeros(0, np.int32), ttl=np.zeros(0, np.int32))
+    old_masks = np.zeros((0,) + size, dtype=bool)
+    matched = 0
+    for f in V.sequence(9, frames=9, seed=4, size=size, with_masks=match == "mask"):
+        n, rows = len(f["boxes"]), len(old["ids"])
+        if match == "box":
+            value = np.array([[V.box_iou(old["boxes"][i], f["boxes"][j]) for j in range(n)] for i in range(rows)], dtype=np.float64).reshape(rows, n)
+        else:
+            inter = np.array([[np.count_nonzero(old_masks[i] & f["masks"][j]) for j in range(n)] for i in range(rows)], dtype=np.int64).reshape(rows, n)
+            value = V.mask_values(inter, [int(m.sum()) for m in old_masks], [int(m.sum()) for m in f["masks"]])
+        new = dict(boxes=f["boxes"], classes=f["classes"])
+        out, src, ids, counters = V.assign_tables(value, old, counters, new, n, cap, ttl, tr.threshold)
+        want_ids = tr.update(f["boxes"], f["classes"], f["masks"])
+        want = tr.arrays()
+        assert ids.tolist() == want_ids.tolist() and counters.tolist() == [len(tr.tracks), tr.next_id, tr.dropped, 77]
+        for k in ("classes", "ids", "ttl"):
+            assert out[k].tolist() == want[k].tolist(), k
+        assert np.array_equal(out["boxes"].view(np.uint32), want["boxes"].view(np.uint32))
+        assert src[:n].tolist() == list(range(n)) and all(v >= n for v in src[n:]) and sorted(set(src.tolist())) == sorted(src.tolist())
+        if match == "mask":
+            both = np.concatenate([f["masks"], old_masks]) if n + rows else old_masks
+            old_masks = both[src] if len(src) else old_masks[:0]
+            assert np.array_equal(old_masks, want["masks"])
+        matched += int(np.isin(ids, old["ids"]).sum())
+        old = out
+    assert matched > 0 and (cap > 12 or tr.dropped > 0)
+
+
 @pytest.mark.parametrize("match,size", [("box", (480, 640)), ("mask", (37, 53)), ("mask", (5, 7))])
 def test_array_form_of_the_table_equals_the_scalar_form(match, size):
     """RefTracker.iou_table (whole arrays, what the GPU tests' sequences run on) against box_iou / mask_iou pair by pair, bit for bit, on

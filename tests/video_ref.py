@@ -117,6 +117,80 @@ class RefTracker:
         return out
 
 
+def mask_values(inter, old_areas, new_areas):
+    """The mask-mode value table of cmk_vis_track_assign: inter[i][j] / (old_areas[i] + new_areas[j] - inter[i][j]) in float64 from
+    Python integers, a zero union gives 0."""
+    rows, n = len(old_areas), len(new_areas)
+    out = np.zeros((rows, n), dtype=np.float64)
+    for i in range(rows):
+        for j in range(n):
+            it = int(inter[i][j])
+            u = int(old_areas[i]) + int(new_areas[j]) - it
+            out[i, j] = 0.0 if u == 0 else float(np.float64(it) / np.float64(u))
+    return out
+
+
+def assign_tables(value, old, counters, new, n, cap, ttl, threshold):
+    """One frame of the association rule of include/cmk.h (cmk_vis_track_assign) on tables, in plain loops.  value: (rows, n) float64,
+    the iou table or mask_values(...), before the class gate; old / new: dicts of boxes (., 4) float32, classes, and for old ids and ttl,
+    `rows` and `n` rows long; counters: the four int32.  -> (out table as a dict of boxes, classes, ids, ttl with the new n_tracks rows,
+    src, track_ids, counters)."""
+    rows = len(old["classes"])
+    tracks = min(max(int(counters[0]), 0), rows)
+    next_id, dropped = int(counters[1]), int(counters[2])
+    best = [-1] * tracks
+    for i in range(tracks):
+        top, at = None, -1
+        for j in range(n):
+            v = float(value[i][j]) if int(old["classes"][i]) == int(new["classes"][j]) else 0.0
+            if v != v:
+                v = 0.0
+            if at < 0 or v > top:                                    # the first j that attains the row maximum
+                top, at = v, j
+        if at >= 0 and top > threshold:
+            best[i] = at
+    owner = [None] * n
+    for i in range(tracks):                                          # in index order: the smallest candidate i claims j
+        if best[i] >= 0 and owner[best[i]] is None:
+            owner[best[i]] = i
+    track_ids = []
+    for j in range(n):
+        if owner[j] is None:
+            track_ids.append(next_id)
+            next_id += 1
+        else:
+            track_ids.append(int(old["ids"][owner[j]]))
+    table = [(new["boxes"][j], int(new["classes"][j]), track_ids[j], int(ttl), j) for j in range(n)]
+    extras = []
+    for i in range(tracks):
+        if best[i] >= 0 and owner[best[i]] == i:
+            continue
+        left = int(old["ttl"][i]) - 1
+        if left > 0:
+            extras.append((old["boxes"][i], int(old["classes"][i]), int(old["ids"][i]), left, n + i))
+    room = cap - n
+    dropped += max(0, len(extras) - room)
+    table += extras[:room]
+    out = dict(boxes=np.array([r[0] for r in table], dtype=np.float32).reshape(-1, 4), classes=np.array([r[1] for r in table], dtype=np.int64),
+               ids=np.array([r[2] for r in table], dtype=np.int64).astype(np.int32), ttl=np.array([r[3] for r in table], dtype=np.int32))
+    src = np.array([r[4] for r in table], dtype=np.int32)
+    new_counters = np.array([len(table), next_id, dropped, int(counters[3])], dtype=np.int64).astype(np.int32)
+    return out, src, np.array(track_ids, dtype=np.int64).astype(np.int32), new_counters
+
+
+def gather_rows(src, n_tracks, old_words, old_areas, new_words, new_areas, n, cap, rows):
+    """cmk_vis_track_gather as a plain copy: {out row s: (words, area)} for s < min(n_tracks, cap, rows) whose src[s] names a new instance
+    (0 <= v < n) or an old row (n <= v < n + cap); every other row is not written."""
+    out = {}
+    for s in range(max(0, min(int(n_tracks), cap, rows))):
+        v = int(src[s])
+        if 0 <= v < n:
+            out[s] = (np.array(new_words[v]), int(new_areas[v]))
+        elif n <= v < n + cap:
+            out[s] = (np.array(old_words[v - n]), int(old_areas[v - n]))
+    return out
+
+
 def sequence(n, frames=12, seed=0, size=(480, 640), with_masks=False, pool_factor=1.5):
     """A seeded sequence of `frames` frames of about n instances: a pool of objects (boxes inside `size`, 3 classes), of which every frame
     shows a shuffled subset with jitter: mostly small (the IoU stays above the thresholds), sometimes large (it does not).  On purpose:

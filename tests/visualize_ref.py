@@ -161,6 +161,84 @@ def render(image, boxes, scores, classes, masks=None, keypoints=None, class_name
     return img
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the record of an instance (include/cmk.h, cmk_vis_prepare) and the keypoint paint on a given image
+# ---------------------------------------------------------------------------------------------------------------
+# The layout, stated once: the int32 offsets VR_* of csrc/visualize.hip (constexpr int VR_HIT .. VR_GLYPH below "record layout"), which is
+# the library's own and which include/cmk.h only sizes (cmk_vis_record_ints).
+REC_INTS = 28
+R_HIT, R_SRC, R_FLAGS, R_LEN, R_COL, R_BOX, R_PLATE, R_EDGE, R_TEXT, R_SPARE, R_GLYPH = 0, 4, 5, 6, 7, 8, 12, 16, 17, 18, 20
+MAX_LABEL = 32
+
+
+def _pack3(c):
+    return int(c[0]) | (int(c[1]) << 8) | (int(c[2]) << 16)
+
+
+def label_glyphs_of(cls, score, names, name_lens):
+    """NAME + " " + P + "%" as glyph indices, at most 32: NAME is row cls of names (its length clamped into [0, 32], a glyph byte above
+    40 is glyph 40) or, for a class outside the names, the text "C<id>"."""
+    if 0 <= cls < len(names):
+        g = [min(int(v), len(FONT_CHARS) - 1) for v in names[cls][:min(max(int(name_lens[cls]), 0), MAX_LABEL)]]
+    else:
+        g = glyph_indices("C" + str(int(cls)))
+    return (g + glyph_indices(" " + str(percent(score)) + "%"))[:MAX_LABEL]
+
+
+def records(boxes, scores, classes, order, names, name_lens, palette, h, w, font_scale, color_by_class=0, color_ids=None):
+    """The (n, 28) int32 records of cmk_vis_prepare[_ids], field by field from the rules of include/cmk.h.  names (num_names, 32) glyph
+    bytes, palette (64, 3) bytes; an order[j] outside [0, n) stands for j."""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    n, s = len(boxes), int(font_scale)
+    out = np.zeros((n, REC_INTS), dtype=np.int64)
+    for j in range(n):
+        src = int(order[j])
+        if not 0 <= src < n:
+            src = j
+        cls = int(classes[src])
+        k = int(color_ids[src]) if color_ids is not None else (cls if color_by_class else src)
+        col = [int(v) for v in palette[k % 64]]                         # Python's remainder is the non-negative one
+        glyphs = label_glyphs_of(cls, scores[src], names, name_lens)
+        nan = bool(np.isnan(boxes[src]).any())
+        bx0, by0, bx1, by1 = (0, 0, -1, -1) if nan else (_floor_clamped(v, 2 ** 20) for v in boxes[src])
+        pw, ph = (6 * len(glyphs) + 1) * s, 9 * s
+        px0, py0 = min(max(bx0, 0), max(0, w - pw)), min(max(by0, 0), max(0, h - ph))
+        r = out[j]
+        r[R_HIT:R_HIT + 4] = (0, 0, -1, -1) if nan else (min(bx0, px0), min(by0, py0), max(bx1, px0 + pw - 1), max(by1, py0 + ph - 1))
+        r[R_SRC], r[R_FLAGS], r[R_LEN] = src, 0 if nan else 1, len(glyphs)
+        r[R_COL] = _pack3(col)
+        r[R_EDGE] = _pack3([(c * 154) >> 8 for c in col])
+        r[R_TEXT] = _pack3([c + (((255 - c) * 179) >> 8) for c in col])
+        r[R_BOX:R_BOX + 4] = (bx0, by0, bx1, by1)
+        r[R_PLATE:R_PLATE + 4] = (px0, py0, pw, ph)
+        g = bytes(glyphs) + bytes(MAX_LABEL - len(glyphs))
+        r[R_GLYPH:R_GLYPH + 8] = np.frombuffer(g, dtype="<i4")
+    return out.astype(np.int32)
+
+
+def paint_keypoints(image, keypoints, recs, skeleton, line_width, threshold, keypoint_colour):
+    """cmk_vis_keypoints restated: onto a copy of `image`, per record in order, the skeleton segments of instance R_SRC in the record's
+    colour, then its visible points as discs in keypoint_colour (an int, bytes 0..2).  A skeleton index outside [0, K) draws nothing."""
+    img = np.array(image, dtype=np.uint8, copy=True)
+    kp = np.asarray(keypoints, dtype=np.float32)
+    lw = int(line_width)
+    kr = max(2, lw + 1)
+    red = (keypoint_colour & 255, (keypoint_colour >> 8) & 255, (keypoint_colour >> 16) & 255)
+    for r in np.asarray(recs).reshape(-1, REC_INTS):
+        col = (int(r[R_COL]) & 255, (int(r[R_COL]) >> 8) & 255, (int(r[R_COL]) >> 16) & 255)
+        pts = []
+        for x, y, sc in kp[int(r[R_SRC])]:
+            vis = bool(np.float32(sc) > np.float32(threshold)) and not (x != x or y != y)
+            pts.append((_floor_clamped(x, 2 ** 15), _floor_clamped(y, 2 ** 15)) if vis else None)
+        for a, b in skeleton:
+            if 0 <= a < len(pts) and 0 <= b < len(pts) and pts[a] is not None and pts[b] is not None:
+                _paint_segment(img, pts[a][0], pts[a][1], pts[b][0], pts[b][1], lw, col)
+        for p in pts:
+            if p is not None:
+                _paint_disc(img, p[0], p[1], kr, red)
+    return img
+
+
 def render_instances(image, instances, **kw):
     """`render` on an Instances whose tensors are downloaded here."""
     def host(t):
