@@ -99,7 +99,7 @@ static int setup_gn(ConvArgs& a, const cmk_conv_desc* d) {
 
 // The tile height (4 | 2) with which descriptor d runs on the pointwise GEMM kernel (conv_pw.hip), 0 if it does not: tune_wm 8 as given, or
 // the untuned default — 1x1 convs with enough pixels and output channels to fill the chip (measured 1.12-1.2x conv_igemm on every concat /
-// lateral / deconv shape of the model, tools/bench_pw.py), 256-pixel workgroups from 2 rounds on.
+// lateral / deconv shape of the model, tools/conv_probe.py time --set pw -v 1/32/4 8/32/4 8/32/2), 256-pixel workgroups from 2 rounds on.
 static int pointwise_mt(const cmk_conv_desc* d, int n) {
     const int cout32 = (d->Cout + 31) / 32;
     const long total_pix = (long)d->N * d->H * d->W;
@@ -132,7 +132,7 @@ static int gather_mt(const cmk_conv_desc* d, int n) {
     if (d->tune_wm || d->tune_sc || d->tune_wn || d->stride != 2) return 0;
     const long ctiles = cdiv(cout32, 4);
     const long wg4 = ((out_pix + 255) / 256) * ctiles;
-    return wg4 >= 1024 ? 4 : 0;          // measured (tools/bench_ga.py): stem_3 1.28x conv_igemm; the 14 -> 7 maskiou conv and P6/P7 stay on its split-K gather form
+    return wg4 >= 1024 ? 4 : 0;          // measured (tools/conv_probe.py time --set s2 -v tuned 9/32/4 9/32/2): stem_3 1.28x conv_igemm; the 14 -> 7 maskiou conv and P6/P7 stay on its split-K gather form
 }
 
 // The variant a launch of these (validated) descriptors runs: the caller's tune fields as given, or the untuned default when they are all
@@ -141,10 +141,10 @@ static int gather_mt(const cmk_conv_desc* d, int n) {
 static Variant resolve(const cmk_conv_desc* descs, int n, bool gn) {
     const cmk_conv_desc* d = &descs[0];
     if (d->tune_wm || d->tune_sc || d->tune_wn) return Variant{d->tune_wm, d->tune_sc, d->tune_wn};     // the caller measured and picked one
-    // the 2-WG/CU Winograd form wins on every 3x3 stride-1 shape measured (tools/bench_wino.py), so take it whenever the caller packed the
+    // the 2-WG/CU Winograd form wins on every 3x3 stride-1 shape measured (tools/conv_probe.py time --set v39 roi -v 1/16/4 5/16/2), so take it whenever the caller packed the
     // transformed weights; otherwise the direct-kernel cost model decides
     const bool wino = d->ksize == 3 && d->stride == 1 && d->res_mode == 0 && !d->in_relu && d->Cin >= 32 && d->splitk <= 1;
-    // F(4x4,3x3) where its 12x40 tiles are reasonably full and there are enough of them (measured on the model's maps, tools/bench_wino6.py:
+    // F(4x4,3x3) where its 12x40 tiles are reasonably full and there are enough of them (measured on the model's maps, tools/conv_probe.py time --set v39 roi -v 5/16/2 6/16/roi:
     // 1.1-1.5x the 2x2 form down to 25x40 maps, 0.4x on 14x14 RoI maps whose tiles are 20 % full)
     if (wino && d->w_wino6 && !(d->Cin & 7)) {
         double px = 0.0, covered = 0.0;

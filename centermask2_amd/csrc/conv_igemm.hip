@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256, (occ_of(WM, WN, STRIDE))) void conv_igemm_kern
                 f32x4 v = a_stage[it];
                 const bool ok = (a_ok >> it) & 1u;
                 // rare, wave-uniform options: real branches (the empty asm keeps hipcc from if-converting them into selects that
-                // every conv would execute — each VALU instruction here costs the matrix pipe ~4 cycles, tools/probe/mfma_probe2)
+                // every conv would execute — each VALU instruction here costs the matrix pipe ~4 cycles, tools/probe/mfma_probe2.hip)
                 if (has_aff) {
                     asm volatile("" ::: "memory");
                     v.x = fmaxf(v.x * in_sc.x + in_sh.x, 0.f); v.y = fmaxf(v.y * in_sc.y + in_sh.y, 0.f);

@@ -18,7 +18,7 @@ namespace cmk {
 //   per-lane register arithmetic; the two frequency halves swap partial sums through LDS once at the end.
 // Weights: what bounded the earlier LDS-DMA forms was a latency chain, not throughput — a weight piece could only be requested one
 // step ahead (two 16 KiB LDS buffers were all that fit) and an L2 round trip under load is about as long as a step, so every step
-// waited for it (tools/probe/trace_wino.py, mfma_probe3).  Here each lane loads its own U operand pieces from global memory
+// waited for it (a shader-clock trace build of those forms, removed with them; tools/probe/mfma_probe3.hip).  Here each lane loads its own U operand pieces from global memory
 // (L2-resident, shared by all workgroups) into registers TWO steps ahead (layout R = one contiguous KiB per wave load,
 // cmk_conv_desc.w_wino); the LDS that a weight buffer would take holds a second V buffer, so the input transform of chunk c+1
 // overlaps the MFMAs of chunk c with two barriers per chunk, none of which waits for memory.

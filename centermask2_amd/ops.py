@@ -296,7 +296,7 @@ PACK_WINO6 = True         # pack the F(4x4,3x3) weights too (4x the filter bank 
 ALLOW_WINOGRAD = True     # let the tuner pick the Winograd F(2x2,3x3) kernel where it is faster (fp32, differs by rounding only)
 TUNE_LOG = []             # (key, {candidate: ms}) per tuned problem
 TAIL_TILES = 0            # tests: the tile count of a variant's tail split-K (cmk.h splitk_tail_tiles); 0 = the library's plan for the device
-FORCE_VARIANT = None      # (wm, sc, wn[, splitk[, tail ways]]) for every conv launched through the wrappers below (tests, A/B tools); None = table/tuner/default
+FORCE_VARIANT = None      # (wm, sc, wn[, splitk[, tail ways]]) for every conv launched through the wrappers below (tests); None = table/tuner/default
 TUNE_ONLY = None          # callable(key) -> [(wm, sc, wn, splitk), ...]: the tuner's candidates for that problem instead of the whole menu (targeted
                           # re-tuning: tools/tune_sp3.py); TUNE_REPS timed launches per candidate, best of TUNE_ROUNDS interleaved rounds
 TUNE_REPS, TUNE_ROUNDS = 2, 1
@@ -394,15 +394,23 @@ def _out_pixels(d) -> int:
     return d.N * ho * wo
 
 
-def _set_variant(descs, n, tv, tail_tiles=None):
+def _set_variant(descs, n, tv, tail_tiles=None, dummy=None):
     """Write a variant (any spelling) into the descriptors; returns the split-K (or tail) workspace (keep it alive until the launch).
-    tail_tiles: the tile count of a tail (cmk.h splitk_tail_tiles); None = TAIL_TILES."""
+    tail_tiles: the tile count of a tail (cmk.h splitk_tail_tiles); None = TAIL_TILES.  dummy: the address that stands for every
+    workspace of descriptors that are planned and never launched (_ConvLaunch.planned); nothing is allocated."""
     wm, sc, wn, sk, tail = Variant.of(tv)
     for i in range(n):
         descs[i].tune_wm, descs[i].tune_sc, descs[i].tune_wn = wm, sc, wn
         descs[i].splitk, descs[i].splitk_ws = 0, None
         descs[i].splitk_tail, descs[i].splitk_tail_tiles = 0, 0
     ws = None
+    if dummy is not None:
+        d = descs[0]
+        if tail:
+            d.splitk_tail, d.splitk_tail_tiles, d.splitk_ws = tail, TAIL_TILES if tail_tiles is None else tail_tiles, dummy
+        if sk > 1:
+            d.splitk, d.splitk_ws = sk, dummy
+        return None
     if tail:
         d = descs[0]
         d.splitk_tail, d.splitk_tail_tiles = tail, TAIL_TILES if tail_tiles is None else tail_tiles
@@ -438,13 +446,47 @@ class _ConvLaunch:
     split-K (or tail) workspace, which lives as long as this object, and the entry they go through (cmk_conv2d_nhwc if single, else the _multi one)."""
 
     def __init__(self, xs, pcs, ys, relu=False, relu_upto=None, res=None, res_upsample=False, in_relu=False, in_affine=None, single=False):
-        self.xs, self.pcs, self.ys, self.n, self.single, self.ws = xs, pcs, ys, len(xs), single, None
+        self.xs, self.pcs, self.ys, self.n, self.single, self.ws, self.dummy = xs, pcs, ys, len(xs), single, None, None
         self.descs = (ConvDesc * self.n)()
         for i in range(self.n):
             _fill_desc(self.descs[i], xs[i], pcs[i], ys[i], relu, relu_upto, res, res_upsample, in_relu, in_affine[i] if in_affine is not None else None)
 
+    @classmethod
+    def planned(cls, shapes, cin, cout, k, stride=1, relu=False, res_mode=0, in_affine=False, single=False) -> "_ConvLaunch":
+        """The launch of problems known by their shapes [(N, H, W)] alone, for _plan and cmk_conv_resolve on a machine without a GPU: dense
+        views, every packing on offer, and one dummy aligned address for every pointer, which the library's front door never follows.
+        set() and gn_stats() work as on a real launch; run() is refused."""
+        self = cls.__new__(cls)
+        self.xs = self.pcs = self.ys = self.ws = None
+        self.n, self.single = len(shapes), single
+        self._buf = (ctypes.c_float * 64)()
+        self.dummy = ptr = (ctypes.addressof(self._buf) + 15) // 16 * 16
+        self.descs = (ConvDesc * self.n)()
+        cin_pad = (cin + 15) // 16 * 16
+        for d, (n, h, w) in zip(self.descs, shapes):
+            d.x = d.w = d.scale = d.shift = d.y = d.w_wino = d.w_wino6 = d.w_split = d.w_splith = ptr
+            d.w_splith_scale = 1.0
+            d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = n, h, w, cin_pad, cout, k, stride
+            d.x_cs, d.y_cs, d.relu_upto = cin_pad, cout, cout if relu else 0
+            d.res_mode = res_mode
+            if res_mode:
+                ho, wo = _out_hw(h, w, stride)
+                d.res, d.res_cs, d.Hr, d.Wr = ptr, cout, (ho, (ho + 1) // 2)[res_mode - 1], (wo, (wo + 1) // 2)[res_mode - 1]
+            if in_affine:
+                d.in_scale = d.in_shift = ptr
+        return self
+
     def set(self, v) -> None:
-        self.ws = _set_variant(self.descs, self.n, v)
+        self.ws = _set_variant(self.descs, self.n, v, dummy=self.dummy)
+
+    def gn_stats(self, groups: int):
+        """Ask the kernel of the variant that is set for the fused statistics of a GroupNorm over its outputs (_gn_records: the affine
+        to call after the launch, or None where that kernel writes none).  A planned launch only puts the question (gn_groups, no workspace)."""
+        if self.dummy is None:
+            return _gn_records(self.descs, self.ys, groups)
+        for i in range(self.n):
+            self.descs[i].gn_groups = groups
+        return None
 
     def choose(self, first=None, with_gn_stats=False) -> Variant:
         """Write an explicit variant into the descriptors and return it: FORCE_VARIANT, else the loaded table, else the start-up tuner, else
@@ -469,6 +511,8 @@ class _ConvLaunch:
         return v
 
     def run(self) -> int:
+        if self.dummy is not None:
+            raise _lib.CmkError("a planned conv launch has no buffers: it can be planned, not run")
         lib = _lib.load()
         return lib.cmk_conv2d_nhwc(ctypes.byref(self.descs[0]), _stream()) if self.single else lib.cmk_conv2d_nhwc_multi(self.descs, self.n, _stream())
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # build_variant.sh <name> <conv_wino6 | conv_pw source> [extra hipcc flags]  ->  centermask2_amd/ab/libcmk_<name>.so
 # (same objects as libcmk_hip.so except the object of that source (its file name starts with conv_wino6 or conv_pw): for same-session
-# A/B runs of kernel variants, tools/ab/ab_wino6.py, tools/bench_pw.py under CMK_LIB)
+# A/B runs of kernel variants: tools/conv_probe.py time ... --lib <lib.so> <lib.so>, or any tool under CMK_LIB)
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 NAME=$1; SRC=$(readlink -f "$2"); shift 2

@@ -1,7 +1,10 @@
-import sys, os, ctypes
+"""The mask head's four 3x3 convs on the RoI features of a real (synthetic-weight V-99) forward pass, layer by layer, on the direct form (2/16/4)
+and on F(2x2,3x3) (5/16/2), each against a float64 convolution of the same input: post-ReLU sparsity and trained-scale weights, which the seeded
+N(0,1) data of conv_probe.py check does not have.  python tools/diag_mask.py"""
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.nn.functional as F
-from centermask2_amd import ops, _lib, synthetic as S
+from centermask2_amd import ops, synthetic as S
 from centermask2_amd.ops import View
 from tests.helpers import build_gpu_model
 model, sd = build_gpu_model("V-99-eSE")
@@ -10,7 +13,6 @@ with torch.no_grad():
     out = model.inference_padded(x.cuda(), [(128, 192)], want=("roi_feat",))
 roi = out["roi_feat"]          # (50,14,14,256)
 print("roi", tuple(roi.shape), float(roi.abs().max()), float(roi.abs().mean()), "zeros frac", float((roi == 0).float().mean()))
-lib = _lib.load()
 xin = View(roi.contiguous())
 for k in range(1, 5):
     w = sd["roi_heads.mask_head.mask_fcn%d.weight" % k]; b = sd["roi_heads.mask_head.mask_fcn%d.bias" % k]
@@ -19,9 +21,9 @@ for k in range(1, 5):
     res = {}
     for name, tv in (("direct", (2, 16, 4)), ("wino", (5, 16, 2))):
         y = View(torch.empty((50, 14, 14, 256), device="cuda"))
-        d = (_lib.ConvDesc * 1)(); ops._fill_desc(d[0], xin, pc, y, True, None, None, False, False)
-        d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = tv
-        assert lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream()) == 0
+        launch = ops._ConvLaunch([xin], [pc], [y], relu=True, single=True)
+        launch.set(tv)
+        launch.launch()
         torch.cuda.synchronize()
         got = y.t.permute(0, 3, 1, 2).cpu()
         err = (got - ref).abs()

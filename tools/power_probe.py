@@ -1,6 +1,6 @@
 """Is a conv kernel clock/power-limited?  Runs one conv shape back to back for a few seconds while sampling rocm-smi (power, sclk).
 usage: power_probe.py H W Cin Cout wm[:wn] [seconds]     (wm 1 or 8 with :wn = a 1x1 conv with that variant forced)"""
-import sys, os, ctypes, subprocess, threading, time, re
+import sys, os, subprocess, threading, time, re
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from centermask2_amd import ops, _lib
@@ -13,9 +13,9 @@ dev = torch.device("cuda:0"); lib = _lib.load()
 taps = 9 if wm not in (1, 8) else 1
 x = View(torch.randn((8, h, w, cin), device=dev)); pc = ops.PackedConv(torch.randn((cout, cin, 3 if taps == 9 else 1, 3 if taps == 9 else 1)) * 0.05, None, None, dev)
 y = View(torch.empty((8, h, w, cout), device=dev))
-d = (_lib.ConvDesc * 1)(); ops._fill_desc(d[0], x, pc, y, True, None, None, False, False)
-if taps == 1 and wn: d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = wm, 32, wn
-if taps == 9: d[0].tune_wm, d[0].tune_sc, d[0].tune_wn = wm, 16, (1 if wm == 6 else 2)
+launch = ops._ConvLaunch([x], [pc], [y], relu=True, single=True)
+if taps == 1 and wn: launch.set((wm, 32, wn))
+if taps == 9: launch.set((wm, 16, 1 if wm == 6 else 2))
 samples = []
 stop = False
 def sampler():
@@ -28,14 +28,14 @@ def sampler():
         except Exception as e:
             samples.append((time.time(), None, None, str(e)))
         time.sleep(0.25)
-for _ in range(5): lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream())
+for _ in range(5): assert launch.run() == 0, lib.cmk_last_error()
 torch.cuda.synchronize()
 th = threading.Thread(target=sampler); th.start()
 t0 = time.time(); n = 0
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
 while time.time() - t0 < secs:
-    for _ in range(50): lib.cmk_conv2d_nhwc(ctypes.byref(d[0]), ops._stream())
+    for _ in range(50): launch.run()
     n += 50
     torch.cuda.synchronize()
 e1.record(); torch.cuda.synchronize()
