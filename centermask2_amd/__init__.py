@@ -2,7 +2,7 @@
 __version__ = "0.1.0"
 
 __all__ = ["Predictor", "load_weights", "GeneralizedRCNNWithTTA", "Visualizer", "draw_instance_predictions", "InstanceTracker",
-           "VideoVisualizer", "__version__"]
+           "VideoVisualizer", "CityscapesInstanceEvaluator", "__version__"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name in ("InstanceTracker", "VideoVisualizer"):
         from . import video
         return getattr(video, name)
+    if name == "CityscapesInstanceEvaluator":
+        from . import evaluation
+        return evaluation.CityscapesInstanceEvaluator
     raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))

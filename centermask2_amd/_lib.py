@@ -117,6 +117,7 @@ SIGNATURES = {
     "cmk_mask_intersections": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cmk_mask_boundary_bits": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cmk_mask_unpack_bits": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cmk_mask_label_counts": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cmk_vis_record_ints": (c_int, []),
     "cmk_vis_prepare": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p]),

@@ -226,3 +226,96 @@ class COCOEvaluator:
                     res["AP-" + name] = float(np.mean(pr) * 100) if pr.size else float("nan")
             out[task] = res
         return out
+
+
+class CityscapesInstanceEvaluator:
+    """Instance-level AP on Cityscapes ground truth, with the reset / process / evaluate protocol of COCOEvaluator: the counterpart of
+    the reference's centermask.evaluation.CityscapesInstanceEvaluator (evaluation/cityscapes_evaluation.py:47-130), predictions ranked
+    by `mask_scores` when present (:77).  The scoring rule is cityscapes_eval.py's restatement of cityscapesscripts'
+    evalInstanceLevelSemanticLabeling, never run beside the real scripts (see its docstring).
+
+    ground_truth: dict <city>_<seq>_<frame> -> (H,W) integer array of *_gtFine_instanceIds values; otherwise gt_dir is globbed for
+    */*_gtFine_instanceIds.png and the files are read with `loader` (default cityscapes_eval.read_label_png) when their image is
+    processed.  thing_classes[k] names model class k; a name outside the dataset's labels is refused here, one that is not an
+    evaluated class is skipped.  An input's file_name .../<city>_<seq>_<frame>_leftImg8bit.png selects its ground truth.
+
+    process() turns the label image into columns (void, other, one per ground-truth region) and keeps, per prediction, its pixel count
+    and its pixels on void and on each region of its class.  For Instances on a GPU the table comes from ops.mask_label_counts and
+    no bitmap is downloaded or written as a file; for CPU Instances from cityscapes_eval.label_counts_host, the same integers —
+    selected by where the input lies.  An image with more than 4094 regions takes the host path.  evaluate() touches no bitmap."""
+
+    def __init__(self, gt_dir=None, ground_truth=None, thing_classes=None, distributed: bool = False, loader=None):
+        import glob
+        import os
+        from . import cityscapes_eval as ce
+        self.thing_classes = list(ce.THING_CLASSES if thing_classes is None else thing_classes)
+        unknown = [n for n in self.thing_classes if n not in ce.LABEL_NAMES]
+        if unknown:
+            raise ValueError("CityscapesInstanceEvaluator: {} are not Cityscapes label names".format(unknown))
+        self._labels = [ce.CLASS_ID.get(n) for n in self.thing_classes]
+        self._loader = loader or ce.read_label_png
+        self._distributed = distributed
+        if ground_truth is not None:
+            self._gt = dict(ground_truth)
+        elif gt_dir is not None:
+            files = sorted(glob.glob(os.path.join(str(gt_dir), "*", "*_gtFine_instanceIds.png")))
+            if not files:
+                raise ValueError("CityscapesInstanceEvaluator: no */*_gtFine_instanceIds.png under {}".format(gt_dir))
+            self._gt = {ce.image_name(f): f for f in files}
+        else:
+            raise ValueError("CityscapesInstanceEvaluator: give gt_dir or ground_truth")
+        self.reset()
+
+    def reset(self):
+        self._predictions = []
+
+    def _label_image(self, name):
+        gt = self._gt[name]
+        if isinstance(gt, (str, bytes)) or hasattr(gt, "__fspath__"):
+            gt = self._loader(gt)
+        return gt
+
+    def process(self, inputs, outputs):
+        from . import cityscapes_eval as ce, ops
+        for inp, out in zip(inputs, outputs):
+            name = ce.image_name(inp["file_name"])
+            if name not in self._gt:
+                raise ValueError("CityscapesInstanceEvaluator: no ground truth for {!r} (file_name {!r})".format(name, inp["file_name"]))
+            cols, regions = ce.columns(self._label_image(name))
+            inst = out.get("instances")
+            if inst is None or len(inst) == 0:                          # an image without predictions still counts its ground truth
+                self._predictions.append(ce.image_record(name, regions, [], [], None, None))
+                continue
+            h, w = cols.shape
+            masks = inst.pred_masks
+            if masks.dim() != 3 or tuple(masks.shape[1:]) != (h, w):
+                raise ValueError("CityscapesInstanceEvaluator: pred_masks of image {!r} are {}, the ground truth is {}x{}: post-process the "
+                                 "instances to the ground-truth size".format(name, "x".join(str(int(v)) for v in masks.shape[1:]), h, w))
+            classes = inst.pred_classes.cpu().tolist()
+            bad = [c for c in classes if not 0 <= c < len(self._labels)]
+            if bad:
+                raise ValueError("CityscapesInstanceEvaluator: a prediction has class {}, thing_classes has {} names".format(bad[0], len(self._labels)))
+            conf = (inst.mask_scores if inst.has("mask_scores") else inst.scores).cpu().tolist()
+            num_cols = 2 + len(regions)
+            if masks.is_cuda and num_cols <= ce.MAX_DEVICE_COLS:
+                table, areas = (t.numpy() for t in ops.mask_label_counts(masks, cols, num_cols))
+            else:
+                table, areas = ce.label_counts_host(masks.cpu().numpy(), cols, num_cols)
+            self._predictions.append(ce.image_record(name, regions, [self._labels[c] for c in classes], conf, table, areas))
+
+    _gathered = COCOEvaluator._gathered
+
+    def evaluate(self):
+        from . import cityscapes_eval as ce
+        predictions = self._gathered()
+        if predictions is None:                                         # not the main process
+            return {}
+        records = {p["name"]: p for p in predictions}
+        missing = sorted(set(self._gt) - set(records))
+        if missing:
+            raise ValueError("CityscapesInstanceEvaluator: {} ground truths were never processed, among them {}".format(len(missing), missing[:5]))
+        res = ce.score([records[k] for k in sorted(records)])
+        out = {"AP": res["AP"] * 100, "AP50": res["AP50"] * 100}
+        for name, v in res["classes"].items():
+            out["AP-" + name] = v * 100
+        return {"segm": out}

@@ -1683,6 +1683,38 @@ def mask_unpack_bits(words: torch.Tensor, h: int, w: int) -> torch.Tensor:
     return out.bool()
 
 
+LABEL_MAX_COLS = 4096       # CMK_LABEL_MAX_COLS of include/cmk.h
+
+
+def mask_label_counts(masks: torch.Tensor, cols, num_cols: int):
+    """Bitmasks (N,h,w) bool on the GPU against one label image: cols (h,w) uint16 on the host, the column of each pixel ->
+    (table (N,num_cols), areas (N,)), int32 CPU tensors: table[n, c] = the pixels of mask n whose column is c (a column >= num_cols is
+    counted nowhere), areas[n] = the pixels of mask n.  The bitmaps stay on the device, packed to bits; what crosses the host link is
+    the label image up and N*num_cols + N integers down, in one copy each."""
+    import numpy as np
+    masks = _need_bitmasks(masks, "mask_label_counts")
+    n, h, w = (int(v) for v in masks.shape)
+    cols = np.ascontiguousarray(cols)
+    if cols.dtype != np.uint16 or cols.shape != (h, w):
+        raise _lib.CmkError("mask_label_counts: expected ({}, {}) uint16 columns on the host, got {} {}".format(h, w, cols.dtype, cols.shape))
+    c = int(num_cols)
+    if not 1 <= c <= LABEL_MAX_COLS:
+        raise _lib.CmkError("mask_label_counts: {} columns outside [1, {}]".format(c, LABEL_MAX_COLS))
+    if h < 1 or w < 1:
+        raise _lib.CmkError("mask_label_counts: empty {}x{} masks".format(h, w))
+    if n == 0:
+        return torch.zeros((0, c), dtype=torch.int32), torch.zeros((0,), dtype=torch.int32)
+    dev = masks.device
+    out = torch.empty((n * c + n,), dtype=torch.int32, device=dev)
+    words = torch.empty((n, mask_words(h, w)), dtype=torch.int64, device=dev)
+    _pack_bits_into(masks, words, out[n * c:])
+    cols_dev = torch.from_numpy(cols.view(np.int16)).to(dev)          # the one upload (torch has no uint16 arithmetic; the bits are kept)
+    check(_lib.load().cmk_mask_label_counts(words.data_ptr(), n, cols_dev.data_ptr(), h, w, c, out.data_ptr(), _stream()),
+          "cmk_mask_label_counts")
+    host = out.cpu()                                                   # the one download
+    return host[:n * c].reshape(n, c), host[n * c:]
+
+
 def mask_boundary(masks: torch.Tensor, dilation: Optional[int] = None) -> torch.Tensor:
     """(R,h,w) bool bitmasks on the GPU -> (R,h,w) bool, their boundaries: packed, eroded on the packed words and unpacked, all on the
     device.  dilation defaults to boundary_dilation(h, w)."""

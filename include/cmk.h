@@ -505,6 +505,15 @@ int cmk_mask_intersections(const uint64_t* det, int N, const uint64_t* gt, int M
 int cmk_mask_boundary_bits(const uint64_t* words, int R, int H, int W, int d, uint64_t* bwords, int32_t* bareas, void* stream);
 /* The inverse of cmk_mask_pack_bits: packed words (R, ceil(H*W/64)) -> masks (R,H,W) bytes 0/1. */
 int cmk_mask_unpack_bits(const uint64_t* words, int R, int H, int W, uint8_t* masks, void* stream);
+/* Overlap counts for Cityscapes instance evaluation (evaluation/cityscapes_evaluation.py:47-130 writes every predicted mask as a PNG for
+ * cityscapesscripts, whose hot loop compares it with the ground-truth image once per ground-truth instance; the rule is restated in
+ * DESIGN §3 "Cityscapes evaluation").  words: N packed masks as cmk_mask_pack_bits writes them.  cols: H*W row-major uint16, the column
+ * of each pixel.  table[n*C + c] = the pixels p with bit p of mask n set and cols[p] == c; a pixel whose column is >= C is counted
+ * nowhere.  Zeroes table on the stream, then accumulates with integer atomics (a C-entry histogram in LDS per workgroup, hence the cap
+ * on C).  Refused before any launch: null pointers, H or W < 1, H*W >= 2^31 - 1, N outside [0, 65535], C outside
+ * [1, CMK_LABEL_MAX_COLS].  N == 0 is CMK_OK with no launch.  Nothing is allocated or synchronised. */
+#define CMK_LABEL_MAX_COLS 4096
+int cmk_mask_label_counts(const uint64_t* words, int N, const uint16_t* cols, int H, int W, int C, int32_t* table, void* stream);
 
 /* ---- visualizer (visualizer.py:21-38 hands the post-processed Instances to detectron2's Visualizer.draw_instance_predictions, which
  * draws on the host with matplotlib; this picture is the package's own, in integer arithmetic: DESIGN §3 "Visualizer").  Images are
