@@ -13,8 +13,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ---- two fp16 pieces: x = h + m, h = fp16(x), m = fp16(x - h): 11 + 11 = 22 bits of significand, the residual x - h is exact in fp32 ----------
 // fp16's narrow exponent is handled by scaling, all powers of two (exact):
-//   activations  x' = x * 2^-4 (|x| up to 1e6 stays finite); the residual is stored as fp16((x' - h) * 2^11), so it keeps 11 bits down to
-//                |x| = 2^-21 (unscaled it would be subnormal below |x| = 0.06), and the weight piece it meets is multiplied by 2^-11 in
+//   activations  x' = x * 2^-4 (|x| up to 1e6 stays finite; measured: up to 65504 * 2^4 = 1.04e6, NaN beyond — h = Inf, the residual Inf - Inf);
+//                the residual is stored as fp16((x' - h) * 2^11), a normal fp16 down to |x| = 2^-21 (unscaled it would be subnormal below
+//                |x| = 0.06); h itself is subnormal below |x| = 2^-10, so from there on x keeps an absolute error of about 2^-31 and not 22 bits
+//                (measured on whole tensors that small: cmk.h tune_wm 11), and the weight piece the residual meets is multiplied by 2^-11 in
 //                registers (4 packed multiplies per tap and cout tile);
 //   weights      w' = w * S_w with S_w the power of two that puts max |w'| in [2^14, 2^15) (host, per conv): both pieces of every weight
 //                larger than 2^-17 of the largest are normal fp16;

@@ -129,7 +129,13 @@ typedef struct {
      * v_mfma_f32_32x32x16_f16 with every fp32 operand split into TWO fp16 pieces (22 bits of significand: h = fp16(x), m = fp16(x - h), the
      * residual is exact) and the products m*h, h*m, h*h accumulated in fp32.  The representation error is below an fp32 GEMM's own accumulation
      * error, so the result carries the error of an fp32 accumulation — NOT the bits of the fp32-MFMA kernels.  Activations are split inside the
-     * kernel (scaled by 2^-4, residual by 2^11: finite up to |x| = 1e6, 22 bits down to 2^-21); the caller packs the weights:
+     * kernel (scaled by 2^-4, residual by 2^11).  The window, as measured on an MI355X (tune_wm 11 and 12 alike; tests/conv_cases.py "f16_domain"
+     * holds the promised part): finite and at fp32-class error up to max|x| = 1.04e6 (65504 * 2^4); from 1.05e6 on every output that reads an
+     * element above that is NaN (h = Inf, the residual Inf - Inf), at 2e6 nearly all and at 1e7 all of them; never Inf.  Downwards the two pieces
+     * carry 22 bits of x only while h is a normal fp16, |x| >= 2^-10; below that an activation keeps an ABSOLUTE error of about 2^-31, which is
+     * nothing beside activations of order 1 but shows on a tensor that is small as a whole: max|x| = 2^-17 comes out 8e-5 of max|ref| off,
+     * 2^-21 1e-3, 2^-25 2e-2, 2^-30 0.5 (always finite).  A weight channel at 2^-16 of the layer's largest keeps the full accuracy.
+     * The caller packs the weights:
      * w' = w * S_w, S_w the power of two with max |w'| in [2^14, 2^15); w_splith = taps x cmk_splith_packed_halves(Cout, Cin) fp16 values,
      * [tap][Cin/16][cout_pad/32][piece h|m][lane 64][8] (lane = 32*hh + li: input channels 16*chunk + 8*hh + 0..7 of output channel 32*tile + li;
      * cout_pad = Cout rounded up to 128, zero filled); w_splith_scale = 1 / S_w.  Takes in_scale/in_shift, gn_ws (records per image:
@@ -150,6 +156,16 @@ typedef struct {
      * (splitk > 1 with tune_wn 2 is the case "every tile is tail": splitk <= Cin / 16 ways, the full-size split-K workspace.) */
     int splitk_tail; int splitk_tail_tiles;
 } cmk_conv_desc;
+/* What a conv reads, and where a non-finite input can show (every tune_wm; tests/conv_cases.py "nonfinite" and the guards of every row):
+ * a launch depends on nothing but the channels [x_co, x_co + Cin) of its N images (and [res_co, res_co + Cout) of the residual) — the other
+ * channels of the tensor, the memory before and behind it, and what the output view held may be any bit pattern, NaN included, and do not
+ * change one output bit.  An Inf or NaN at one input pixel reaches only the outputs that read it: the k x k outputs around it for the
+ * direct, gather, pointwise and split forms (at stride 2 those it lands on), the 2x2 (tune_wm 5) or 4x4 (tune_wm 6) output tiles,
+ * anchored at the image's corner, whose 4x4 or 6x6 input window holds it for the Winograd forms (Inf - Inf in the transform: the whole
+ * tile may be NaN).  Every other output of that image, every other image — the other map of a RoI pair, the other problems of a _multi
+ * launch — and their pooled sums (pool_ws) and GroupNorm records (gn_ws) keep the bits of the launch without it; wherever the exact result
+ * is non-finite the output is non-finite.  The fused ReLU is fmaxf: relu(NaN) = 0 on channels below relu_upto and behind in_relu /
+ * in_scale, as in groupnorm.hip. */
 int cmk_conv2d_nhwc(const cmk_conv_desc* d, void* stream);
 int cmk_conv_pool_rows(const cmk_conv_desc* d);
 /* Same conv applied to up to 5 inputs of different H x W in ONE launch (the FCOS towers/predictors share their weights

@@ -8,7 +8,8 @@ A case is a dict (case() below gives the defaults):
   x_view / y_view = (channel stride, channel offset) or None for a dense tensor, same_buffer (x and y are disjoint channel slices of one
   tensor), relu_upto (None = Cout), in_relu, in_affine, res_mode 0 | 1 | 2 with res_view, per_problem (every problem its own scale and shift),
   weight_sets (2: the second half of the problems runs other weights), gn_groups, pool, zero_shift (the bar of tune_wm 11 is relative to the
-  image's own magnitude, which a bias would hide), answer "accept" | "refuse".
+  image's own magnitude, which a bias would hide), regime (None, or the value feature whose data tests/conv_values.py puts into the row's
+  tensors: the rows of VALUE_FEATURES), answer "accept" | "refuse".
 
 Shapes are the smallest at which a tiling can still go wrong: two images, more than one spatial tile and ragged in both directions, a Cout
 that leaves masked columns in the last cout tile, an odd number of K chunks (Cin 48) or chunk pairs (Cin 96) where the family takes it."""
@@ -57,31 +58,44 @@ FEATURES = [
     "pool",                 # pooled sums of the eSE gate
     "odd_n",                # an odd image count (on the RoI-pair geometry: a last pair with one image)
     "n1",                   # one image
+    # value features (tests/conv_values.py has the regimes, the emulations and the bars): the family's plain problem, a dense output
+    "ints",                 # small integers: the output EQUALS float64, whatever the summation order (F(4x4): HELD_TO_BAR)
+    "pow2_channels",        # x[..., c] * 2^e, w[:, c] * 2^-e: the bits of the plain launch (the fp16-split forms: HELD_TO_BAR)
+    "cancel",               # x = 1 + 2^-9 r against zero-sum filters: the signal lives in the low bits of x
+    "sparse",               # x = relu(r), every fifth channel and the last image zero, the fused ReLU on
+    "nonfinite",            # one Inf, one NaN: every output outside the pixel's reach keeps the bits of the clean launch
+    "f16_domain",           # the edges of the fp16 window cmk.h promises: max|x| = 1e6; a weight channel 2^-16 of the largest
 ]
 
 # The support table: one letter per feature, in the order of FEATURES.  A = the family takes the feature and honours it, R = its front door
 # refuses it (a non-zero return with an error text, nothing launched), - = the cell cannot be put (N_A below says why).
-#                           x y s rp rz ir ia rs uh uw k2 k4 k8 kv kr ka tl m5 m10 gn ga pl on n1
+#                           x y s rp rz ir ia rs uh uw k2 k4 k8 kv kr ka tl m5 m10 gn ga pl on n1 in p2 ca sp nf fd
 MATRIX = {
-    "igemm 1x1":             "A A A A  A  A  A  A  A  A  A  A  A  A  A  A  R  A  R   R  R  R  A  A",
-    "igemm 3x3 stride 1":    "A A A A  A  A  A  A  A  A  A  A  A  A  A  A  R  A  R   R  R  R  A  A",
-    "igemm 3x3 stride 2":    "A A - A  A  A  A  A  A  A  A  A  A  A  A  A  R  A  R   R  R  R  A  A",
-    "gather (wm 7)":         "A A A A  A  A  R  A  R  R  A  A  A  A  A  R  R  R  R   R  R  R  A  A",
-    "pw (wm 8)":             "A A A A  A  R  R  A  A  R  A  A  A  A  A  R  R  R  R   R  R  A  A  A",
-    "pw gather (wm 9)":      "A A A A  A  R  R  A  R  R  A  A  A  A  A  R  R  R  R   R  R  R  A  A",
-    "pw split bf16 (wm 10)": "A A A A  A  R  R  R  A  R  R  R  R  R  R  R  R  R  R   R  R  A  A  A",
-    "pw split fp16 (wm 12)": "A A A A  A  R  R  R  A  R  R  R  R  R  R  R  R  R  R   R  R  A  A  A",
-    "wino4r (wm 5)":         "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  R   A  A  R  A  A",
-    "wino6 map tiles":       "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  R  A  A   A  A  R  A  A",
-    "wino6 RoI pairs":       "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  A  R  R   R  R  R  A  A",
-    "wino6p map tiles":      "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  R  A  A   A  A  R  A  A",
-    "wino6p RoI pairs":      "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  A  R  R   R  R  R  A  A",
-    "wino6s map tiles":      "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  A   A  A  R  A  A",
-    "wino6s RoI pairs":      "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  R  R   R  R  R  A  A",
-    "sp3 (sc 2)":            "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  A   A  A  R  A  A",
-    "sp3 (sc 21)":           "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  A   A  A  R  A  A",
+    "igemm 1x1":             "A A A A  A  A  A  A  A  A  A  A  A  A  A  A  R  A  R   R  R  R  A  A  A  A  A  A  A  -",
+    "igemm 3x3 stride 1":    "A A A A  A  A  A  A  A  A  A  A  A  A  A  A  R  A  R   R  R  R  A  A  A  A  A  A  A  -",
+    "igemm 3x3 stride 2":    "A A - A  A  A  A  A  A  A  A  A  A  A  A  A  R  A  R   R  R  R  A  A  A  A  A  A  A  -",
+    "gather (wm 7)":         "A A A A  A  A  R  A  R  R  A  A  A  A  A  R  R  R  R   R  R  R  A  A  A  A  A  A  A  -",
+    "pw (wm 8)":             "A A A A  A  R  R  A  A  R  A  A  A  A  A  R  R  R  R   R  R  A  A  A  A  A  A  A  A  -",
+    "pw gather (wm 9)":      "A A A A  A  R  R  A  R  R  A  A  A  A  A  R  R  R  R   R  R  R  A  A  A  A  A  A  A  -",
+    "pw split bf16 (wm 10)": "A A A A  A  R  R  R  A  R  R  R  R  R  R  R  R  R  R   R  R  A  A  A  A  A  A  A  A  -",
+    "pw split fp16 (wm 12)": "A A A A  A  R  R  R  A  R  R  R  R  R  R  R  R  R  R   R  R  A  A  A  A  A  A  A  A  A",
+    "wino4r (wm 5)":         "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  R   A  A  R  A  A  A  A  A  A  A  -",
+    "wino6 map tiles":       "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  R  A  A   A  A  R  A  A  A  A  A  A  A  -",
+    "wino6 RoI pairs":       "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  A  R  R   R  R  R  A  A  A  A  A  A  A  -",
+    "wino6p map tiles":      "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  R  A  A   A  A  R  A  A  A  A  A  A  A  -",
+    "wino6p RoI pairs":      "A A A A  A  R  A  R  R  R  A  A  A  A  R  A  A  R  R   R  R  R  A  A  A  A  A  A  A  -",
+    "wino6s map tiles":      "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  A   A  A  R  A  A  A  A  A  A  A  -",
+    "wino6s RoI pairs":      "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  R  R   R  R  R  A  A  A  A  A  A  A  -",
+    "sp3 (sc 2)":            "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  A   A  A  R  A  A  A  A  A  A  A  A",
+    "sp3 (sc 21)":           "A A A A  A  R  A  R  R  R  R  R  R  R  R  R  R  A  A   A  A  R  A  A  A  A  A  A  A  A",
 }
 N_A = {("igemm 3x3 stride 2", "same_buffer"): "a stride-2 output has another height and width than its input: the two cannot be slices of one tensor"}
+N_A.update({(f, "f16_domain"): "fp32 operands and bf16 pieces carry fp32's exponent: there is no window to leave" for f in FAMILIES if MATRIX[f].split()[-1] == "-"})
+# value cells whose exact claim cannot hold, held to the emulation's bar instead (tests/conv_values.py), with the reason
+HELD_TO_BAR = {(f, "ints"): "F(4x4) has thirds in G: U = G g G^T is rounded and the output cannot be exact" for f in FAMILIES if f.startswith("wino6")}
+HELD_TO_BAR.update({(f, "pow2_channels"): "an fp16 piece of a scaled channel can go subnormal and lose bits: e_c in [-6, 6], and the output is near the plain launch's, not equal to it"
+                    for f in ("pw split fp16 (wm 12)", "sp3 (sc 2)", "sp3 (sc 21)")})
+VALUE_FEATURES = ("ints", "pow2_channels", "cancel", "sparse", "nonfinite", "f16_domain")
 
 MULTI5 = [(2, 20, 36), (2, 9, 17), (2, 5, 3), (2, 3, 2), (2, 1, 1)]
 GN3 = [(2, 20, 36), (2, 9, 17), (2, 5, 3)]       # the levels at which the Winograd forms' records hold their 1e-4 bar (one pixel per image has no variance to speak of)
@@ -98,7 +112,7 @@ def declared(family, feature):
 def case(**kw):
     c = dict(id="", family="", feature="census", k=3, stride=1, shapes=[(2, 19, 37)], cin=48, cout=80, tv=(1, 16, 3), tail_tiles=0,
              x_view=None, y_view=None, same_buffer=False, relu_upto=None, in_relu=False, in_affine=False, res_mode=0, res_view=None,
-             per_problem=False, weight_sets=1, gn_groups=0, pool=False, zero_shift=False, answer="accept")
+             per_problem=False, weight_sets=1, gn_groups=0, pool=False, zero_shift=False, regime=None, answer="accept")
     unknown = set(kw) - set(c)
     assert not unknown, unknown
     c.update(kw)
@@ -189,6 +203,10 @@ def _feature_row(family, feature):
     elif feature == "n1":
         n, h, w = base["shapes"][0]
         c.update(shapes=[(1, h, w)])
+    elif feature in VALUE_FEATURES:
+        c.update(regime=feature, y_view=None, relu_upto=None if feature == "sparse" else 0)
+        if feature == "nonfinite":
+            c.update(pool=declared(family, "pool") == "accept")                # the pair of launches with the records on
     else:
         raise KeyError(feature)
     return case(answer=declared(family, feature), **c)
@@ -257,13 +275,26 @@ def _extra_rows():
     return rows
 
 
+def _value_rows():
+    """The cells of the value features (after every other row: a row's index seeds its tensors, and those of the older rows stay), then
+    nonfinite once more per family on a launch whose images share something."""
+    rows = [_feature_row(family, feature) for family in FAMILIES for feature in VALUE_FEATURES if declared(family, feature) is not None]
+    # nonfinite on the launches that share something between images or problems: the GroupNorm records where the family takes them (those
+    # rows are multi-problem launches already), else the five-level launch where it takes that
+    for family in FAMILIES:
+        with_records = "gn" if declared(family, "gn") == "accept" else "multi5" if declared(family, "multi5") == "accept" else None
+        if with_records:
+            rows.append(dict(_feature_row(family, with_records), feature="nonfinite", regime="nonfinite", y_view=None, relu_upto=0))
+    return rows
+
+
 def all_cases():
     rows = _census_rows()
     for family in FAMILIES:
         for feature in FEATURES:
-            if declared(family, feature) is not None:
+            if declared(family, feature) is not None and feature not in VALUE_FEATURES:
                 rows.append(_feature_row(family, feature))
-    rows += _extra_rows()
+    rows += _extra_rows() + _value_rows()
     seen = {}
     for c in rows:
         name = "{} | {} | k{}s{} {} cin{} cout{} tv{}".format(c["family"], c["feature"], c["k"], c["stride"], "+".join("{}x{}x{}".format(*s) for s in c["shapes"][:1]) +

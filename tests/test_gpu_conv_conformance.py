@@ -5,7 +5,15 @@ ops._set_variant, through conv_cases.fill_descs) and checked for: the output aga
 written outside the output view (the view lies in a NaN-filled tensor that is itself the middle images of a NaN-filled allocation with one
 guard image before and one after); input, residual, weights and epilogue vectors bit-unchanged; a second launch giving the same bits;
 cmk_conv_plan agreeing with the launch.  A refused case must return non-zero with an error text and leave the NaN-filled output and every
-workspace handed in NaN: nothing was launched before the refusal.  Inputs are finite (the kernels' ReLU maps a NaN to 0, groupnorm.hip).
+workspace handed in NaN: nothing was launched before the refusal.  The values a row reads are finite (the kernels' ReLU maps a NaN to 0,
+groupnorm.hip), but nothing around them is: x and the residual lie between NaN guard images like the output, the channels beside their
+views are NaN (same_buffer: the channels of neither x nor y), so a finite output means that none of it was read into a product; and the
+second launch runs after all of that was refilled with the byte 0xC3 and must give the same bits.
+
+Value rows (conv_cases.VALUE_FEATURES; regimes, emulations and bars in tests/conv_values.py): ints and pow2_channels are compared with
+torch.equal / same_bits wherever the table claims exactness, the all-zero image of sparse too; cancel, sparse, f16_domain and the cells of
+conv_cases.HELD_TO_BAR at 4x the CPU emulation's own distance from float64 on the row's tensors; nonfinite by the bits of its clean launch
+outside the poisoned pixel's reach, in every other image and problem and in their pooled sums and GroupNorm {scale, shift}.
 
 Bars (none is new): the fp32 and Winograd families max abs err <= min(1e-3, 2e-4 * max(1, max|ref|)) (test_gpu_backbone_ops._close); the
 split GEMM forms tune_wm 10 / 12 2e-5 absolute; the direct split form tune_wm 11 1e-5 * max|ref| per image with a zero shift; GroupNorm
@@ -16,7 +24,31 @@ max|ref|)) (test_conv_pointwise_pooled_sums_and_ese_gate).
 Observed on an MI355X (the run's error report has them per family): relative to max(1, max|ref|) igemm 1x1 4.2e-7, 3x3 stride 1 1.2e-6,
 stride 2 9.2e-7, gather 9.0e-7, pw 4.5e-7, pw gather 1.3e-6, wino4r 3.5e-7, the six F(4x4) forms 5.5e-6 .. 7.8e-6; tune_wm 10 7.8e-6 and
 tune_wm 12 4.5e-6 absolute; tune_wm 11 7.5e-7 of the image's magnitude; GroupNorm scale / shift below 5.4e-7; pooled means below 1.1e-7.
-Census rows write a dense output between the guard images, feature rows a channel slice of a wider tensor."""
+Census rows write a dense output between the guard images, feature rows a channel slice of a wider tensor.
+
+Value rows observed on an MI355X (the run prints kernel, emulation and bar per row; cancel and f16_domain relative to max|ref|, the others
+to max(1, max|ref|)); every exact cell was exact, the 16-bit-MFMA families (tune_wm 10, 11, 12) on ints included, and every nonfinite row
+kept the clean launch's bits outside the reach:
+  family               ints      pow2      cancel    sparse    f16 a     f16 b
+  igemm 1x1            exact     bits      5.4e-7    1.2e-7
+  igemm 3x3 stride 1   exact     bits      7.8e-7    5.0e-7
+  igemm 3x3 stride 2   exact     bits      5.8e-7    5.0e-7
+  gather (wm 7)        exact     bits      8.4e-7    5.6e-7
+  pw (wm 8)            exact     bits      8.3e-7    2.5e-7
+  pw gather (wm 9)     exact     bits      6.0e-7    7.1e-7
+  pw split bf16 (10)   exact     bits      4.1e-7    2.6e-7
+  pw split fp16 (12)   exact     2.7e-7    2.9e-6    3.1e-7    1.9e-7    2.1e-7
+  wino4r (wm 5)        exact     bits      2.2e-6    2.1e-7
+  wino6 map tiles      3.4e-6    bits      2.9e-6    3.2e-6
+  wino6 RoI pairs      4.1e-6    bits      3.0e-6    4.1e-6
+  wino6p map tiles     4.6e-6    bits      2.5e-6    3.4e-6
+  wino6p RoI pairs     3.3e-6    bits      3.3e-6    3.6e-6
+  wino6s map tiles     5.6e-6    bits      2.7e-6    3.9e-6
+  wino6s RoI pairs     5.1e-6    bits      2.6e-6    2.3e-6
+  sp3 (sc 2)           exact     5.6e-7    5.0e-5    3.9e-7    3.8e-7    3.7e-7
+  sp3 (sc 21)          exact     4.1e-7    4.1e-5    4.4e-7    4.2e-7    4.0e-7
+The emulations' own distances on the same rows are 0.6x to 3.5x these (the bars 4x that): cancel 3.9e-7 .. 5.8e-7 for the direct forms,
+1.8e-6 F(2x2), 3.7e-6 .. 5.5e-6 F(4x4), 4.4e-7 tune_wm 10, 2.6e-6 tune_wm 12, 4.2e-5 tune_wm 11 (a zero-shift signal of 1.6e-2)."""
 import pytest
 import torch
 
@@ -24,6 +56,8 @@ from centermask2_amd import _lib, ops
 from centermask2_amd.ops import View
 from tests import conformance as C
 from tests import conv_cases as cc
+from tests import conv_values as cv
+from tests import helpers
 from tests.helpers import close, close_abs, relaunch
 
 pytestmark = pytest.mark.gpu
@@ -32,41 +66,65 @@ NAN = float("nan")
 PACKINGS = ("w", "w_wino", "w_wino6", "w_split", "w_splith", "scale", "shift")
 
 
+def _guarded(data, co, ch, dev):
+    """The channels [co, co + ch) of `data` (N, H, W, CS) as the images 1..N of a NaN-filled allocation of N + 2 images: guard images
+    before and after, and NaN in every channel beside the slice."""
+    n = data.shape[0]
+    alloc = torch.full((n + 2,) + tuple(data.shape[1:]), NAN, device=dev)
+    alloc[1:n + 1, :, :, co:co + ch] = data[..., co:co + ch].to(dev)
+    return alloc
+
+
+def _refill(alloc, n, co, ch, byte=0xC3):
+    """Every guard image and every channel outside [co, co + ch) of a _guarded allocation gets another (finite) byte pattern."""
+    kept = alloc[1:n + 1, :, :, co:co + ch].clone()
+    alloc.view(torch.uint8).fill_(byte)
+    alloc[1:n + 1, :, :, co:co + ch] = kept
+
+
 def _device_buffers(c, t, dev):
-    """The tensors of a case on the device.  y: the images 1..N of a NaN-filled allocation of N + 2 (guard images); same_buffer: x and y in
-    that one allocation, every channel outside the output view finite."""
+    """The tensors of a case on the device.  x, y and the residual are each the images 1..N of a NaN-filled allocation of N + 2 (guard
+    images) and NaN in every channel outside their view; same_buffer: x and y in that one allocation, NaN in the channels of neither."""
     (x_cs, x_co), (y_cs, y_co) = cc.views_of(c)
-    b = {"xa": [], "ya": [], "xv": [], "yv": [], "pcs": [], "res": [], "aff": []}
+    b = {"xa": [], "ya": [], "xv": [], "yv": [], "pcs": [], "res": [], "ra": [], "aff": []}
     base = [ops.PackedConv(w, None, None, dev, stride=c["stride"]) for w in t["w"]]
     for i, (n, h, w) in enumerate(c["shapes"]):
         ho, wo = cc.out_hw(c, h, w)
+        xa = _guarded(t["x"][i], x_co, c["cin"], dev)
         if c["same_buffer"]:
-            alloc = torch.full((n + 2, h, w, x_cs), NAN, device=dev)
-            alloc[1:n + 1] = t["x"][i].to(dev)
-            alloc[1:n + 1, :, :, y_co:y_co + c["cout"]] = NAN
-            xa = ya = alloc
-            xv, yv = View(alloc[1:n + 1], x_co, c["cin"]), View(alloc[1:n + 1], y_co, c["cout"])
+            ya = xa
         else:
-            xa = t["x"][i].to(dev)
             ya = torch.full((n + 2, ho, wo, y_cs), NAN, device=dev)
-            xv, yv = View(xa, x_co, c["cin"]), View(ya[1:n + 1], y_co, c["cout"])
+        xv, yv = View(xa[1:n + 1], x_co, c["cin"]), View(ya[1:n + 1], y_co, c["cout"])
         pc = ops.PackedConv.__new__(ops.PackedConv)
         pc.__dict__.update(base[cc.weight_set(c, i)].__dict__)
         pc.scale, pc.shift = t["scale"][i].to(dev), t["shift"][i].to(dev)
         b["xa"].append(xa); b["ya"].append(ya); b["xv"].append(xv); b["yv"].append(yv); b["pcs"].append(pc)
-        b["res"].append(t["res"][i].to(dev) if c["res_mode"] else None)
+        ra = _guarded(t["res"][i], c["res_view"][1] if c["res_view"] else 0, c["cout"], dev) if c["res_mode"] else None
+        b["ra"].append(ra)
+        b["res"].append(ra[1:ra.shape[0] - 1] if ra is not None else None)
         b["aff"].append(tuple(v.to(dev) for v in t["aff"][i]) if c["in_affine"] else None)
     return b
 
 
+def _refill_inputs(c, b):
+    """The surroundings of every input (guard images, channels outside the views) refilled with the byte 0xC3: what a launch read of them
+    shows as other output bits."""
+    (_, x_co), _ = cc.views_of(c)
+    for i, (n, _, _) in enumerate(c["shapes"]):
+        _refill(b["xa"][i], n, x_co, c["cin"])       # same_buffer: the output view with it; the caller fills that with NaN again
+        if b["ra"][i] is not None:
+            _refill(b["ra"][i], n, c["res_view"][1] if c["res_view"] else 0, c["cout"])
+
+
 def _read_only(c, b):
-    """Everything a launch may only read, by name."""
+    """Everything a launch may only read, by name (x and the residual with their guards and outside channels)."""
     ro = {}
     for i in range(len(c["shapes"])):
         if not c["same_buffer"]:
             ro["x{}".format(i)] = b["xa"][i]
-        if b["res"][i] is not None:
-            ro["res{}".format(i)] = b["res"][i]
+        if b["ra"][i] is not None:
+            ro["res{}".format(i)] = b["ra"][i]
         if b["aff"][i] is not None:
             ro["in_scale{}".format(i)], ro["in_shift{}".format(i)] = b["aff"][i]
         for name in PACKINGS:
@@ -98,7 +156,8 @@ def _check_output(c, b, ref, what):
     for i, (n, _, _) in enumerate(c["shapes"]):
         got = b["yv"][i].t[..., y_co:y_co + c["cout"]].double().cpu()
         want = ref["y"][i]
-        assert got.shape == want.shape and bool(torch.isfinite(got).all()), (c["id"], i, "the output view is not written everywhere")
+        assert got.shape == want.shape and bool(torch.isfinite(got).all()), (c["id"], i, "the output view is not finite everywhere: {} of {} values".format(
+            int((~torch.isfinite(got)).sum()), got.numel()))
         diff = got - want
         if wm in (10, 12):
             close_abs(diff, torch.zeros_like(diff), 2e-5, what)
@@ -128,18 +187,23 @@ def _check_outside(c, b, before):
             assert _all_nan(left) and _all_nan(right), (c["id"], i, "written outside the output view")
 
 
+def _gn_affine(c, keep, t, dev):
+    """[(scale, shift)] per problem from the GroupNorm records of the launch."""
+    assert keep["affine"] is not None, (c["id"], "the kernel is declared to write GroupNorm records and the plan offers none")
+    n = len(c["shapes"])
+    half = n // 2 if c["weight_sets"] == 2 else n
+    got = []
+    for s in range(c["weight_sets"]):
+        gamma, beta = (v.to(dev) for v in t["gn"][s])
+        got += keep["affine"](s * half, (s + 1) * half, gamma, beta, 1e-5)
+    torch.cuda.synchronize()
+    return got
+
+
 def _check_records(c, b, keep, ref, t, dev, what):
     wm = c["tv"][0]
     if c["gn_groups"]:
-        assert keep["affine"] is not None, (c["id"], "the kernel is declared to write GroupNorm records and the plan offers none")
-        n = len(c["shapes"])
-        half = n // 2 if c["weight_sets"] == 2 else n
-        got = []
-        for s in range(c["weight_sets"]):
-            gamma, beta = (v.to(dev) for v in t["gn"][s])
-            got += keep["affine"](s * half, (s + 1) * half, gamma, beta, 1e-5)
-        torch.cuda.synchronize()
-        for (sc, sh), (ref_sc, ref_sh) in zip(got, ref["gn"]):
+        for (sc, sh), (ref_sc, ref_sh) in zip(_gn_affine(c, keep, t, dev), ref["gn"]):
             d_sc, d_sh = sc.double().cpu() - ref_sc, sh.double().cpu() - ref_sh
             if wm == 11:
                 close_abs(d_sc / float(ref_sc.abs().max()), torch.zeros_like(d_sc), 2e-3, what + " GroupNorm scale")
@@ -161,8 +225,11 @@ def _check_records(c, b, keep, ref, t, dev, what):
         _fp32_bar(sums[:n] / (h * w) - want, want, 1e-5, what + " pooled means")
 
 
-def _run_case(c, seed, dev, lib, what, skipped):
-    t = cc.host_tensors(c, seed)
+def _one(c, t, dev, lib, skipped, again=True):
+    """One launch of a case on the tensors t, with everything that does not depend on the values: plan and launch agree, a refusal touches
+    nothing, an accepted launch writes nothing outside its output view and changes no input, and (again) a second launch gives the same
+    bits after every guard image and outside channel of the inputs was refilled with 0xC3.  Returns "skipped" | "refused" | what the
+    launch left: {"b", "keep", "y": [output view per problem, host], "pool", "gn": [(scale, shift) per problem] of a value row}."""
     b = _device_buffers(c, t, dev)
     descs, keep = cc.fill_descs(c, _lib, bufs=b, ops=ops)
     n = len(descs)
@@ -187,27 +254,125 @@ def _run_case(c, seed, dev, lib, what, skipped):
             assert C.same_bits(v, before[k]), (c["id"], k, "changed by a refused launch")
         return "refused"
     assert rc == 0, (c["id"], "declared accept, refused", err)
-    ref = cc.reference(c, t)
-    _check_output(c, b, ref, what)
     _check_outside(c, b, before)
-    _check_records(c, b, keep, ref, t, dev, what)
     for k, v in ro.items():
         assert C.same_bits(v, before[k]), (c["id"], k, "an input of the launch changed")
-    # determinism: the same launch into a NaN output again
     (_, _), (_, y_co) = cc.views_of(c)
     first = [b["yv"][i].t[..., y_co:y_co + c["cout"]].clone() for i in range(n)]
     first_pool = keep["pool"].clone() if keep["pool"] is not None else None
-    for i in range(n):
-        b["yv"][i].t[..., y_co:y_co + c["cout"]] = NAN
-    for ws in (keep["ws"], keep["pool"]):
-        if ws is not None:
-            ws.fill_(NAN)
-    rc2, err2 = _launch(lib, descs)
-    assert rc2 == 0, (c["id"], err2)
-    for i in range(n):
-        assert C.same_bits(b["yv"][i].t[..., y_co:y_co + c["cout"]].contiguous(), first[i].contiguous()), (c["id"], i, "a second launch gave other bits")
-    if first_pool is not None:
-        assert C.same_bits(keep["pool"], first_pool), (c["id"], "a second launch gave other pooled sums")
+    out = {"b": b, "keep": keep, "y": [f.cpu() for f in first], "pool": None if first_pool is None else first_pool.cpu(), "gn": None}
+    if c["regime"] and c["gn_groups"]:
+        out["gn"] = [(sc.cpu(), sh.cpu()) for sc, sh in _gn_affine(c, keep, t, dev)]
+    if again:                                     # determinism, and nothing read of the inputs' surroundings: the same launch into a NaN output again
+        _refill_inputs(c, b)
+        for i in range(n):
+            b["yv"][i].t[..., y_co:y_co + c["cout"]] = NAN
+        for ws in (keep["ws"], keep["pool"]):
+            if ws is not None:
+                ws.fill_(NAN)
+        rc2, err2 = _launch(lib, descs)
+        assert rc2 == 0, (c["id"], err2)
+        for i in range(n):
+            assert C.same_bits(b["yv"][i].t[..., y_co:y_co + c["cout"]].contiguous(), first[i].contiguous()), \
+                (c["id"], i, "a second launch, with 0xC3 around its inputs, gave other bits")
+        if first_pool is not None:
+            assert C.same_bits(keep["pool"], first_pool), (c["id"], "a second launch gave other pooled sums")
+    return out
+
+
+def _held_to_bar(c, t, y, what, label):
+    """The outputs y of a value row's launch against float64 at the row's bar: 4x the emulation's own distance on these tensors."""
+    ref = cc.reference(c, t)
+    bar, own = cv.bar(c, t, ref)
+    norm = cv.norm_of(c, torch.cat([r.reshape(-1) for r in ref["y"]]))
+    err = 0.0
+    for i, (got, want) in enumerate(zip(y, ref["y"])):
+        assert got.shape == want.shape and bool(torch.isfinite(got).all()), (c["id"], label, i, "{} outputs are not finite".format(int((~torch.isfinite(got)).sum())))
+        err = max(err, float((got.double() - want).abs().max()))
+    print("{} [{}]: {:.3e} (emulation {:.3e}, bar {:.3e}) of {:.3e}".format(c["id"], label, err / norm, own / norm, bar / norm, norm))
+    helpers.OBSERVED["{} {} {} (of the row's norm)".format(what, c["feature"], label)] = err / norm
+    assert err <= bar, "{} [{}]: max abs err {:.3e} > {:.3e}, 4x the emulation's {:.3e}".format(c["id"], label, err, bar, own)
+
+
+def _records_by_image(c, out, p, j):
+    """(the records of a launch that belong to the image j of problem p, all the others), each as a list of tensors."""
+    mine, others = [], []
+    if out["pool"] is not None:
+        n, h, w = c["shapes"][0]
+        rows = out["keep"]["rows"]
+        for g in range(out["pool"].shape[0] // 2):           # record 2g: the image of block g's first pixel; 2g + 1: the next image
+            img = (g * rows) // (h * w)
+            for k, im in ((2 * g, img), (2 * g + 1, img + 1)):
+                (mine if (0, im) == (p, j) else others).append(out["pool"][k])
+    for i, pair in enumerate(out["gn"] or ()):
+        for v in pair:
+            for im in range(v.shape[0]):
+                (mine if (i, im) == (p, j) else others).append(v[im])
+    return mine, others
+
+
+def _check_values(c, sets, outs, what):
+    r = c["regime"]
+    finite = lambda o: all(bool(torch.isfinite(y).all()) for y in o["y"])
+    if r == "ints" and cv.exact_ints(c):
+        ref = cc.reference(c, sets["row"])
+        for i, (got, want) in enumerate(zip(outs["row"]["y"], ref["y"])):
+            assert torch.equal(got.double(), want), "{}: integers are not exact, max abs err {:.3e}".format(c["id"], float((got.double() - want).abs().max()))
+        print("{} [row]: equal to float64".format(c["id"]))
+    elif r == "pow2_channels" and cv.exact_pow2(c):
+        assert finite(outs["row"])
+        for i, (got, want) in enumerate(zip(outs["row"]["y"], outs["plain"]["y"])):
+            assert C.same_bits(got, want), "{}: per-channel powers of two changed the output, by {:.3e}".format(c["id"], float((got.double() - want.double()).abs().max()))
+        print("{} [row]: the bits of the plain launch".format(c["id"]))
+    elif r in ("ints", "pow2_channels", "cancel", "sparse"):
+        _held_to_bar(c, sets["row"], outs["row"]["y"], what, "row")
+        if r == "sparse":
+            want = sets["row"]["shift"][-1].relu()
+            got = outs["row"]["y"][-1][-1]
+            assert torch.equal(got, want.expand_as(got)), (c["id"], "the all-zero image is not relu(shift)", float((got - want).abs().max()))
+    elif r == "f16_domain":
+        for label in ("a", "b"):
+            _held_to_bar(c, sets[label], outs[label]["y"], what, label)
+    elif r == "nonfinite":
+        clean = outs["clean"]
+        assert finite(clean) and (clean["pool"] is None or bool(torch.isfinite(clean["pool"]).all()))
+        for label in ("inf", "nan"):
+            p, j, py, px, _ = cv.poison_site(c, label)
+            got, ref = outs[label], cc.reference(c, sets[label])
+            for i, (n, h, w) in enumerate(c["shapes"]):
+                for img in range(n):
+                    g, cl = got["y"][i][img], clean["y"][i][img]
+                    if (i, img) != (p, j):
+                        assert C.same_bits(g, cl), (c["id"], label, "problem {} image {} changed with the {} in problem {} image {}".format(i, img, label, p, j))
+                        continue
+                    inside = cv.reach(c, h, w, py, px)
+                    assert C.same_bits(g[~inside], cl[~inside]), (c["id"], label, "{} outputs outside the pixel's reach changed".format(
+                        int((C.bits(g) != C.bits(cl))[~inside].sum())))
+                    bad = ~torch.isfinite(ref["y"][i][img])
+                    assert bool(bad.any()) and bool((~torch.isfinite(g))[bad].all()), (c["id"], label, "finite where float64 is not: {} of {}".format(
+                        int(torch.isfinite(g)[bad].sum()), int(bad.sum())))
+            mine, others = _records_by_image(c, got, p, j)
+            for a, b_ in zip(others, _records_by_image(c, clean, p, j)[1]):
+                assert C.same_bits(a, b_), (c["id"], label, "a record of another image changed")
+            assert not mine or not all(bool(torch.isfinite(v).all()) for v in mine), (c["id"], label, "the records of the poisoned image are finite")
+        print("{}: outside the reach of the Inf and of the NaN, the bits of the clean launch ({} records)".format(c["id"], len(_records_by_image(c, clean, 0, 0)[1]) + 0))
+    else:
+        raise KeyError(r)
+
+
+def _run_case(c, seed, dev, lib, what, skipped):
+    sets = cv.launch_sets(c, seed) if c["regime"] else {"row": cc.host_tensors(c, seed)}
+    outs = {}
+    for label, t in sets.items():
+        outs[label] = _one(c, t, dev, lib, skipped, again=not outs)
+        if not isinstance(outs[label], dict):
+            return outs[label]
+    if c["regime"]:
+        _check_values(c, sets, outs, what)
+    else:
+        ref = cc.reference(c, sets["row"])
+        _check_output(c, outs["row"]["b"], ref, what)
+        _check_records(c, outs["row"]["b"], outs["row"]["keep"], ref, sets["row"], dev, what)
     return "launched"
 
 

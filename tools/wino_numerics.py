@@ -32,19 +32,20 @@ AT4 = torch.tensor([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0]
 MATS = {2: (BT2, G2, AT2), 4: (BT4, G4, AT4)}
 
 
-def wino_conv(x, w, bias, mh, mw):
-    """F(mh x mw, 3x3), pad 1, fp32 arithmetic."""
+def wino_conv(x, w, bias, mh, mw, mats=None, contract=None):
+    """F(mh x mw, 3x3), pad 1, fp32 arithmetic.  mats: other matrices than MATS (the mutants of tests/test_cpu_conv_values.py); contract(u, v):
+    the per-frequency channel contraction (a, b, O, C) x (a, b, N, C, P) -> (a, b, N, O, P) when it is to follow another order than torch's."""
     n, c, h, wd = x.shape
     o = w.shape[0]
-    bth, gh, ath = MATS[mh]
-    btw, gw, atw = MATS[mw]
+    bth, gh, ath = (mats or MATS)[mh]
+    btw, gw, atw = (mats or MATS)[mw]
     th, tw = -(-h // mh), -(-wd // mw)
     xp = F.pad(x, (1, tw * mw - wd + 1, 1, th * mh - h + 1))
     u = torch.einsum("ik,ockl,jl->ijoc", gh, w.double(), gw).float()                        # (a, b, O, C), rounded once
     t = xp.unfold(2, mh + 2, mh).unfold(3, mw + 2, mw)                                      # (N, C, th, tw, a, b)
     v = torch.einsum("ia,nctsab,jb->ijncts", bth.float(), t, btw.float())                   # fp32 transform
     v = v.reshape(mh + 2, mw + 2, n, c, th * tw)
-    m = torch.einsum("ijoc,ijncp->ijnop", u, v)                                            # fp32 contraction over channels
+    m = contract(u, v) if contract else torch.einsum("ijoc,ijncp->ijnop", u, v)            # fp32 contraction over channels
     y = torch.einsum("ia,abnop,jb->nopij", ath.float(), m, atw.float())                     # (N, O, P, mh, mw)
     y = y.reshape(n, o, th, tw, mh, mw).permute(0, 1, 2, 4, 3, 5).reshape(n, o, th * mh, tw * mw)[:, :, :h, :wd]
     if bias is not None:
