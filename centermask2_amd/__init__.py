@@ -1,7 +1,7 @@
 """centermask2_amd — MI355X-native CenterMask2 inference hot path (VoVNetV2-FPN, FCOS, CenterROIHeads)."""
 __version__ = "0.1.0"
 
-__all__ = ["Predictor", "load_weights", "GeneralizedRCNNWithTTA", "Visualizer", "draw_instance_predictions", "InstanceTracker",
+__all__ = ["Predictor", "load_weights", "GeneralizedRCNNWithTTA", "SlicedInference", "Visualizer", "draw_instance_predictions", "InstanceTracker",
            "VideoVisualizer", "CityscapesInstanceEvaluator", "__version__"]
 
 
@@ -13,6 +13,9 @@ def __getattr__(name):
     if name == "GeneralizedRCNNWithTTA":
         from .modeling import test_time_augmentation
         return test_time_augmentation.GeneralizedRCNNWithTTA
+    if name == "SlicedInference":
+        from .modeling import sliced_inference
+        return sliced_inference.SlicedInference
     if name in ("Visualizer", "draw_instance_predictions"):
         from . import visualize
         return getattr(visualize, name)

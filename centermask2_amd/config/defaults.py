@@ -49,7 +49,11 @@ _TABLE = dict(
     DATASETS=dict(TRAIN=(), TEST=()),
     DATALOADER=dict(NUM_WORKERS=4),
     TEST=dict(DETECTIONS_PER_IMAGE=100, KEYPOINT_OKS_SIGMAS=[],
-              AUG=dict(ENABLED=False, MIN_SIZES=(400, 500, 600, 700, 800, 900, 1000, 1100, 1200), MAX_SIZE=4000, FLIP=True)),
+              AUG=dict(ENABLED=False, MIN_SIZES=(400, 500, 600, 700, 800, 900, 1000, 1100, 1200), MAX_SIZE=4000, FLIP=True),
+              # sliced inference (modeling/sliced_inference.py): TILE is (h, w) in image pixels, OVERLAP the share of a tile its neighbour
+              # repeats, FULL_IMAGE adds the whole image as one more pass, MATCH_METRIC "IOS" | "IOU" at MATCH_THRESH merges, BATCH tiles per
+              # model call.  Not a detectron2 key: the reference has no counterpart.
+              SLICE=dict(ENABLED=False, TILE=(512, 512), OVERLAP=0.2, FULL_IMAGE=True, MATCH_METRIC="IOS", MATCH_THRESH=0.5, BATCH=8)),
     SOLVER=dict(CHECKPOINT_PERIOD=5000, IMS_PER_BATCH=16, BASE_LR=0.001, STEPS=(30000,), MAX_ITER=40000),
 )
 

@@ -150,18 +150,20 @@ constexpr int NT = 1024;
 constexpr int NW = NT / 64;
 constexpr int MAXK = 1024;      // POST_NMS_TOPK_TEST the keep list (LDS) is sized for
 
+// metric 0: IoU.  metric 1: intersection over the smaller box (cmk_nms_topk_metric); a zero smaller area gives 0 / 0 = NaN, which is not
+// > thr and suppresses nothing.  The metric is uniform over the launch; with metric 0 the arithmetic is what it was before the metric existed.
 __device__ inline float iou_f(float ax1, float ay1, float ax2, float ay2, float aarea, float bx1, float by1, float bx2, float by2,
-                              float barea) {
+                              float barea, int metric) {
     float xx1 = fmaxf(ax1, bx1), yy1 = fmaxf(ay1, by1);
     float xx2 = fminf(ax2, bx2), yy2 = fminf(ay2, by2);
     float w = fmaxf(0.0f, xx2 - xx1), h = fmaxf(0.0f, yy2 - yy1);
     float inter = w * h;
-    return inter / (aarea + barea - inter);
+    return inter / (metric ? fminf(aarea, barea) : (aarea + barea - inter));
 }
 
 __global__ __launch_bounds__(NT) void nms_topk_kernel(const float* __restrict__ cand_box, const float* __restrict__ cand_score,
                                                      const int32_t* __restrict__ cand_cls, const float* __restrict__ cand_loc,
-                                                     const int32_t* __restrict__ counts, int cap, float thr, int topk,
+                                                     const int32_t* __restrict__ counts, int cap, float thr, int metric, int topk,
                                                      float* __restrict__ out_box, float* __restrict__ out_score,
                                                      int64_t* __restrict__ out_cls, float* __restrict__ out_loc,
                                                      int32_t* __restrict__ out_idx, int32_t* __restrict__ out_count,
@@ -342,7 +344,7 @@ __global__ __launch_bounds__(NT) void nms_topk_kernel(const float* __restrict__ 
                 area = (x2 - x1) * (y2 - y1);
                 for (int k = 0; k < nkept; ++k) {
                     if (per_class && kcls[k] != mycls) continue;
-                    if (iou_f(kx1[k], ky1[k], kx2[k], ky2[k], karea[k], x1, y1, x2, y2, area) > thr) { alive = false; break; }
+                    if (iou_f(kx1[k], ky1[k], kx2[k], ky2[k], karea[k], x1, y1, x2, y2, area, metric) > thr) { alive = false; break; }
                 }
             }
             for (int t = 0; t < 64 && nkept < topk; ++t) {
@@ -366,7 +368,7 @@ __global__ __launch_bounds__(NT) void nms_topk_kernel(const float* __restrict__ 
                 }
                 ++nkept;
                 if (lane > t && alive && (!per_class || tcls == mycls) &&
-                    iou_f(tx1, ty1, tx2, ty2, tarea, x1, y1, x2, y2, area) > thr)
+                    iou_f(tx1, ty1, tx2, ty2, tarea, x1, y1, x2, y2, area, metric) > thr)
                     alive = false;
                 if (lane == t) alive = false;
             }
@@ -446,14 +448,22 @@ extern "C" int cmk_fcos_select(const cmk_fcos_level* levels, int num_levels, int
     return check_launch("sel_write");
 }
 
-extern "C" int cmk_nms_topk(const float* cand_box, const float* cand_score, const int32_t* cand_cls, const float* cand_loc,
-                            const int32_t* counts, int N, int cap, float iou_thr, int topk, float* out_box, float* out_score,
-                            int64_t* out_cls, float* out_loc, int32_t* out_idx, int32_t* out_count, uint32_t* sort_ws, void* stream) {
+extern "C" int cmk_nms_topk_metric(const float* cand_box, const float* cand_score, const int32_t* cand_cls, const float* cand_loc,
+                                   const int32_t* counts, int N, int cap, float thr, int metric, int topk, float* out_box, float* out_score,
+                                   int64_t* out_cls, float* out_loc, int32_t* out_idx, int32_t* out_count, uint32_t* sort_ws, void* stream) {
     if (!cand_box || !cand_score || !cand_cls || !cand_loc || !counts || !out_box || !out_score || !out_cls || !out_loc || !out_idx ||
         !out_count || !sort_ws)
         return fail(CMK_EINVAL, "nms_topk: null pointer%s", "");
     if (N < 1 || cap < 1 || topk < 1 || topk > MAXK) return fail(CMK_EINVAL, "nms_topk: need 1 <= topk <= %s%ld", "", (long)MAXK);
+    if (metric != 0 && metric != 1) return fail(CMK_EINVAL, "nms_topk: metric must be 0 (IoU) or 1 (IoS)%s, got %ld", "", (long)metric);
     hipLaunchKernelGGL(nms_topk_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, cand_box, cand_score, cand_cls, cand_loc, counts, cap,
-                       iou_thr, topk, out_box, out_score, out_cls, out_loc, out_idx, out_count, sort_ws);
+                       thr, metric, topk, out_box, out_score, out_cls, out_loc, out_idx, out_count, sort_ws);
     return check_launch("nms_topk");
+}
+
+extern "C" int cmk_nms_topk(const float* cand_box, const float* cand_score, const int32_t* cand_cls, const float* cand_loc,
+                            const int32_t* counts, int N, int cap, float iou_thr, int topk, float* out_box, float* out_score,
+                            int64_t* out_cls, float* out_loc, int32_t* out_idx, int32_t* out_count, uint32_t* sort_ws, void* stream) {
+    return cmk_nms_topk_metric(cand_box, cand_score, cand_cls, cand_loc, counts, N, cap, iou_thr, 0, topk, out_box, out_score, out_cls, out_loc,
+                               out_idx, out_count, sort_ws, stream);
 }

@@ -1073,7 +1073,13 @@ def fcos_select(logits: Sequence[torch.Tensor], regctr: Sequence[torch.Tensor], 
     return out
 
 
-def nms_topk(cand: dict, iou_thr: float, topk: int):
+NMS_METRICS = {"iou": 0, "ios": 1}       # include/cmk.h, cmk_nms_topk_metric
+
+
+def nms_topk(cand: dict, iou_thr: float, topk: int, metric: str = "iou"):
+    """metric "iou": the detector's NMS.  "ios": suppress on intersection over the smaller box > iou_thr (the merge of sliced inference)."""
+    if metric not in NMS_METRICS:
+        raise _lib.CmkError("nms_topk: metric must be one of {}, got {!r}".format(sorted(NMS_METRICS), metric))
     lib = _lib.load()
     n, cap = cand["score"].shape
     dev = cand["score"].device
@@ -1085,10 +1091,10 @@ def nms_topk(cand: dict, iou_thr: float, topk: int):
                idx=torch.empty((n, topk), dtype=torch.int32, device=dev),
                counts=torch.empty((n,), dtype=torch.int32, device=dev))
     ws = torch.empty((n, 4, cap), dtype=torch.int32, device=dev)
-    check(lib.cmk_nms_topk(cand["box"].data_ptr(), cand["score"].data_ptr(), cand["cls"].data_ptr(), cand["loc"].data_ptr(),
-                           cand["counts"].data_ptr(), n, cap, float(iou_thr), topk, out["box"].data_ptr(), out["score"].data_ptr(),
-                           out["cls"].data_ptr(), out["loc"].data_ptr(), out["idx"].data_ptr(), out["counts"].data_ptr(),
-                           ws.data_ptr(), _stream()), "cmk_nms_topk")
+    check(lib.cmk_nms_topk_metric(cand["box"].data_ptr(), cand["score"].data_ptr(), cand["cls"].data_ptr(), cand["loc"].data_ptr(),
+                                  cand["counts"].data_ptr(), n, cap, float(iou_thr), NMS_METRICS[metric], topk, out["box"].data_ptr(),
+                                  out["score"].data_ptr(), out["cls"].data_ptr(), out["loc"].data_ptr(), out["idx"].data_ptr(),
+                                  out["counts"].data_ptr(), ws.data_ptr(), _stream()), "cmk_nms_topk_metric")
     return out
 
 
@@ -1474,6 +1480,65 @@ def tta_reduce_masks(masks: torch.Tensor, flips: torch.Tensor, mask_scores: Opti
                                    count.data_ptr(), a, k, s, out.data_ptr(), out_ms.data_ptr() if out_ms is not None else None, _stream()),
           "cmk_tta_reduce_masks")
     return out, out_ms
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# sliced inference (modeling/sliced_inference.py): the tile grid, the per-pass table and the map back into the image frame
+# ---------------------------------------------------------------------------------------------------------------
+def slice_grid(h: int, w: int, tile_h: int, tile_w: int, overlap: float) -> List[Tuple[int, int, int, int]]:
+    """The tiles [(y0, x0, th, tw)] of an h x w image in row-major order.  th = min(tile_h, h), tw = min(tile_w, w); per axis the
+    stride is max(1, int(t * (1 - overlap))), the starts are 0, stride, 2 * stride, .. while start + t < size, and the last start is
+    size - t: the last tile is shifted back and ends on the image border.  Every tile has the same size; repeated windows are dropped."""
+    h, w, tile_h, tile_w = int(h), int(w), int(tile_h), int(tile_w)
+    if h < 1 or w < 1 or tile_h < 1 or tile_w < 1 or not 0.0 <= float(overlap) < 1.0:
+        raise ValueError("slice_grid: need a positive image and tile and 0 <= overlap < 1, got {}x{}, tile {}x{}, overlap {}".format(
+            h, w, tile_h, tile_w, overlap))
+
+    def starts(size, t):
+        stride = max(1, int(t * (1.0 - float(overlap))))
+        out, s = [], 0
+        while s + t < size:
+            out.append(s)
+            s += stride
+        if size - t not in out:
+            out.append(size - t)
+        return out
+
+    th, tw = min(tile_h, h), min(tile_w, w)
+    return [(y0, x0, th, tw) for y0 in starts(h, th) for x0 in starts(w, tw)]
+
+
+def slice_table(passes, device) -> torch.Tensor:
+    """The (A,6) float32 table of slice_boxes_to_image for passes [(y0, x0, th, tw, new_h, new_w)]: (x0, y0, rx, ry, tw, th) with
+    rx, ry = tw / new_w, th / new_h, each computed in double and rounded once to fp32."""
+    import numpy as np
+    rows = [(x0, y0, np.float32(tw / nw), np.float32(th / nh), tw, th) for y0, x0, th, tw, nh, nw in passes]
+    return torch.tensor(np.asarray(rows, dtype=np.float32)).to(device)
+
+
+def slice_boxes_to_image(det: dict, table: torch.Tensor, height: int, width: int) -> dict:
+    """det: the padded detections of A passes (box (A,K,4), score (A,K), cls (A,K) int64, loc (A,K,2), counts (A) int32) and their
+    slice_table -> one ops.nms_topk candidate set (1, A*K, ..) in the frame of the height x width image: scaled, shifted to the pass's
+    corner, clipped to the pass's window; compacted in pass order, counts = [the sum]; src (A*K) int32 = the padded slot a*K + k of
+    every candidate."""
+    lib = _lib.load()
+    if not torch.is_tensor(det["score"]) or det["score"].dim() != 2:
+        raise _lib.CmkError("slice_boxes_to_image: need (A,K) scores")
+    a, k = int(det["score"].shape[0]), int(det["score"].shape[1])
+    dev = det["score"].device
+    for name, dt, shp in (("box", torch.float32, (a, k, 4)), ("score", torch.float32, (a, k)), ("cls", torch.int64, (a, k)),
+                          ("loc", torch.float32, (a, k, 2)), ("counts", torch.int32, (a,))):
+        _need_tta(det[name], dt, shp, "slice_boxes_to_image " + name)
+    _need_tta(table, torch.float32, (a, 6), "slice_boxes_to_image table")
+    cap = a * k
+    cand = dict(box=torch.empty((1, cap, 4), dtype=torch.float32, device=dev), score=torch.empty((1, cap), dtype=torch.float32, device=dev),
+                cls=torch.empty((1, cap), dtype=torch.int32, device=dev), loc=torch.empty((1, cap, 2), dtype=torch.float32, device=dev),
+                counts=torch.empty((1,), dtype=torch.int32, device=dev), src=torch.empty((cap,), dtype=torch.int32, device=dev), cap=cap)
+    check(lib.cmk_slice_boxes_to_image(det["box"].data_ptr(), det["score"].data_ptr(), det["cls"].data_ptr(), det["loc"].data_ptr(),
+                                       det["counts"].data_ptr(), table.data_ptr(), a, k, int(width), int(height), cand["box"].data_ptr(),
+                                       cand["score"].data_ptr(), cand["cls"].data_ptr(), cand["loc"].data_ptr(), cand["src"].data_ptr(),
+                                       cand["counts"].data_ptr(), _stream()), "cmk_slice_boxes_to_image")
+    return cand
 
 
 def paste_masks(masks: torch.Tensor, boxes: torch.Tensor, height: int, width: int, threshold: float = 0.5) -> torch.Tensor:

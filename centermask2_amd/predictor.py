@@ -44,6 +44,10 @@ class Predictor:
         if self.input_format not in ("BGR", "RGB"):
             raise _lib.CmkError("Predictor: INPUT.FORMAT must be BGR or RGB, got {!r}".format(self.input_format))
         self.tta = None                         # cfg.TEST.AUG: multi-scale + flip inference, merged on the device
+        self.sliced = None                      # cfg.TEST.SLICE: overlapping tiles at the model's test size, merged on the device
+        if cfg.TEST.SLICE.ENABLED:              # refuses TEST.AUG.ENABLED beside it
+            from .modeling.sliced_inference import SlicedInference
+            self.sliced = SlicedInference(cfg, self.model)
         if cfg.TEST.AUG.ENABLED:
             from .modeling.test_time_augmentation import GeneralizedRCNNWithTTA
             self.tta = GeneralizedRCNNWithTTA(cfg, self.model)
@@ -63,6 +67,9 @@ class Predictor:
     def predict_batch(self, images: Sequence) -> List[Dict[str, Instances]]:
         """One model call over raw BGR images that may differ in size; results at each image's own resolution."""
         raw = [self._upload(im) for im in images]
+        if self.sliced is not None:
+            return [{"instances": self.sliced.inference_one_image(im, int(im.shape[0]), int(im.shape[1]),
+                                                                  reverse_channels=self.input_format == "RGB")} for im in raw]
         if self.tta is not None:
             return [{"instances": self.tta.inference_one_image(im, int(im.shape[0]), int(im.shape[1]),
                                                                reverse_channels=self.input_format == "RGB")} for im in raw]

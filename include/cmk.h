@@ -354,6 +354,18 @@ int cmk_nms_topk(const float* cand_box, const float* cand_score, const int32_t* 
                  const int32_t* counts, int N, int cap, float iou_thr, int topk,
                  float* out_box /* N*topk*4 */, float* out_score, int64_t* out_cls, float* out_loc, int32_t* out_idx,
                  int32_t* out_count /* N */, uint32_t* sort_ws, void* stream);
+/* The same launch with the overlap measure as an argument; cmk_nms_topk forwards here with metric 0.
+ *   metric 0   IoU: inter / (area_a + area_b - inter), the arithmetic and the bits of cmk_nms_topk.
+ *   metric 1   IoS, intersection over the smaller box: inter / fminf(area_a, area_b).  A box nested in a larger one of its class scores
+ *              1 however small it is.  A zero smaller area gives 0 / 0 = NaN, which is not > thr: such a box suppresses nothing and is
+ *              not suppressed.
+ * A candidate is suppressed when its measure with a kept box exceeds thr.  The sort, the class separation (coordinate trick below 40000
+ * candidates, per class from there on), the top-k limit and out_idx are those of cmk_nms_topk.  Refused: what cmk_nms_topk refuses, and
+ * a metric other than 0 or 1. */
+int cmk_nms_topk_metric(const float* cand_box, const float* cand_score, const int32_t* cand_cls, const float* cand_loc,
+                        const int32_t* counts, int N, int cap, float thr, int metric, int topk,
+                        float* out_box /* N*topk*4 */, float* out_score, int64_t* out_cls, float* out_loc, int32_t* out_idx,
+                        int32_t* out_count /* N */, uint32_t* sort_ws, void* stream);
 
 /* ---- multi-level ROIAlignV2 with CenterMask's ratio level assignment (pooler.py:80-118,290-366) ---------------- */
 int cmk_roi_align_ratio(const float* const* feats /* host array of device pointers */, const int* feat_h, const int* feat_w,
@@ -467,6 +479,24 @@ int cmk_tta_boxes_to_aug(const float* box, const int32_t* count, const float* ta
                          void* stream);
 int cmk_tta_reduce_masks(const float* masks, const int32_t* flips, const float* mask_scores, const int32_t* count, int A, int K, int S,
                          float* out_masks, float* out_scores, void* stream);
+
+/* ---- sliced inference (TEST.SLICE, modeling/sliced_inference.py): a large image cut into T equal, overlapping tiles, every tile resized
+ * by the ordinary test rule to new_h x new_w and run as a pass of its own, optionally the whole image as pass T; the detections of all
+ * A = T (+ 1) passes mapped back and merged by cmk_nms_topk_metric.
+ * The map takes a per-pass table in DEVICE memory, 6 floats each: (x0, y0, rx, ry, tw, th) with (x0, y0) the tile's corner in the image,
+ * tw x th its size there, rx = tw / new_w and ry = th / new_h computed in double on the host and rounded once to fp32 (the whole image:
+ * x0 = y0 = 0, tw x th the image).  Every step is one fp32 operation, nothing is fused.
+ *   cmk_slice_boxes_to_image   det_* are the padded (A,K,..) outputs of the passes, det_counts (A) clamped to [0, K].  Per valid detection:
+ *                              x' = x * rx, then x' + x0, the same for y; then clipped to the pass's own window [x0, x0 + tw] x
+ *                              [y0, y0 + th] (the bounds are one fp32 addition each).  loc is mapped as a point by the same rule, without
+ *                              the clip; score is copied, cls narrowed to int32.  Candidates are written compacted in pass order and in
+ *                              the detector's order within a pass; cand_count[0] = the sum of the clamped counts; cand_src (A*K) int32
+ *                              receives a*K + k, the padded slot the candidate came from (what a mask gather indexes with).  Rows at
+ *                              and beyond each count are never read; outputs beyond cand_count[0] are not written.
+ * Refused: null pointers, A < 1 or A > 4096, K < 1 or K > 65535, img_w / img_h not in [1, 65535], boxes not 16-byte aligned. ----------- */
+int cmk_slice_boxes_to_image(const float* det_box, const float* det_score, const int64_t* det_cls, const float* det_loc,
+                             const int32_t* det_counts, const float* table, int A, int K, int img_w, int img_h, float* cand_box,
+                             float* cand_score, int32_t* cand_cls, float* cand_loc, int32_t* cand_src, int32_t* cand_count, void* stream);
 
 /* ---- output side: paste (R,S,S) soft masks into (R,H,W) uint8 bitmasks at `threshold` (deploy_utils.py:151-156 ->
  * d2 ROIMasks.to_bitmasks: bilinear grid_sample, align_corners=False, zero padding); boxes (R,4) are the rescaled and
